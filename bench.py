@@ -13,10 +13,17 @@ A "step" is one pass of the hot path over one batch of B synthetic frames per GP
 (cycled from a >= 1 GB device pool so they are not cache resident).  Rank 0 prints ONE JSON line.
 
 Default = the parity-grade throughput mode: bf16x3 (split-bf16 MFMA operands, three MFMAs per product, fp32 accumulate and
-master weights; losses ~1e-7 and gradients ~1e-4 of their maximum against float64, tests/test_gpu_fused.py).  The same line
-carries, measured in the same process (N = 1): `parity_mode` (the exact-fp32-MFMA policy and the one-bf16-per-operand fast
-mode), `spread` (5 more repeats of the timed region), `b128` (the reference scripts' batch size, GPU and CPU) and
-`cpu_baseline` (oracle/torch_ref.py on the host cores: all granted cores, and one thread).
+master weights; losses ~1e-7 and gradients ~1e-4 of their maximum against float64, tests/test_gpu_fused.py).
+
+A plain run sets up, pre-warms, warms up, times the K steps and prints the line.  `--full` adds, measured in the same process:
+`roofline` (per-kernel device times of 50 more steps), and for N = 1 `parity_mode` (the exact-fp32-MFMA policy and the
+one-bf16-per-operand fast mode), `spread` (5 more repeats of the timed region), `b128` (the reference scripts' batch size, GPU and
+CPU), `large_batch`, `encoder_gemm`, `side_kernels` (STFT / ISTFT / MCEM) and `cpu_baseline` (oracle/torch_ref.py on the host
+cores: all granted cores, and one thread); `--no-extras` / `--no-cpu-baseline` trim that set.
+
+`--dump-outputs DIR` writes what the timed path returned in its last step (the loss vector) and the parameters after the K updates
+as float32 DIR/<name>.npy files.  The inputs are seeded and the pre-warm steps run on a trainer of their own, so that the same
+arguments give the same outputs from run to run and two builds can be compared output for output.
 """
 import argparse
 import importlib
@@ -50,8 +57,13 @@ def parse():
                     help="MFMA operand policy of the fused path: bf16x3 = split bf16 (parity grade), bf16 = one bf16 per operand (fast, loose), fp32 = exact fp32 MFMA")
     ap.add_argument("--pool-gb", type=float, default=1.0)
     ap.add_argument("--ksplit", type=int, default=0, help="frame-axis slices of the weight-gradient kernel (0 = library default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip parity_mode / spread / b128 (they run outside the timed region)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements outside the headline figure: roofline (per-kernel times), parity_mode, spread, b128, large_batch, "
+                         "encoder_gemm, side_kernels and cpu_baseline; a plain run only times the K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's losses and the parameters after the K updates to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip parity_mode / spread / b128 (they run outside the timed region)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--prewarm-ms", type=float, default=200.0,
                     help="untimed train steps for this long BEFORE the W warmup steps, so that the K timed steps run at the clocks a training run "
@@ -368,6 +380,24 @@ def timed_steps(impl, batches, first, steps, dist, device):
     return dt, last
 
 
+def dump_outputs(path, impl, last, max_bytes=64 << 20):
+    """--dump-outputs: the loss vector the last timed step returned and every parameter after the K updates, float32, one .npy each
+    (M2 y 513: 1.2 MB in all)."""
+    import numpy as np
+    if hasattr(impl, "tr"):
+        params = impl.tr.state_dict_numpy()
+    else:
+        params = {k: v.detach().cpu().numpy() for k, v in impl.m.state_dict().items()}
+    out = {"losses": last.detach().reshape(-1).float().cpu().numpy()}
+    out.update({"param." + k: np.asarray(v, dtype=np.float32) for k, v in params.items()})
+    total = sum(v.nbytes for v in out.values())
+    if total > max_bytes:
+        raise SystemExit(f"--dump-outputs: {total} bytes, more than {max_bytes}")
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def launch_ranks(a):
     """`bench.py --gpus N` with N > 1 and no launcher (WORLD_SIZE unset): this process starts N fresh ranks -- `python -m
     torch.distributed.run --nproc-per-node N ... bench.py <same arguments>` as a CHILD process -- before it has made a single GPU call
@@ -466,18 +496,23 @@ def main():
             if a.impl == "fused":
                 raise SystemExit(f"fused train step does not cover {a.model} {dims}")
             impl_name = "modules"
-    if impl_name == "fused":
-        impl = trainer_mod.BenchImpl(a.model, dims, B, device, world, a.precision, ksplit=a.ksplit)
-    else:
-        impl = ModulesImpl(a.model, dims, device, world)
+
+    def make_impl():
+        if impl_name == "fused":
+            return trainer_mod.BenchImpl(a.model, dims, B, device, world, a.precision, ksplit=a.ksplit)
+        return ModulesImpl(a.model, dims, device, world)
+    impl = make_impl()
 
     prewarm_steps = 0
     if a.prewarm_ms > 0:                                                            # untimed: bring the GPU to its sustained clocks
+        # on a second trainer of the same seed: the number of pre-warm steps depends on the clock, so the timed trainer starts from
+        # the same state in every run and its outputs (--dump-outputs) do not depend on how fast the pre-warm went
+        pre = make_impl()
         torch.cuda.synchronize()
         t_pw = time.perf_counter()
         while True:
             for i in range(50):
-                impl.step(*batches[(prewarm_steps + i) % nb])
+                pre.step(*batches[(prewarm_steps + i) % nb])
             prewarm_steps += 50
             torch.cuda.synchronize()
             go = torch.tensor([1 if (time.perf_counter() - t_pw) * 1e3 < a.prewarm_ms else 0], dtype=torch.int32,
@@ -490,15 +525,17 @@ def main():
         impl.step(*batches[i % nb])
     dt, last = timed_steps(impl, batches, a.warmup, a.steps, dist, device)          # THE timed region: exactly K steps
     final_loss = float(last.reshape(-1)[0].item()) if last is not None else float("nan")
+    if a.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(a.dump_outputs, impl, last)
 
-    extras = not a.no_extras
+    extras = a.full and not a.no_extras
     spread = None
     if extras:                                                                      # run-to-run spread inside the process
         reps = [1e3 * timed_steps(impl, batches, a.warmup + (r + 1) * a.steps, a.steps, dist, device)[0] / a.steps for r in range(5)]
         spread = {"repeats": 5, "steps_each": a.steps, "ms_per_step_min": min(reps), "ms_per_step_median": statistics.median(reps),
                   "ms_per_step_max": max(reps), "note": "five more repeats of the timed region, after it"}
 
-    prof = impl.kernel_profile(batches, min(a.steps, 50))
+    prof = impl.kernel_profile(batches, min(a.steps, 50)) if a.full else None
     direct_rec = None
     if (world > 1 and impl_name == "fused" and os.environ.get("DVAE_ALLREDUCE", "rccl") == "rccl"
             and (a.direct_trial or os.environ.get("DVAE_BENCH_DIRECT_TRIAL", "0") == "1")):
@@ -618,7 +655,7 @@ def main():
                 # one figure per side kernel: microseconds per launch (STFT / ISTFT of ten minutes of audio); MCEM: milliseconds per EM iteration of 25 utterances (batched), per utterance (single)
                 out["roofline"]["side_kernels"] = {k: (round(v["us"], 1) if "us" in v else round(v.get("ms_per_utterance", v.get("ms_per_em_iteration", 0.0)), 3))
                                                    for k, v in sk.items() if isinstance(v, dict)}
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.model, dims, B, a.cpu_seconds)
             if "b128" in out:
                 v, n, dtc, thr = cpu_steps_per_s(a.model, dims, 128, 3.0, host_cores())

@@ -34,7 +34,8 @@ def pytest_collection_modifyitems(config, items):
 
 @pytest.fixture(scope="session")
 def vae_golden():
-    return np.load(os.path.join(HERE, "golden", "vae_golden.npz"))
+    import golden_util as gu
+    return gu.load_golden("vae_golden")
 
 
 @pytest.fixture(scope="session")

@@ -1,6 +1,6 @@
 """Measured deviation of the benchmarked operand policy (bf16x3) -- and of the fp32 / bf16 policies beside it -- per configuration:
 (a) one 8192-frame train step against the float64 numpy oracle (losses: relative; gradients: worst |err| / max|ref| per tensor);
-(b) the reference-captured golden vectors (tests/golden/vae_golden.npz, step 1) through Trainer(precision=...): the same two figures.
+(b) the reference-captured golden vectors (tests/golden/vae_golden.part*.npz, step 1) through Trainer(precision=...): the same two figures.
 Writes profiles-style JSON to the path given (default gpurun_out/r03_parity.json).  Test infrastructure: uses oracle/ as the checker."""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -48,7 +48,7 @@ for prec in ("fp32", "bf16x3"):
         per_clean[k] = float(rows[2]) if rows.size > 2 else float(rows[-1])            # third-worst row: outside <= 2 ReLU-tie rows
     res["oracle_8192"][f"M2_info_y1_{prec}"] = {"loss_rel": float(np.max(np.abs(losses[:7] - ref) / (np.abs(ref) + 1e-5))), "grad_relmax_worst": max(per.values()),
                                                "grad_relmax_worst_tensor": max(per, key=per.get), "grad_relmax_worst_outside_2_rows_per_tensor": max(per_clean.values())}
-fix = np.load(os.path.join(ROOT, "tests", "golden", "vae_golden.npz"))
+fix = gu.load_golden("vae_golden")
 for case in gu.CASES:
     name, model, dims, B, wscale = case
     if "full" not in name:

@@ -1,10 +1,10 @@
 """Capture golden vectors by running the REFERENCE ITSELF (CPU, fp32) on
 deterministic inputs.  Build-container only (imports /root/reference read-only):
 
-    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py          # -> vae_golden.npz (golden_util.CASES, B <= 32)
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py          # -> vae_golden.part*.npz (golden_util.CASES, B <= 32)
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py --big    # -> vae_golden_b8192.npz (golden_util.BIG_CASES: the benchmarked 8192-frame batch)
 
-Output: tests/golden/vae_golden.npz -- data only (inputs are regenerated from
+Output: tests/golden/vae_golden.part*.npz -- data only (inputs are regenerated from
 seeds by tests/golden_util.py; a checksum of them is stored).  For each case
 of golden_util.CASES it runs NSTEPS iterations of the reference loop body
 (scripts/training_M1.py:134-139, scripts/training_M2.py:142-147,
@@ -164,9 +164,12 @@ def main():
         x = torch.rand(32, 513) ** 2
         r, mu, lv = m(x)
         fix["kat_m1_seed0_elbo"] = np.array([t.item() for t in elbo(x, r, mu, lv, 1e-8)])
-        out = os.path.join(HERE, "vae_golden.npz")
-    np.savez_compressed(out, **fix)
-    print("wrote", out, os.path.getsize(out), "bytes", len(fix), "arrays")
+        out = None
+    if out is not None:
+        np.savez_compressed(out, **fix)
+    else:
+        out = ", ".join(gu.save_golden("vae_golden", fix))
+    print("wrote", out, len(fix), "arrays")
     print("torch", torch.__version__, "numpy", np.__version__)
 
 

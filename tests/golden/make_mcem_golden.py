@@ -5,7 +5,7 @@ packages/models/mcem.py classes (CPU, fp32).  Build-container only (imports /roo
 
 Every torch.rand / torch.randn the reference draws is recorded (in call order) and stored, so the
 oracle and the HIP kernels can be run on exactly the same noise.  Output:
-tests/golden/mcem_golden.npz (data only).
+tests/golden/mcem_golden.part*.npz (data only).
 """
 import os
 import sys
@@ -123,9 +123,7 @@ def main():
         for k, v in fix.items():
             out[f"{case['name']}/{k}"] = v
         print(case["name"], "cost", fix["cost"], "acc Z moved", float(np.abs(fix["Z"][0] - fix["Z0"]).mean()), flush=True)
-    path = os.path.join(HERE, "mcem_golden.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+    print("wrote", gu.save_golden("mcem_golden", out))
 
 
 if __name__ == "__main__":

@@ -106,6 +106,53 @@ import sys as _sys
 _sys.path.insert(0, _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__))))
 make_batch = _importlib.import_module("disentangled-vae_amd.synth").make_batch    # the benchmark's generator: one definition
 
+GOLDEN_DIR = _os.path.join(_os.path.dirname(_os.path.abspath(__file__)), "golden")
+PART_BYTES = 900 * 1024          # every committed file stays under 1 MiB
+
+
+class GoldenArchive(dict):
+    """The arrays of one fixture by name; `.files` as on the NpzFile of np.load."""
+    @property
+    def files(self):
+        return list(self)
+
+
+def _parts(stem):
+    import glob
+    return sorted(glob.glob(_os.path.join(GOLDEN_DIR, stem + ".part*.npz")), key=lambda p: int(p.rsplit(".part", 1)[1][:-4]))
+
+
+def load_golden(stem):
+    """tests/golden/<stem>.part<i>.npz, i = 0, 1, ...: one fixture stored in parts, read back as one archive."""
+    parts = _parts(stem)
+    assert parts, f"no tests/golden/{stem}.part*.npz"
+    out = GoldenArchive()
+    for p in parts:
+        with np.load(p) as f:
+            out.update({k: f[k] for k in f.files})
+    return out
+
+
+def save_golden(stem, arrays, part_bytes=PART_BYTES):
+    """np.savez_compressed of `arrays` into tests/golden/<stem>.part<i>.npz files of at most ~part_bytes each (in key order)."""
+    import zlib
+    for p in _parts(stem):
+        _os.remove(p)
+    groups, cur, size = [], {}, 0
+    for k, v in arrays.items():
+        n = len(zlib.compress(np.ascontiguousarray(v).tobytes(), 6)) + 256
+        if cur and size + n > part_bytes:
+            groups.append(cur)
+            cur, size = {}, 0
+        cur[k], size = v, size + n
+    groups.append(cur)
+    paths = []
+    for i, g in enumerate(groups):
+        paths.append(_os.path.join(GOLDEN_DIR, f"{stem}.part{i}.npz"))
+        np.savez_compressed(paths[-1], **g)
+        assert _os.path.getsize(paths[-1]) < 1 << 20, paths[-1]
+    return paths
+
 
 def checksum(arrs):
     s = 0.0

@@ -15,7 +15,7 @@ from oracle import mcem_oracle as mo
 pytestmark = pytest.mark.gpu
 mcem_dev = importlib.import_module("disentangled-vae_amd.mcem")
 
-FIX = np.load(os.path.join(os.path.dirname(__file__), "golden", "mcem_golden.npz"))
+FIX = gu.load_golden("mcem_golden")
 
 
 def case_fix(name):

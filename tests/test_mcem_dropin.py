@@ -14,7 +14,7 @@ import mcem_cases as mc
 from impl_modules import build_model
 from packages.models import mcem
 
-FIX = np.load(os.path.join(os.path.dirname(__file__), "golden", "mcem_golden.npz"))
+FIX = gu.load_golden("mcem_golden")
 CLS = {"M1": mcem.MCEM_M1, "M2": mcem.MCEM_M2, "M2_info": mcem.MCEM_M2v3}
 
 

@@ -10,7 +10,7 @@ import golden_util as gu
 from oracle import mcem_oracle as mo
 from oracle import vae_oracle as vo
 
-FIX = np.load(os.path.join(os.path.dirname(__file__), "golden", "mcem_golden.npz"))
+FIX = gu.load_golden("mcem_golden")
 
 
 def case_fix(name):

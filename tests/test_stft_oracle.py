@@ -28,27 +28,20 @@ def test_oracle_reproduces_reference_h5_power_frames(stft_golden, utt):
     assert ibm.shape == f[utt + "_Y_ibm"].shape
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/data/subset"), reason="reference data not present (GPU box)")
-def test_oracle_reproduces_whole_reference_h5(stft_golden):
-    """Build-container only: whole wavs against all 201 X_train frames + IBM labels + mean/std."""
-    import subprocess, tempfile
-    from scipy.io import wavfile
-    tmp = tempfile.mkdtemp()
-    code = ("import h5py,numpy as np;f=h5py.File('/root/reference/data/subset/processed/ntcd_timit/"
-            "Clean_ibm_labels_upsampled.h5','r');np.savez('%s/m.npz',**{k:f[k][:] for k in f})" % tmp)
-    subprocess.check_call(["/opt/conda/bin/python3.9", "-c", code])
-    h5 = np.load(tmp + "/m.npz")
-    specs = []
+def test_oracle_reproduces_whole_reference_h5():
+    """Whole wavs against all 201 X_train frames + IBM labels of the reference's h5 (tests/golden/stft_whole_fixture.part*.npz,
+    tests/golden/make_stft_whole_golden.py)."""
+    import golden_util as gu
+    f = gu.load_golden("stft_whole_fixture")
     for j, u in enumerate(["sa1", "sa2", "si462"]):
-        fs, w = wavfile.read(f"/root/reference/data/subset/raw/ntcd_timit/Clean/volunteers/01M/straightcam/{u}.wav")
+        w = f["01M_" + u + "_wav_i16"]
         x = w.astype(np.float64) / 32768.0
         x = x / np.max(np.abs(x))
         S = so.stft(x, **KW)
         P = (np.abs(S) ** 2)
-        specs.append(P[:, :67])
-        np.testing.assert_allclose(P[:, :67].astype(np.float32), h5["X_train"][:, 67 * j:67 * (j + 1)], rtol=3e-7)
+        np.testing.assert_allclose(P[:, :67].astype(np.float32), f["X_train"][:, 67 * j:67 * (j + 1)], rtol=3e-7)
         ibm = (20 * np.log10(np.abs(S) + 1e-8) > np.max(20 * np.log10(np.abs(S) + 1e-8)) - 50).astype(np.float32)
-        assert np.array_equal(ibm[:, :67], h5["Y_train"][:, 67 * j:67 * (j + 1)])
+        assert np.array_equal(ibm[:, :67], f["Y_train"][:, 67 * j:67 * (j + 1)])
 
 
 def test_oracle_vs_torch_stft_and_istft():

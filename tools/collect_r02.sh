@@ -3,16 +3,16 @@
 # for the headline configuration under both bf16 policies.  Outputs land in gpurun_out/r02/ and are copied into profiles/ by hand.
 set -e
 O=gpurun_out/r02; mkdir -p $O
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --model M1 --no-extras > $O/bench_M1.json 2>/dev/null
-python bench.py --model M2 --y-dim 1 --no-extras > $O/bench_M2_y1.json 2>/dev/null
-python bench.py --model M2_info --precision bf16x3 --no-extras > $O/bench_M2_info.json 2>/dev/null
-python bench.py --batch 1048576 --steps 20 --warmup 5 --pool-gb 8 --no-extras --no-cpu-baseline > $O/bench_B1048576.json 2>/dev/null
-python bench.py --batch 65536 --steps 50 --warmup 10 --pool-gb 4 --no-extras --no-cpu-baseline > $O/bench_B65536.json 2>/dev/null
-python bench.py --precision bf16 --batch 1048576 --steps 20 --warmup 5 --pool-gb 8 --no-extras --no-cpu-baseline > $O/bench_bf16_B1048576.json 2>/dev/null
-python bench.py --impl modules --steps 2000 --warmup 300 --no-extras --no-cpu-baseline > $O/bench_modules_B8192.json 2>/dev/null
-python bench.py --impl modules --batch 128 --steps 2000 --warmup 300 --no-extras --no-cpu-baseline > $O/bench_modules_B128.json 2>/dev/null
-DVAE_MODULE_PATH=layers python bench.py --impl modules --batch 128 --steps 500 --warmup 100 --no-extras --no-cpu-baseline > $O/bench_modules_layers_B128.json 2>/dev/null
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --model M1 --no-extras > $O/bench_M1.json 2>/dev/null
+python bench.py --full --model M2 --y-dim 1 --no-extras > $O/bench_M2_y1.json 2>/dev/null
+python bench.py --full --model M2_info --precision bf16x3 --no-extras > $O/bench_M2_info.json 2>/dev/null
+python bench.py --full --batch 1048576 --steps 20 --warmup 5 --pool-gb 8 --no-extras --no-cpu-baseline > $O/bench_B1048576.json 2>/dev/null
+python bench.py --full --batch 65536 --steps 50 --warmup 10 --pool-gb 4 --no-extras --no-cpu-baseline > $O/bench_B65536.json 2>/dev/null
+python bench.py --full --precision bf16 --batch 1048576 --steps 20 --warmup 5 --pool-gb 8 --no-extras --no-cpu-baseline > $O/bench_bf16_B1048576.json 2>/dev/null
+python bench.py --full --impl modules --steps 2000 --warmup 300 --no-extras --no-cpu-baseline > $O/bench_modules_B8192.json 2>/dev/null
+python bench.py --full --impl modules --batch 128 --steps 2000 --warmup 300 --no-extras --no-cpu-baseline > $O/bench_modules_B128.json 2>/dev/null
+DVAE_MODULE_PATH=layers python bench.py --full --impl modules --batch 128 --steps 500 --warmup 100 --no-extras --no-cpu-baseline > $O/bench_modules_layers_B128.json 2>/dev/null
 tools/pmc_collect.sh x3 --precision bf16x3 > $O/pmc_x3.log 2>&1
 python tools/pmc_summary.py gpurun_out/pmc_x3 $O/pmc_M2_y513_B8192_bf16x3.json M2 513 8192 bf16x3 > $O/pmc_x3_summary.txt
 tools/pmc_collect.sh bf --precision bf16 > $O/pmc_bf.log 2>&1

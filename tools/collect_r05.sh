@@ -4,21 +4,21 @@
 #   part 2 (argument "pmc"): rocprofv3 kernel stats + counter passes (incl. the per-class instruction split) of the headline configuration and of M2_info, side kernels
 O=gpurun_out/r05c; mkdir -p $O
 if [ "$1" != "pmc" ]; then
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --model M1 --no-extras > $O/bench_M1.json 2>/dev/null
-python bench.py --model M2 --y-dim 1 --no-extras > $O/bench_M2_y1.json 2>/dev/null
-python bench.py --model M2_info --no-extras > $O/bench_M2_info.json 2>/dev/null
-python bench.py --precision fp32 --no-extras --no-cpu-baseline > $O/bench_fp32.json 2>/dev/null
-python bench.py --batch 1048576 --steps 20 --warmup 5 --pool-gb 8 --no-extras --no-cpu-baseline > $O/bench_B1048576.json 2>/dev/null
-python bench.py --batch 65536 --steps 50 --warmup 10 --pool-gb 4 --no-extras --no-cpu-baseline > $O/bench_B65536.json 2>/dev/null
-python bench.py --impl modules --steps 1000 --warmup 200 --no-extras --no-cpu-baseline > $O/bench_modules_B8192.json 2>/dev/null
-python bench.py --impl modules --batch 128 --steps 1000 --warmup 200 --no-extras --no-cpu-baseline > $O/bench_modules_B128.json 2>/dev/null
-python bench.py --impl modules --model M2_info --steps 300 --warmup 50 --no-extras --no-cpu-baseline > $O/bench_modules_M2_info.json 2>/dev/null
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --model M1 --no-extras > $O/bench_M1.json 2>/dev/null
+python bench.py --full --model M2 --y-dim 1 --no-extras > $O/bench_M2_y1.json 2>/dev/null
+python bench.py --full --model M2_info --no-extras > $O/bench_M2_info.json 2>/dev/null
+python bench.py --full --precision fp32 --no-extras --no-cpu-baseline > $O/bench_fp32.json 2>/dev/null
+python bench.py --full --batch 1048576 --steps 20 --warmup 5 --pool-gb 8 --no-extras --no-cpu-baseline > $O/bench_B1048576.json 2>/dev/null
+python bench.py --full --batch 65536 --steps 50 --warmup 10 --pool-gb 4 --no-extras --no-cpu-baseline > $O/bench_B65536.json 2>/dev/null
+python bench.py --full --impl modules --steps 1000 --warmup 200 --no-extras --no-cpu-baseline > $O/bench_modules_B8192.json 2>/dev/null
+python bench.py --full --impl modules --batch 128 --steps 1000 --warmup 200 --no-extras --no-cpu-baseline > $O/bench_modules_B128.json 2>/dev/null
+python bench.py --full --impl modules --model M2_info --steps 300 --warmup 50 --no-extras --no-cpu-baseline > $O/bench_modules_M2_info.json 2>/dev/null
 python tools/bench_stft.py > $O/bench_stft.json 2>/dev/null
 python tools/bench_mcem.py --batch 8 25 > $O/bench_mcem.json 2>/dev/null
 # the N > 1 line as the driver would ask for it (no launcher in the environment): bench.py starts the ranks itself; gloo lets the two ranks share the one GPU
-DVAE_DIST_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 2 --steps 20 --warmup 5 --batch 4096 --no-extras --no-cpu-baseline > $O/bench_2rank_selflaunch_gloo_rehearsal.json 2> $O/bench_2rank_selflaunch.err
-timeout -k 10 120 python bench.py --gpus 2 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $O/bench_2rank_rccl_on_one_gpu.out 2> $O/bench_2rank_rccl_on_one_gpu.err; echo "exit code $?" >> $O/bench_2rank_rccl_on_one_gpu.err
+DVAE_DIST_BACKEND=gloo timeout -k 10 300 python bench.py --full --gpus 2 --steps 20 --warmup 5 --batch 4096 --no-extras --no-cpu-baseline > $O/bench_2rank_selflaunch_gloo_rehearsal.json 2> $O/bench_2rank_selflaunch.err
+timeout -k 10 120 python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $O/bench_2rank_rccl_on_one_gpu.out 2> $O/bench_2rank_rccl_on_one_gpu.err; echo "exit code $?" >> $O/bench_2rank_rccl_on_one_gpu.err
 python tools/stamp_rows.py bf16x3 8192 > $O/stamps_bf16x3.txt 2>/dev/null
 else
 tools/pmc_collect.sh x3 --precision bf16x3 > $O/pmc_x3.log 2>&1

@@ -9,7 +9,7 @@ if [ "$1" = "run" ]; then
     for so in $V/*.so; do
         n=$(basename $so .so)
         for p in bf16x3 bf16; do
-            DVAE_ROWS=2 DVAE_LIB=$PWD/$so python bench.py --no-extras --precision $p --steps 200 --warmup 50 --no-cpu-baseline 2>/dev/null | python -c "
+            DVAE_ROWS=2 DVAE_LIB=$PWD/$so python bench.py --full --no-extras --precision $p --steps 200 --warmup 50 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('$n $p', round(d['ms_per_step']*1e3,1), 'us/step', {k:round(v,1) for k,v in d['roofline']['avg_us'].items()})"

@@ -6,7 +6,7 @@ for spec in "$@"; do
   DVAE_CFLAGS="$fl" python disentangled-vae_amd/build.py --force > /dev/null 2>&1
   python - <<PY
 import json, subprocess, sys
-out = subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline", "--no-extras", "--steps", "300", "--warmup", "30", "--ksplit", "$ks", "--precision", "$pr"], capture_output=True, text=True).stdout.strip().splitlines()[-1]
+out = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--no-extras", "--steps", "300", "--warmup", "30", "--ksplit", "$ks", "--precision", "$pr"], capture_output=True, text=True).stdout.strip().splitlines()[-1]
 r = json.loads(out)
 print(repr("$fl"), "ks $ks $pr", "us/step", round(r["ms_per_step"]*1e3, 2), {k: round(v, 2) for k, v in r["roofline"]["avg_us"].items()}, flush=True)
 PY

@@ -3,7 +3,7 @@
 # uniform / class-sliced schedule -- alternating, 2 rounds
 cd $GRAFT_REPO_ROOT
 one() { lib=$PWD/disentangled-vae_amd/build/variants/$1.so; [ "$1" = base ] && lib=$PWD/disentangled-vae_amd/libdvae_hip.so
-  DVAE_LIB=$lib python bench.py --no-extras --steps 300 --warmup 30 --no-cpu-baseline 2>/dev/null | python -c "
+  DVAE_LIB=$lib python bench.py --full --no-extras --steps 300 --warmup 30 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$1', '$2', round(d['ms_per_step']*1e3,1), 'us/step', {k:round(v,1) for k,v in d['roofline']['avg_us'].items()}, flush=True)"; }

@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU box: class-sliced weight-gradient schedule (default) against the uniform one (DVAE_W4_UNIFORM=1), alternating, several configurations
 cd $GRAFT_REPO_ROOT
-one() { python bench.py --no-extras --steps 300 --warmup 30 --no-cpu-baseline $2 2>/dev/null | python -c "
+one() { python bench.py --full --no-extras --steps 300 --warmup 30 --no-cpu-baseline $2 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$1', '$2', round(d['ms_per_step']*1e3,1), 'us/step', {k:round(v,1) for k,v in d['roofline']['avg_us'].items()}, flush=True)"; }
