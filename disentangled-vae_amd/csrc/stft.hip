@@ -330,6 +330,25 @@ __global__ __launch_bounds__(256) void stft1024_kernel(const TIN* __restrict__ x
     }
 }
 
+// Ragged batches: `pref` [U + 1] is the prefix of the per-utterance work-item counts (pref[0] = 0); item i belongs to the utterance u
+// with pref[u] <= i < pref[u + 1] (a binary search with wave-uniform addresses: scalar loads).  u = -1 past the last item.
+struct BatchItem { int u; int64_t local; };
+__device__ __forceinline__ int64_t uni64(int64_t v) {          // a wave-uniform 64-bit value in scalar registers
+    const uint64_t w = (uint64_t)v;
+    return (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(w >> 32)) << 32) |
+                     (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)w));
+}
+__device__ __forceinline__ BatchItem batch_item(const int64_t* __restrict__ pref, int U, int64_t item) {
+    if (U < 1 || item < 0 || item >= uni64(pref[U])) return BatchItem{-1, 0};
+    int lo = 0, hi = U;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (uni64(pref[mid]) <= item) lo = mid; else hi = mid;
+    }
+    const int64_t local = item - uni64(pref[lo]);
+    return local < 0 ? BatchItem{-1, 0} : BatchItem{lo, local};
+}
+
 // hop = 256 (every caller of the reference), frame-major outputs: the walk of stft1024_kernel<., 1 / 2> with the per-frame VALU work that is
 // not the transform taken out.  Round 3 measured the walk at ~100 % VALU issue (2 waves per SIMD, 520 VALU instructions per frame, 282 of them
 // fp64 transform arithmetic); the rest was (a) 48 v_mov_b64 rotating the six carried sample pairs from one frame's slots into the next, (b) ~80
@@ -341,9 +360,14 @@ __global__ __launch_bounds__(256) void stft1024_kernel(const TIN* __restrict__ x
 // not the correctly rounded sqrtf: its square is within ~2 ulp of np.abs(complex64) ** 2, inside the 4e-7 relative bound at which
 // tests/test_gpu_stft.py pins the reference's HDF5 power frames; |X|^2 below 1.2e-38 -- where the reference's own result is a denormal
 // or zero -- gives 0: parity for denormal magnitudes is unpinned by any reference fixture).
-template <typename TIN, bool POWER, bool OCC3>
+//
+// BATCH (dvae_stft_batch): the same walk over a ragged batch.  A wave's work item is one utterance and a run of at most `chunk` of its
+// frames; tab = [item prefix (U + 1) | first output frame (U + 1) | first signal sample (U)] (int64, see batch_item).  The buffer
+// descriptors are built from the utterance's own base address, so the 32-bit byte-offset limit holds per utterance, not per batch.
+template <typename TIN, bool POWER, bool OCC3, bool BATCH = false>
 __global__ __launch_bounds__(256, OCC3 ? 3 : 2) void stft1024_walk_kernel(const TIN* __restrict__ x, int64_t n, const double* __restrict__ window, int64_t T, int chunk,
-                                                             void* out) {
+                                                             void* out, const int64_t* __restrict__ tab = nullptr, int U = 0) {
+    static_assert(!(BATCH && OCC3), "the batch walk has the two-wave form only");
     constexpr int M = 512, F = 513;
     constexpr int ESZ = POWER ? 4 : 8;
     __shared__ double lre[4][M + 64], lim[4][M + 64];
@@ -368,6 +392,21 @@ __global__ __launch_bounds__(256, OCC3 ? 3 : 2) void stft1024_walk_kernel(const 
         for (int r = 0; r < 4; ++r) sincospi(-2.0 * (double)(lane + 64 * r) / 1024.0, &si[r], &sr[r]);   // split twiddles exp(-2 pi i k / 1024), k = lane + 64 r
     }
 
+    int64_t tb = ((int64_t)blockIdx.x * 4 + wave) * chunk;
+    if constexpr (BATCH) {
+        const BatchItem it = batch_item(tab, U, (int64_t)blockIdx.x * 4 + wave);
+        if (it.u < 0) return;
+        const int64_t f0 = uni64(tab[U + 1 + it.u]), Tu = uni64(tab[U + 2 + it.u]) - f0, s0 = uni64(tab[2 * U + 2 + it.u]);
+        const int64_t nu = (Tu - 1) * 256 + 1024;                               // the samples the utterance's frames read
+        // a table the host's checks would have refused: the wave leaves without touching memory
+        if (Tu < 1 || f0 < 0 || f0 + Tu > T || s0 < 0 || s0 + nu > n || nu * (int64_t)sizeof(TIN) >= ((int64_t)1 << 31) ||
+            Tu * F * ESZ >= ((int64_t)1 << 31) || it.local * chunk >= Tu) return;
+        x += s0;
+        n = nu;
+        out = (char*)out + f0 * F * ESZ;
+        T = Tu;
+        tb = it.local * chunk;
+    }
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<TIN*>(x), 0, (int)(n * (int64_t)sizeof(TIN)), 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)(T * F * ESZ), 0x00020000);
     struct TIN2 { TIN a, b; };
@@ -398,7 +437,6 @@ __global__ __launch_bounds__(256, OCC3 ? 3 : 2) void stft1024_walk_kernel(const 
         }
     };
 
-    const int64_t tb = ((int64_t)blockIdx.x * 4 + wave) * chunk;
     const int64_t te = tb + chunk < T ? tb + chunk : T;
     TIN2 buf[8];                                                                   // ring: slot r of a frame with t - tb = p (mod 4) is buf[(r + 2 p) & 7]
     if (tb < te) {
@@ -861,9 +899,25 @@ __global__ __launch_bounds__(256) void istft1024_fused_kernel(const float2* __re
 // [256 t, 256 t + 256) have received all their frames in frame order with one float rounding per addition -- the arithmetic of
 // librosa's `y[...] += ytmp`, of istft_ola_kernel and of the fused kernel above (bit-identical results) -- and leave as 512-byte runs.
 // LDS: the FFT exchange buffers only (9 KB per wave).
+//
+// BATCH (dvae_istft_batch): the walk over a ragged batch of frame-major spectrograms packed row after row; a wave's work item is one
+// utterance and a run of at most `chunk` of its frames (its three halo frames are the utterance's own).  GAIN: every bin is scaled by a
+// real gain before the transform, re = g xr and im = g xi in float32 (numpy's `WF * X` of a float32 gain and a complex64 spectrogram);
+// blockIdx.y selects the gain plane and the output (two Wiener estimates in one launch).
+struct IstftBatch {
+    const int64_t* tab;      // [item prefix (U + 1) | first frame (U) | frames (U) | first output sample (U) | output length (U) | gain column (U)]
+    int U;
+    int64_t T_total, y_total;
+    const float* g[2];       // gain planes, bin-major [513][ldg]: bin k of the utterance's frame t at g[k * ldg + column + t]
+    int64_t ldg;
+    float* y1;               // the output of gain plane 1
+};
+
+template <bool BATCH = false, bool GAIN = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void istft1024_walk_kernel(const float2* __restrict__ S, int64_t T, int64_t ld,
                                                              const double* __restrict__ window, int64_t start,
-                                                             float* __restrict__ y, int64_t out_len, int chunk) {
+                                                             float* __restrict__ y, int64_t out_len, int chunk, IstftBatch bt = IstftBatch{}) {
+    static_assert(BATCH || !GAIN, "the fused gain exists in the batch walk only");
     constexpr int M = 512, HOP = 256, NF = 1024;
     __shared__ double lre[4][M + 64], lim[4][M + 64];
     // per-bin constants of the whole workgroup in LDS (two waves per SIMD need the kernel under 256 registers):
@@ -879,8 +933,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         wn[k] = double2{window[2 * k] * (1.0 / M), -(window[2 * k + 1] * (1.0 / M))};
     }
     __syncthreads();                                              // the only workgroup barrier
+    int64_t c = (int64_t)blockIdx.x * 4 + wave;
+    const float* __restrict__ gp = nullptr;
+    if constexpr (BATCH) {
+        const BatchItem it = batch_item(bt.tab, bt.U, c);
+        if (it.u < 0) return;
+        const int U = bt.U, u = it.u;
+        const int64_t f0 = uni64(bt.tab[U + 1 + u]), Tu = uni64(bt.tab[2 * U + 1 + u]), o0 = uni64(bt.tab[3 * U + 1 + u]);
+        const int64_t lu = uni64(bt.tab[4 * U + 1 + u]), gc = uni64(bt.tab[5 * U + 1 + u]);
+        // a table the host's checks would have refused: the wave leaves without touching memory (odd output offsets too: the
+        // paired stores below are 8-byte aligned)
+        if (Tu < 1 || f0 < 0 || f0 + Tu > bt.T_total || o0 < 0 || (o0 & 1) || lu < 0 || o0 + lu > bt.y_total || it.local * chunk >= Tu) return;
+        if constexpr (GAIN) {
+            if (gc < 0 || gc + Tu > bt.ldg) return;
+            gp = (blockIdx.y ? bt.g[1] : bt.g[0]) + gc;
+        }
+        S += f0 * ld;
+        T = Tu;
+        y = (GAIN && blockIdx.y ? bt.y1 : y) + o0;
+        out_len = lu;
+        c = it.local;
+    }
     const int64_t nchunks = (T + chunk - 1) / chunk;
-    const int64_t c = (int64_t)blockIdx.x * 4 + wave;
     if (c >= nchunks) return;
     Fft512 fft;
     fft.init(lane);
@@ -902,16 +976,40 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const bool last = c == nchunks - 1;
     const int64_t t_emit_end = last ? T + 3 : te;                 // the last chunk also flushes the three hops behind frame T - 1
     float2 ra[8], rb[8], na[8], nb[8];                            // X[k] and X[512 - k] of the current / the next frame
+    float ga[GAIN ? 8 : 1], gb[GAIN ? 8 : 1];                     // the gains of X[k], X[512 - k] of the frame in flight
+    // the utterance's gain columns through a buffer descriptor (the host keeps a gain plane below 2 GB)
+    const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gp), 0, GAIN ? (int)(513 * bt.ldg * 4) : 0, 0x00020000);
+    const int vga = GAIN ? (int)(lane * bt.ldg * 4) : 0, vgb = GAIN ? (int)((64 - lane) * bt.ldg * 4) : 0;
     auto fetch = [&](int64_t t, float2 (&a)[8], float2 (&b)[8]) __attribute__((always_inline)) {
         const float2* row = S + t * ld;
 #pragma unroll
         for (int r = 0; r < 8; ++r) { a[r] = row[lane + 64 * r]; b[r] = row[M - lane - 64 * r]; }
     };
+    auto fetch_gain = [&](int64_t t) __attribute__((always_inline)) {
+        if constexpr (GAIN) {
+            // bins lane + 64 r and (64 - lane) + 64 (7 - r) = 512 - lane - 64 r: a per-lane byte offset and a wave-uniform one
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                ga[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_g, vga, (int)((64 * r * bt.ldg + t) * 4), 0));
+                gb[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_g, vgb, (int)((64 * (7 - r) * bt.ldg + t) * 4), 0));
+            }
+        }
+    };
+    // re = g xr, im = g xi in float32 (numpy's product of a float32 gain and a complex64 bin, up to the sign of a zero)
+    auto apply_gain = [&](float2 (&a)[8], float2 (&b)[8]) __attribute__((always_inline)) {
+        if constexpr (GAIN) {
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                a[r] = float2{__fmul_rn(ga[r], a[r].x), __fmul_rn(ga[r], a[r].y)};
+                b[r] = float2{__fmul_rn(gb[r], b[r].x), __fmul_rn(gb[r], b[r].y)};
+            }
+        }
+    };
     float acc[8][2];
 #pragma unroll
     for (int r = 0; r < 8; ++r) { acc[r][0] = 0.f; acc[r][1] = 0.f; }
     int64_t t = t0 - 3 < 0 ? 0 : t0 - 3;                          // frames in front of the signal do not exist (nothing to add, nothing to emit)
-    if (t < T) fetch(t, ra, rb);
+    if (t < T) { fetch(t, ra, rb); fetch_gain(t); apply_gain(ra, rb); }
     for (; t < t_emit_end; ++t) {
         if (t < T) {
             if (t + 1 < te) fetch(t + 1, na, nb);                 // in flight under this frame's transform
@@ -927,6 +1025,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 v[r] = cd{e.x - o.y, -(e.y + o.x)};               // conj(E + i O)
             }
             fft.run(v, re, im, lane);
+            if (t + 1 < te) fetch_gain(t + 1);                    // (after the transform: not live across it)
             __builtin_amdgcn_wave_barrier();                      // the next frame's first exchange writes come after every lane's last reads
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
@@ -936,6 +1035,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 acc[r][0] = (float)__dadd_rn((double)acc[r][0], __dmul_rn(w.x, v[r].x));
                 acc[r][1] = (float)__dadd_rn((double)acc[r][1], __dmul_rn(w.y, v[r].y));
             }
+            if (t + 1 < te) apply_gain(na, nb);
 #pragma unroll
             for (int r = 0; r < 8; ++r) { ra[r] = na[r]; rb[r] = nb[r]; }
         }
@@ -1392,7 +1492,7 @@ static int istft_run(const void* S, int64_t T, int64_t ld, bool tf, const double
             int chunk = (int)cdiv(T, slots);
             chunk = chunk < 1 ? 1 : chunk;
             const int wb = (int)cdiv(cdiv(T, chunk), 4);
-            hipLaunchKernelGGL(istft1024_walk_kernel, dim3(wb), dim3(256), 0, s, (const float2*)S, T, ld, window, start, y, out_len, chunk);
+            hipLaunchKernelGGL((istft1024_walk_kernel<false, false>), dim3(wb), dim3(256), 0, s, (const float2*)S, T, ld, window, start, y, out_len, chunk);
             DVAE_LAUNCH_OK("istft1024_walk_kernel");
             return 0;
         }
@@ -1404,7 +1504,7 @@ static int istft_run(const void* S, int64_t T, int64_t ld, bool tf, const double
             int chunk = (int)cdiv(T, 2048);
             chunk = chunk < 1 ? 1 : chunk;
             const int wb = (int)cdiv(cdiv(T, chunk), 4);
-            hipLaunchKernelGGL(istft1024_walk_kernel, dim3(wb), dim3(256), 0, s, (const float2*)ws, T, (int64_t)513, window, start, y, out_len, chunk);
+            hipLaunchKernelGGL((istft1024_walk_kernel<false, false>), dim3(wb), dim3(256), 0, s, (const float2*)ws, T, (int64_t)513, window, start, y, out_len, chunk);
             DVAE_LAUNCH_OK("istft1024_walk_kernel");
             return 0;
         }
@@ -1454,6 +1554,55 @@ extern "C" int dvae_istft(const void* S, int64_t T, int64_t ldT, const double* w
 extern "C" int dvae_istft_frames(const void* S, int64_t T, int64_t ldF, const double* window, int nfft, int hop,
                                  int64_t start, float* y, int64_t out_len, void* ws, void* stream) {
     return istft_run(S, T, ldF, true, window, nfft, hop, start, y, out_len, ws, stream);
+}
+
+// Ragged batches (nfft 1024 / hop 256 only).  Work items: one utterance and a run of at most `chunk` of its frames, chunk = one round of
+// 2048 wave slots over the batch's frames (as the single-signal walks), so item counts and the launch depend on the tables the host
+// built; the kernels check every table entry against the scalar extents below before they touch memory.
+extern "C" int dvae_stft_batch(const void* x, int in_f64, int64_t n, const double* window, int nfft, int hop, int U, const int64_t* tables,
+                               int64_t n_items, int chunk, int64_t T_total, void* out, int layout, void* stream) {
+    DVAE_CHECK_ARG(nfft == 1024 && hop == 256, "stft_batch: the batch transform exists for nfft 1024 / hop 256 (got %d / %d): use dvae_stft per signal",
+                   nfft, hop);
+    DVAE_CHECK_ARG(x && window && tables && out && n > 0 && U > 0 && n_items > 0 && chunk > 0 && T_total > 0, "stft_batch: bad argument");
+    DVAE_CHECK_ARG(layout == 1 || layout == 2, "stft_batch: frame-major layouts only (1 power frames, 2 complex frames), got %d", layout);
+    DVAE_CHECK_ARG(n_items <= T_total && cdiv(n_items, 4) < ((int64_t)1 << 31), "stft_batch: %lld work items for %lld frames", (long long)n_items,
+                   (long long)T_total);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)cdiv(n_items, 4));
+    if (layout == 1) {
+        if (in_f64) hipLaunchKernelGGL((stft1024_walk_kernel<double, true, false, true>), grid, dim3(256), 0, s, (const double*)x, n, window, T_total, chunk, out, tables, U);
+        else hipLaunchKernelGGL((stft1024_walk_kernel<float, true, false, true>), grid, dim3(256), 0, s, (const float*)x, n, window, T_total, chunk, out, tables, U);
+    } else {
+        if (in_f64) hipLaunchKernelGGL((stft1024_walk_kernel<double, false, false, true>), grid, dim3(256), 0, s, (const double*)x, n, window, T_total, chunk, out, tables, U);
+        else hipLaunchKernelGGL((stft1024_walk_kernel<float, false, false, true>), grid, dim3(256), 0, s, (const float*)x, n, window, T_total, chunk, out, tables, U);
+    }
+    DVAE_LAUNCH_OK("stft1024_walk_kernel (batch)");
+    return 0;
+}
+
+extern "C" int dvae_istft_batch(const void* S, int64_t T_total, const double* window, int nfft, int hop, int U, const int64_t* tables, int64_t n_items,
+                                int chunk, int64_t start, float* y, int64_t y_total, const float* gain0, const float* gain1, int64_t ldg, float* y1,
+                                void* stream) {
+    DVAE_CHECK_ARG(nfft == 1024 && hop == 256, "istft_batch: the batch transform exists for nfft 1024 / hop 256 (got %d / %d): use dvae_istft_frames per "
+                   "signal", nfft, hop);
+    DVAE_CHECK_ARG(S && window && tables && y && T_total > 0 && U > 0 && n_items > 0 && chunk > 0 && start >= 0 && y_total > 0, "istft_batch: bad argument");
+    DVAE_CHECK_ARG(n_items <= T_total && cdiv(n_items, 4) < ((int64_t)1 << 31), "istft_batch: %lld work items for %lld frames", (long long)n_items,
+                   (long long)T_total);
+    DVAE_CHECK_ARG(gain0 || !gain1, "istft_batch: a second gain plane needs a first");
+    DVAE_CHECK_ARG(!gain0 || (ldg > 0 && 513 * ldg * 4 < ((int64_t)1 << 31)), "istft_batch: gain leading dimension %lld (a gain plane is read below 2 GB)",
+                   (long long)ldg);
+    DVAE_CHECK_ARG(!gain1 || y1, "istft_batch: the second gain plane needs its output");
+    hipStream_t s = (hipStream_t)stream;
+    IstftBatch bt{tables, U, T_total, y_total, {gain0, gain1}, ldg, y1};
+    if (gain0) {
+        const dim3 grid((unsigned)cdiv(n_items, 4), gain1 ? 2 : 1);
+        hipLaunchKernelGGL((istft1024_walk_kernel<true, true>), grid, dim3(256), 0, s, (const float2*)S, T_total, (int64_t)513, window, start, y, y_total, chunk, bt);
+    } else {
+        hipLaunchKernelGGL((istft1024_walk_kernel<true, false>), dim3((unsigned)cdiv(n_items, 4)), dim3(256), 0, s, (const float2*)S, T_total, (int64_t)513, window,
+                           start, y, y_total, chunk, bt);
+    }
+    DVAE_LAUNCH_OK("istft1024_walk_kernel (batch)");
+    return 0;
 }
 
 // float32-arithmetic inverse transform (istft_pytorch): S bin-major ([513][ld], frames = 0: transposed into ws first, T * 513 complex64)

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import native as N
+from . import stft as STFT
 
 F_BINS, Z_DIM, H_DIM = 513, 16, 128
 PREC = {"fp32": 0, "bf16": 1, "bf16x3": 2}      # bf16x3: split-bf16 operands (hi + lo planes, three MFMAs per product): parity grade
@@ -166,6 +167,8 @@ class McemBatch:
         self.label_in_encoder, self.label_in_decoder = label_in_encoder, label_in_decoder
         self.precision = precision
         self._pack = None
+        self.spec = self.X_list = self.WFs = self.WFn = None
+        self._S_hat = self._N_hat = None
 
     def _layout(self, counts, dev):
         starts, pos = [], 0
@@ -179,13 +182,29 @@ class McemBatch:
         return starts, pos, i32(starts), i32(counts), i32(tile_seg)
 
     def init_parameters(self, X_list, y_list=None, device="cuda"):
-        """X_list: complex mixture STFTs (F, N_u) (numpy); y_list: labels (y_dim, N_u) tensors/arrays or None."""
-        dev = torch.device(device)
-        self.X_list = X_list
-        self.counts = [x.shape[1] for x in X_list]
+        """X_list: complex mixture STFTs (F, N_u) (numpy), or a SpecBatch of complex frames (stft.stft_batch) that stays on the
+        device: |X|^2 is then formed there (dvae_mcem_spec_init, the same bits) and run() keeps the Wiener gains there for enhance().
+        y_list: labels (y_dim, N_u) tensors/arrays or None."""
+        spec = X_list if isinstance(X_list, STFT.SpecBatch) else None
+        if spec is not None:
+            if spec.layout != 2 or not spec.frames.is_cuda:
+                raise TypeError("McemBatch.init_parameters: a SpecBatch of complex frames (layout 2) on the device required")
+            dev = spec.frames.device
+        else:
+            dev = torch.device(device)
+        self.spec = spec
+        self.X_list = None if spec is not None else X_list
+        self._S_hat = self._N_hat = None
+        self._bufs = None                    # the M-step workspace depends on the utterance count, not only on the padded frame total
+        self.counts = list(spec.counts) if spec is not None else [x.shape[1] for x in X_list]
         self.starts, self.ntot, self.seg_start, self.seg_count, self.tile_seg = self._layout(self.counts, dev)
-        U, K = len(X_list), self.K
+        U, K = len(self.counts), self.K
         self.X2 = torch.ones((F_BINS, self.ntot), dtype=torch.float32, device=dev)
+        if spec is not None:
+            tab = np.concatenate([spec.frame_off, np.asarray(self.starts, np.int64)]).astype(np.int64)
+            tab_dev = torch.from_numpy(tab).to(dev)
+            N.check(N.load().dvae_mcem_spec_init(N.ptr(spec.frames), int(spec.frame_off[-1]), U, N.ptr(tab_dev), N.ptr(self.X2), self.ntot, N.stream()),
+                    "dvae_mcem_spec_init")
         self.H = torch.ones((K, self.ntot), dtype=torch.float32, device=dev)
         self.Vb = torch.ones((F_BINS, self.ntot), dtype=torch.float32, device=dev)
         self.g = torch.ones(self.ntot, dtype=torch.float32, device=dev)
@@ -195,9 +214,10 @@ class McemBatch:
         if self.label_in_decoder:
             y_dim = y_list[0].shape[0]
             self.y = torch.zeros((y_dim, self.ntot), dtype=torch.float32, device=dev)
-        for u, X in enumerate(X_list):
+        for u in range(U):
             s, c = self.starts[u], self.counts[u]
-            self.X2[:, s:s + c] = torch.from_numpy((np.abs(X) ** 2).astype(np.float32)).to(dev)
+            if spec is None:
+                self.X2[:, s:s + c] = torch.from_numpy((np.abs(X_list[u]) ** 2).astype(np.float32)).to(dev)
             self.W[u] = torch.clamp_min(torch.rand(F_BINS, K, device=dev), self.eps)               # mcem.py:42
             self.H[:, s:s + c] = torch.clamp_min(torch.rand(K, c, device=dev), self.eps)           # mcem.py:43
             self.Vb[:, s:s + c] = self.W[u] @ self.H[:, s:s + c]                                    # mcem.py:52
@@ -320,7 +340,37 @@ class McemBatch:
                                                         cptr + 4 * U * (self.niter - 1), N.ptr(self._loop_buffers()[2]), N.stream()), "dvae_mcem_cost_flush")
         Zs, Vs = self._chain(self.n_wf, self.b_wf, None if draws is None else draws[self.niter])
         self.WFs, self.WFn = wiener(Vs, self.g, self.Vb)
-        WFs, WFn = self.WFs.cpu().numpy(), self.WFn.cpu().numpy()
-        self.S_hat = [WFs[:, s:s + c] * X for s, c, X in zip(self.starts, self.counts, self.X_list)]
-        self.N_hat = [WFn[:, s:s + c] * X for s, c, X in zip(self.starts, self.counts, self.X_list)]
+        self._S_hat = self._N_hat = None
+        if self.spec is None:
+            self._estimates()
         return cost.cpu().numpy()
+
+    def _estimates(self):
+        """S_hat / N_hat = WF * X per utterance on the host (mcem.py:330-331), complex (F, N_u)."""
+        X_list = self.X_list if self.spec is None else self.spec.numpy()
+        WFs, WFn = self.WFs.cpu().numpy(), self.WFn.cpu().numpy()
+        self._S_hat = [WFs[:, s:s + c] * X for s, c, X in zip(self.starts, self.counts, X_list)]
+        self._N_hat = [WFn[:, s:s + c] * X for s, c, X in zip(self.starts, self.counts, X_list)]
+
+    # After a SpecBatch init the estimates are built on first use only: enhance() goes from the gains to the waveforms on the device
+    @property
+    def S_hat(self):
+        if self._S_hat is None:
+            self._estimates()
+        return self._S_hat
+
+    @property
+    def N_hat(self):
+        if self._N_hat is None:
+            self._estimates()
+        return self._N_hat
+
+    def enhance(self, max_len=None, center=None):
+        """The speech and noise waveforms, istft(S_hat) and istft(N_hat) of every utterance (evaluate_ntcd_M2.py:211-225), from the
+        device-resident gains and spectrogram in one fused-gain batch ISTFT -> (WaveBatch, WaveBatch).  max_len: None, one value or one
+        per utterance (istft's max_len).  Needs a run() after an init_parameters from a SpecBatch."""
+        if self.spec is None:
+            raise RuntimeError("McemBatch.enhance: initialise from a SpecBatch (stft.stft_batch) to keep the spectrogram on the device")
+        if getattr(self, "WFs", None) is None or self.WFs.shape[1] != self.ntot:
+            raise RuntimeError("McemBatch.enhance: run() first")
+        return STFT.istft_batch(self.spec, max_len, gain=(self.WFs, self.WFn), gain_cols=self.starts, center=center)

@@ -55,6 +55,8 @@ SIGNATURES = {
     "dvae_istft": (c_i, [c_vp, c_i64, c_i64, c_vp, c_i, c_i, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "dvae_istft_frames": (c_i, [c_vp, c_i64, c_i64, c_vp, c_i, c_i, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "dvae_istft_f32": (c_i, [c_vp, c_i64, c_i64, c_i, c_vp, c_i, c_i, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "dvae_stft_batch": (c_i, [c_vp, c_i, c_i64, c_vp, c_i, c_i, c_i, c_vp, c_i64, c_i, c_i64, c_vp, c_i, c_vp]),
+    "dvae_istft_batch": (c_i, [c_vp, c_i64, c_vp, c_i, c_i, c_i, c_vp, c_i64, c_i, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "dvae_transpose": (c_i, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp]),
     "dvae_gather_rows": (c_i, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i, c_vp, c_i64, c_vp, c_vp]),
     "dvae_vad_workspace_bytes": (c_sz, [c_i64]),
@@ -102,6 +104,7 @@ SIGNATURES = {
                                      c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dvae_mcem_cost_flush": (c_i, [c_i, c_i64, c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dvae_mcem_wiener": (c_i, [c_vp, c_i, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "dvae_mcem_spec_init": (c_i, [c_vp, c_i64, c_i, c_vp, c_vp, c_i64, c_vp]),
 }
 
 

@@ -207,3 +207,256 @@ def istft_numpy(Sxx, fs, wlen_sec, win, hop_percent, center, dtype, max_len):
     if max_len:
         y = y[:int(max_len * fs)]      # quirk Q8: max_len is already in samples, so this is a no-op
     return y
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Ragged batches (dvae_stft_batch / dvae_istft_batch): U utterances packed end to end, nfft 1024 / hop 256 (every caller of the
+# reference).  The per-utterance decisions (end pad, centre pad, frame count, max_len truncation) are the single-signal ones above,
+# made on the host; the offset tables are checked here before upload, and the kernels check them again against the buffers' extents.
+
+BATCH_NFFT, BATCH_HOP = 1024, 256
+_SLOTS = 2048                      # one round of waves, as the single-signal walks (256 CUs x 4 SIMDs x 2 resident waves)
+
+
+def batch_covers(nfft, hop):
+    return nfft == BATCH_NFFT and hop == BATCH_HOP
+
+
+def plan_stft_batch(lengths, fs=16000, wlen_sec=64e-3, hop_percent=0.25, center=False, pad_at_end=True):
+    """Per-utterance padding and frame counts of stft() for signals of the given lengths, packed end to end.  Returns a dict of
+    numpy int64 arrays: end_pad (0 / 1), padded (samples after end and centre padding), frames (T_u), frame_off [U + 1] (first output
+    row of each utterance), x0 (first sample of each padded signal in the packed buffer), plus nfft / hop.  Raises ValueError for a
+    signal shorter than nfft after padding (librosa's message)."""
+    nfft, hop = sizes(fs, wlen_sec, hop_percent, "STFT")
+    lengths = [int(n) for n in lengths]
+    if not lengths:
+        raise ValueError("stft_batch: no signals")
+    end_pad = np.array([1 if pad_at_end and needs_end_pad(n, fs, wlen_sec, hop_percent) else 0 for n in lengths], np.int64)
+    padded = np.array(lengths, np.int64) + hop * end_pad + (2 * (nfft // 2) if center else 0)
+    frames = np.array([frame_count(int(p), nfft, hop) for p in padded], np.int64)
+    frame_off = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
+    x0 = np.concatenate([[0], np.cumsum(padded)[:-1]]).astype(np.int64)
+    return dict(nfft=nfft, hop=hop, end_pad=end_pad, padded=padded, frames=frames, frame_off=frame_off, x0=x0)
+
+
+def batch_chunk(frames):
+    """Frames per work item: the least rounds of the 2048 wave slots times the frames a wave walks per round.  ceil(T_total / 2048),
+    the single-signal choice, leaves up to one partial item per utterance beyond the slots (256 utterances of 5 s: ~2 130 items,
+    a second round for 80 waves); a slightly longer chunk keeps the items inside one round."""
+    frames = np.asarray(frames, np.int64)
+    c0 = max(1, -(-int(frames.sum()) // _SLOTS))
+    best = None
+    for c in range(c0, 2 * c0 + 2):
+        cost = -(-int((-(-frames // c)).sum()) // _SLOTS) * c
+        if best is None or cost < best[0]:
+            best = (cost, c)
+    return best[1]
+
+
+def _items(frames, chunk):
+    items = -(-np.asarray(frames, np.int64) // chunk)
+    return np.concatenate([[0], np.cumsum(items)]).astype(np.int64)
+
+
+def _monotone(name, a):
+    a = np.asarray(a, np.int64)
+    if a.size > 1 and np.any(np.diff(a) < 0):
+        raise ValueError(f"{name} must be non-decreasing: {a.tolist()[:16]}")
+
+
+def stft_tables(frames, x0, padded, n_total, chunk):
+    """The int64 table of dvae_stft_batch, [items (U + 1) | frame_off (U + 1) | x0 (U)], after checking that the signals do not
+    overlap and lie inside the n_total packed samples, and that every frame lies inside its own signal."""
+    frames, x0, padded = (np.asarray(a, np.int64) for a in (frames, x0, padded))
+    U = frames.size
+    if not (x0.size == U and padded.size == U and U > 0):
+        raise ValueError("stft_batch: frames, x0 and padded lengths need one entry per utterance")
+    if np.any(frames < 1):
+        raise ValueError(f"stft_batch: every utterance needs at least one frame (frames {frames.tolist()[:16]})")
+    _monotone("stft_batch: signal offsets", x0)
+    if x0[0] < 0 or np.any(x0[:-1] + padded[:-1] > x0[1:]) or x0[-1] + padded[-1] > n_total:
+        raise ValueError("stft_batch: signals overlap or leave the packed buffer")
+    if np.any((frames - 1) * BATCH_HOP + BATCH_NFFT > padded):
+        raise ValueError("stft_batch: frames beyond the end of their signal")
+    if np.any(padded * 8 >= 2 ** 31) or np.any(frames * 513 * 8 >= 2 ** 31):
+        raise ValueError("stft_batch: an utterance of 2 GB or more (use the single-signal stft)")
+    return np.concatenate([_items(frames, chunk), np.concatenate([[0], np.cumsum(frames)]), x0]).astype(np.int64)
+
+
+def istft_tables(f0, nfr, y0, out_len, gcol, T_total, y_total, ldg, chunk):
+    """The int64 table of dvae_istft_batch, [items (U + 1) | f0 | nfr | y0 | len | gcol], after checking that every utterance's
+    frames lie inside the packed spectrogram, its output inside y (at an even offset, no overlaps) and its gain columns inside the
+    gain plane (ldg = None: no gain)."""
+    f0, nfr, y0, out_len, gcol = (np.asarray(a, np.int64) for a in (f0, nfr, y0, out_len, gcol))
+    U = f0.size
+    if U == 0 or any(a.size != U for a in (nfr, y0, out_len, gcol)):
+        raise ValueError("istft_batch: the tables need one entry per utterance")
+    if np.any(nfr < 1) or np.any(out_len < 0):
+        raise ValueError("istft_batch: every utterance needs at least one frame and a non-negative length")
+    _monotone("istft_batch: frame offsets", f0)
+    _monotone("istft_batch: output offsets", y0)
+    if f0[0] < 0 or np.any(f0[:-1] + nfr[:-1] > f0[1:]) or f0[-1] + nfr[-1] > T_total:
+        raise ValueError("istft_batch: frames overlap or leave the packed spectrogram")
+    if y0[0] < 0 or np.any(y0 % 2) or np.any(y0[:-1] + out_len[:-1] > y0[1:]) or y0[-1] + out_len[-1] > y_total:
+        raise ValueError("istft_batch: outputs overlap, leave the output buffer or start at an odd sample")
+    if ldg is not None and (np.any(gcol < 0) or np.any(gcol + nfr > ldg) or 513 * ldg * 4 >= 2 ** 31):
+        raise ValueError("istft_batch: gain columns outside the gain plane (or a plane of 2 GB or more)")
+    return np.concatenate([_items(nfr, chunk), f0, nfr, y0, out_len, gcol]).astype(np.int64)
+
+
+def _upload(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(dev, non_blocking=True)
+
+
+class SpecBatch:
+    """A ragged batch of spectrograms on the device, as stft_batch returns it.  frames: [sum T_u, 513] frame-major, complex64
+    (layout 2) or float32 power (layout 1); utterance u is rows frame_off[u]:frame_off[u + 1] -- the memory order of librosa's
+    Fortran-ordered [513, T_u] result, so spec(u) = those rows' `.T`.  counts: T_u; lengths: the signals' own lengths."""
+
+    def __init__(self, frames, counts, lengths, nfft, hop, center, layout):
+        self.frames, self.nfft, self.hop, self.center, self.layout = frames, nfft, hop, center, layout
+        self.counts = [int(c) for c in counts]
+        self.lengths = [int(n) for n in lengths]
+        self.frame_off = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int64)
+
+    def __len__(self):
+        return len(self.counts)
+
+    def spec(self, u):
+        """Utterance u as a [513, T_u] view on the device."""
+        return self.frames[int(self.frame_off[u]):int(self.frame_off[u + 1])].T
+
+    def numpy(self):
+        """Every utterance as a host array [513, T_u] (Fortran-ordered views of one host copy)."""
+        h = self.frames.cpu().numpy()
+        return [h[a:b].T for a, b in zip(self.frame_off[:-1], self.frame_off[1:])]
+
+
+class WaveBatch:
+    """A ragged batch of waveforms on the device: y float32, utterance u is y[offsets[u] : offsets[u] + lengths[u]] (offsets are
+    multiples of 64 samples; what lies between two utterances is unspecified)."""
+
+    def __init__(self, y, offsets, lengths):
+        self.y, self.offsets, self.lengths = y, [int(o) for o in offsets], [int(n) for n in lengths]
+
+    def __len__(self):
+        return len(self.lengths)
+
+    def __getitem__(self, u):
+        return self.y[self.offsets[u]:self.offsets[u] + self.lengths[u]]
+
+    def numpy(self):
+        h = self.y.cpu().numpy()
+        return [h[o:o + n] for o, n in zip(self.offsets, self.lengths)]
+
+
+def stft_packed(x_dev, frames, x0, padded, lengths=None, center=False, layout=2):
+    """The batch transform of signals already padded and packed on the device (x_dev: 1-D float32 / float64 CUDA tensor; utterance
+    u's padded signal is x_dev[x0[u] : x0[u] + padded[u]], T_u = frames[u]) -> SpecBatch."""
+    lib = N.load()
+    if not x_dev.is_cuda or x_dev.dim() != 1 or x_dev.dtype not in (torch.float32, torch.float64):
+        raise TypeError("stft_batch: 1-D float32/float64 CUDA tensor required")
+    if layout not in (1, 2):
+        raise ValueError(f"stft_batch: layout 1 (power frames) or 2 (complex frames), got {layout}")
+    x_dev = x_dev.contiguous()
+    frames = np.asarray(frames, np.int64)
+    T_total = int(frames.sum())
+    chunk = batch_chunk(frames)
+    tab = stft_tables(frames, x0, padded, x_dev.numel(), chunk)
+    U = frames.size
+    out = torch.empty((T_total, BATCH_NFFT // 2 + 1), dtype=torch.complex64 if layout == 2 else torch.float32, device=x_dev.device)
+    tab_dev = _upload(tab, x_dev.device)
+    N.check(lib.dvae_stft_batch(N.ptr(x_dev), 1 if x_dev.dtype == torch.float64 else 0, x_dev.numel(), N.ptr(window_f64("hann", BATCH_NFFT, x_dev.device)),
+                                BATCH_NFFT, BATCH_HOP, U, N.ptr(tab_dev), int(tab[U]), chunk, T_total, N.ptr(out), layout, N.stream()), "dvae_stft_batch")
+    return SpecBatch(out, frames, padded if lengths is None else lengths, BATCH_NFFT, BATCH_HOP, center, layout)
+
+
+def stft_batch(signals, fs=16000, wlen_sec=64e-3, win="hann", hop_percent=0.25, center=False, pad_mode="reflect", pad_at_end=True, layout=2):
+    """stft() of every signal in one launch (nfft 1024 / hop 256 only): the reference's per-utterance end pad, centre pad and frame
+    count on the host, the padded signals packed into one buffer and copied to the device once.  Returns a SpecBatch whose every
+    frame is bit-identical to stft_device(..., layout) of that utterance alone."""
+    nfft, hop = sizes(fs, wlen_sec, hop_percent, "STFT")
+    if not batch_covers(nfft, hop):
+        raise ValueError(f"stft_batch: nfft {nfft} / hop {hop}: the batch transform covers nfft 1024 / hop 256; use stft() per signal")
+    if win != "hann":
+        raise ValueError("stft_batch: the batch transform uses the periodic Hann window")
+    xs = [np.asarray(x) for x in signals]
+    for x in xs:
+        if x.ndim != 1 or not np.issubdtype(x.dtype, np.floating):
+            raise TypeError("stft_batch: every signal must be a 1-D floating-point array (as librosa requires)")
+    plan = plan_stft_batch([len(x) for x in xs], fs, wlen_sec, hop_percent, center, pad_at_end)
+    # float32 samples convert to double exactly, and the kernel computes in double whatever it reads: one buffer type serves all
+    dt = np.float32 if all(x.dtype == np.float32 for x in xs) else np.float64
+    buf = np.empty(int(plan["padded"].sum()), dt)
+    for x, e, a, p in zip(xs, plan["end_pad"], plan["x0"], plan["padded"]):
+        x_ = np.pad(x, (0, hop), mode="constant") if e else x
+        if center:
+            x_ = np.pad(x_, int(nfft // 2), mode=pad_mode)
+        buf[a:a + p] = x_
+    dev = _device()
+    return stft_packed(torch.from_numpy(buf).to(dev), plan["frames"], plan["x0"], plan["padded"], [len(x) for x in xs], center, layout)
+
+
+def istft_plan(counts, max_len, nfft, hop, center):
+    """istft_numpy's per-utterance frame truncation and output length: (n_frames, out_len, start) lists."""
+    U = len(counts)
+    mls = list(max_len) if isinstance(max_len, (list, tuple, np.ndarray)) else [max_len] * U
+    if len(mls) != U:
+        raise ValueError(f"istft_batch: {len(mls)} max_len entries for {U} utterances")
+    nfr, lens = [], []
+    for T, ml in zip(counts, mls):
+        n_frames = int(T)
+        if ml:
+            padded = ml + nfft if center else ml
+            n_frames = min(n_frames, int(np.ceil(padded / hop)))
+        ntot = nfft + hop * (n_frames - 1)
+        if ml is None:
+            out_len = ntot - 2 * (nfft // 2) if center else ntot
+        else:
+            out_len = int(ml)
+        nfr.append(n_frames)
+        lens.append(max(out_len, 0))
+    return nfr, lens, (nfft // 2 if center else 0)
+
+
+def istft_batch(spec, max_len=None, gain=None, gain_cols=None, center=None):
+    """istft() of every utterance of a SpecBatch (complex frames) in one launch -> WaveBatch, bit-identical per utterance to
+    istft_device.  max_len: None, one value or one per utterance (istft_numpy's truncation: n_frames = min(T, ceil(padded / hop))).
+    gain: None, a float32 CUDA tensor [513, ldg] or a pair of them (McemBatch's bin-major Wiener gains), utterance u's frame t
+    scaled by column gain_cols[u] + t, re = g xr and im = g xi in float32; with a pair, two WaveBatches come back from one launch."""
+    lib = N.load()
+    if not isinstance(spec, SpecBatch) or spec.layout != 2:
+        raise TypeError("istft_batch: a SpecBatch of complex frames (layout 2) required")
+    if not batch_covers(spec.nfft, spec.hop):
+        raise ValueError(f"istft_batch: nfft {spec.nfft} / hop {spec.hop}: the batch transform covers nfft 1024 / hop 256; use istft() per signal")
+    center = spec.center if center is None else center
+    S = spec.frames
+    if not (S.is_cuda and S.dtype == torch.complex64 and S.dim() == 2 and S.shape[1] == 513 and S.is_contiguous()):
+        raise TypeError("istft_batch: frames must be a contiguous complex64 [T, 513] CUDA tensor")
+    U = len(spec)
+    nfr, lens, start = istft_plan(spec.counts, max_len, spec.nfft, spec.hop, center)
+    y0 = np.concatenate([[0], np.cumsum((np.asarray(lens, np.int64) + 63) // 64 * 64)]).astype(np.int64)
+    y_total = max(int(y0[-1]), 2)
+    planes = None if gain is None else (list(gain) if isinstance(gain, (list, tuple)) else [gain])
+    ldg = None
+    if planes is not None:
+        if not 1 <= len(planes) <= 2:
+            raise ValueError("istft_batch: one or two gain planes")
+        ldg = planes[0].shape[1] if planes[0].dim() == 2 else -1
+        for g in planes:
+            if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.dim() == 2 and g.shape == (513, ldg)):
+                raise TypeError("istft_batch: gains must be contiguous float32 CUDA tensors [513, ldg] of one shape")
+        if gain_cols is None:
+            raise ValueError("istft_batch: gain_cols (the first gain column of each utterance) is required with a gain")
+    gcol = np.zeros(U, np.int64) if gain_cols is None else np.asarray(gain_cols, np.int64)
+    chunk = batch_chunk(nfr)
+    tab = istft_tables(spec.frame_off[:-1], nfr, y0[:-1], lens, gcol, S.shape[0], y_total, ldg, chunk)
+    tab_dev = _upload(tab, S.device)
+    ys = [torch.empty(y_total, dtype=torch.float32, device=S.device) for _ in range(1 if planes is None else len(planes))]
+    g0 = planes[0] if planes else None
+    g1 = planes[1] if planes and len(planes) > 1 else None
+    N.check(lib.dvae_istft_batch(N.ptr(S), S.shape[0], N.ptr(window_f64("hann", BATCH_NFFT, S.device)), BATCH_NFFT, BATCH_HOP, U, N.ptr(tab_dev),
+                                 int(tab[U]), chunk, start, N.ptr(ys[0]), y_total, N.ptr(g0), N.ptr(g1), ldg or 0,
+                                 N.ptr(ys[1]) if g1 is not None else None, N.stream()), "dvae_istft_batch")
+    out = [WaveBatch(y, y0[:-1], lens) for y in ys]
+    return out[0] if planes is None or len(planes) == 1 else tuple(out)

@@ -1,6 +1,7 @@
 """Speech enhancement of a batch of utterances on the MI355X-native path: the per-utterance flow of the reference's
 scripts/evaluate_ntcd_M2.py:139-230 (STFT -> MCEM with a VAE speech prior and an NMF noise model -> Wiener
-filtering -> ISTFT), for many utterances at once (disentangled-vae_amd/mcem.py: McemBatch).
+filtering -> ISTFT), for many utterances at once (disentangled-vae_amd/mcem.py: McemBatch), with nothing leaving the
+device between the batch STFT and the waveforms.
 
     python examples/enhance_mcem.py --wav a.wav b.wav --checkpoint models/M2_epoch_118_vloss_407.90.pt --out enhanced/
     python examples/enhance_mcem.py --synthetic 8                       # no data at hand: modulated-noise "speech" + noise
@@ -21,10 +22,10 @@ from scipy.io import wavfile
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from packages.models.models import DeepGenerativeModel
-from packages.processing.stft import stft, istft
 from packages.processing.target import clean_speech_VAD
 
 McemBatch = importlib.import_module("disentangled-vae_amd.mcem").McemBatch
+stft_batch = importlib.import_module("disentangled-vae_amd.stft").stft_batch
 STFT = dict(fs=16000, wlen_sec=64e-3, win="hann", hop_percent=0.25, center=False)      # evaluate_ntcd_M2.py:37-45
 
 
@@ -63,21 +64,22 @@ def main():
         p.requires_grad = False
 
     t0 = time.perf_counter()
-    X = [stft(w, pad_mode="reflect", pad_at_end=True, dtype="complex64", **STFT) for w in waves]          # (513, N_u) complex64
+    # every mixture's STFT in one launch, kept on the device: (513, N_u) complex64 per utterance, frame-major and packed
+    X = stft_batch(waves, pad_mode="reflect", pad_at_end=True, **STFT)
     Y = [clean_speech_VAD(w, fs=16000, wlen_sec=64e-3, hop_percent=0.25, center=False, pad_mode="reflect", pad_at_end=True,
                           vad_threshold=1.70) for w in waves]                                              # (1, N_u)
     mb = McemBatch(vae, niter=a.niter, nsamples_E_step=10, burnin_E_step=30, nsamples_WF=25, burnin_WF=75, var_RW=0.01,
                    nmf_rank=10, precision=a.precision)                                                      # evaluate_ntcd_M2.py:92-99
     mb.init_parameters(X, Y)
     cost = mb.run()
+    # Wiener filtering and ISTFT of both estimates in one launch: istft(S_hat, max_len=len(w)) / istft(N_hat, ...) per utterance
+    s_hat, n_hat = mb.enhance(max_len=[len(w) for w in waves])
     os.makedirs(a.out, exist_ok=True)
-    for name, w, S_hat, N_hat in zip(names, waves, mb.S_hat, mb.N_hat):
-        s_hat = istft(S_hat, max_len=len(w), **STFT)
-        n_hat = istft(N_hat, max_len=len(w), **STFT)
-        wavfile.write(os.path.join(a.out, name + "_s_est.wav"), 16000, s_hat.astype(np.float32))
-        wavfile.write(os.path.join(a.out, name + "_n_est.wav"), 16000, n_hat.astype(np.float32))
+    for name, s_u, n_u in zip(names, s_hat.numpy(), n_hat.numpy()):
+        wavfile.write(os.path.join(a.out, name + "_s_est.wav"), 16000, s_u.astype(np.float32))
+        wavfile.write(os.path.join(a.out, name + "_n_est.wav"), 16000, n_u.astype(np.float32))
     dt = time.perf_counter() - t0
-    frames = sum(x.shape[1] for x in X)
+    frames = sum(X.counts)
     print(f"{len(waves)} utterances, {frames} frames, {a.niter} EM iterations: {dt:.2f} s wall ({len(waves) / dt:.1f} utterances/s); "
           f"cost {cost[0].mean():.3f} -> {cost[-1].mean():.3f}")
 

@@ -190,6 +190,29 @@ int dvae_istft(const void* S, int64_t T, int64_t ldT, const double* window, int 
 int dvae_istft_frames(const void* S, int64_t T, int64_t ldF, const double* window, int nfft, int hop,
                       int64_t start, float* y, int64_t out_len, void* ws, void* stream);
 
+/* Ragged batches of the two transforms above (nfft 1024 / hop 256 only, which every caller of the reference uses; any other size:
+ * DVAE_E_BADARG naming the single-signal functions).  U utterances are packed end to end; a work item is one utterance and a run of at
+ * most `chunk` of its frames, and `tables` (device int64) starts with the prefix of the per-utterance item counts, items[U + 1]
+ * (items[0] = 0, items[U] = n_items).  Every frame and sample is bit-identical to the single-signal call on the utterance alone.  The
+ * kernels check each table entry against the scalar extents before touching memory: a bad entry drops that utterance's work, it is
+ * never an out-of-bounds access.  Each utterance (not the batch) must stay below 2 GB of input and of output.
+ *
+ * dvae_stft_batch: the transform of dvae_stft (double arithmetic) of x (n samples, float64 when in_f64, else float32: the padded
+ * signals, as dvae_stft takes them), output frame-major [T_total][513] in layout 1 (float32 power) or 2 (complex64).
+ *   tables = [items (U + 1) | frames (U + 1) | x0 (U)]: utterance u's frames are output rows [frames[u], frames[u + 1]) and read
+ *   samples from x0[u] on ((frames[u + 1] - frames[u] - 1) * 256 + 1024 of them). */
+int dvae_stft_batch(const void* x, int in_f64, int64_t n, const double* window, int nfft, int hop, int U, const int64_t* tables,
+                    int64_t n_items, int chunk, int64_t T_total, void* out, int layout, void* stream);
+/* dvae_istft_batch: the transform of dvae_istft_frames of S complex64 [T_total][513] (frame-major rows).
+ *   tables = [items (U + 1) | f0 (U) | nfr (U) | y0 (U) | len (U) | gcol (U)]: utterance u transforms rows [f0[u], f0[u] + nfr[u])
+ *   and writes y[y0[u] ... y0[u] + len[u]) (y0 even), `start` as in dvae_istft_frames, zeros past the utterance's own signal.
+ *   gain0 (may be NULL): every bin is first scaled by a real gain, re = g xr and im = g xi in float32 (numpy's `WF * X` of a float32
+ *   gain and a complex64 spectrogram), g = gain0[k * ldg + gcol[u] + t] for bin k of the utterance's frame t (McemBatch's bin-major
+ *   Wiener gains, 513 * ldg floats below 2 GB); gain1 (may be NULL) does the same into y1 in the same launch. */
+int dvae_istft_batch(const void* S, int64_t T_total, const double* window, int nfft, int hop, int U, const int64_t* tables, int64_t n_items,
+                     int chunk, int64_t start, float* y, int64_t y_total, const float* gain0, const float* gain1, int64_t ldg, float* y1,
+                     void* stream);
+
 /* The inverse transform of istft_pytorch (packages/processing/stft.py:154-190: torch.istft of a complex64 tensor with
  * torch.hann_window, center handled by `start` / `out_len` as above) in ITS arithmetic: inverse FFT, window product, overlap-add and
  * the division by the window envelope in float32 (dvae_istft computes in double -- the arithmetic of istft(), librosa's).  nfft 1024 /

@@ -99,6 +99,13 @@ int dvae_mcem_cost_flush(int R, int64_t N, int K, int U, const int* seg_start, c
 /* compute_WF (mcem.py:321-327): WFs = mean_r(g Vs / Vx), WFn = mean_r(Vb / Vx), both (F, N). */
 int dvae_mcem_wiener(const float* Vs, int R, int64_t N, const float* g, const float* Vb, float* WFs, float* WFn, void* stream);
 
+/* The mixture power X2 = |X|^2 of McemBatch (mcem.py:200, 364: `np.abs(X) ** 2`) from a packed batch of spectrograms on the device:
+ * S frame-major complex64 [T_total][513] (dvae_stft_batch layout 2), utterance u in rows [frames[u], frames[u + 1]); it is written to the
+ * columns [col[u], col[u] + frames[u + 1] - frames[u]) of the bin-major X2 [513][ntot], every other column is left as it is.
+ * tables = [frames (U + 1) | col (U)] (device int64).  Bit-identical to `(np.abs(X) ** 2).astype(np.float32)` of numpy's complex64
+ * absolute value.  Frames outside the tables' range, or whose columns would leave [0, ntot), are skipped. */
+int dvae_mcem_spec_init(const void* S, int64_t T_total, int U, const int64_t* tables, float* X2, int64_t ntot, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,11 @@ as the reference makes them; the transforms are hand-written HIP kernels
 (batched real FFT in LDS, windowed overlap-add) reached through libdvae_hip.so.
 librosa is not imported and there is no CPU transform: without a GPU these
 functions raise.
+
+Beyond the reference: `stft_many` / `istft_many`, lists in and lists out, equal
+to the loops of `stft` / `istft` and computed as one ragged batch per call.
 """
+import numpy as np
 import torch
 
 from packages import _native
@@ -106,3 +110,62 @@ def istft_pytorch(Sxx,
     if max_len:
         y = y[:int(max_len * fs)]
     return y if Sxx.is_cuda else y.cpu()
+
+
+def stft_many(xs,
+              fs=16e3,
+              wlen_sec=50e-3,
+              win='hann',
+              hop_percent=0.25,
+              center=True,
+              pad_mode='reflect',
+              pad_at_end=True,
+              dtype='complex64'):
+    """[stft(x, ...) for x in xs] (equal arrays: dtype, shape and Fortran order included) in one batch transform when nfft is 1024
+    and the hop 256 (every caller of the reference); any other size runs that loop."""
+    H = _native.stft_host()
+    xs = list(xs)
+    nfft, hop = H.sizes(fs, wlen_sec, hop_percent, "STFT")
+    if not xs or not H.batch_covers(nfft, hop) or win != 'hann' or any(np.asarray(x).ndim != 1 for x in xs):
+        return [stft(x, fs, wlen_sec, win, hop_percent, center, pad_mode, pad_at_end, dtype) for x in xs]
+    res = H.stft_batch(xs, fs, wlen_sec, win, hop_percent, center, pad_mode, pad_at_end, layout=2).numpy()
+    if np.dtype(dtype) != np.complex64:
+        res = [r.astype(dtype) for r in res]
+    return res
+
+
+def istft_many(Sxx_list,
+               fs=16000,
+               wlen_sec=50e-3,
+               win='hann',
+               hop_percent=0.25,
+               center=True,
+               dtype='float32',
+               max_len=None):
+    """[istft(S, ..., max_len=m) for S, m in zip(Sxx_list, max_len)] (max_len: None, one value or one per spectrogram) in one batch
+    transform when nfft is 1024 and the hop 256; any other size runs that loop."""
+    H = _native.stft_host()
+    Ss = list(Sxx_list)
+    mls = list(max_len) if isinstance(max_len, (list, tuple, np.ndarray)) else [max_len] * len(Ss)
+    if len(mls) != len(Ss):
+        raise ValueError(f"istft_many: {len(mls)} max_len entries for {len(Ss)} spectrograms")
+    nfft, hop = H.sizes(fs, wlen_sec, hop_percent, "iSTFT")
+    if not Ss or not H.batch_covers(nfft, hop) or win != 'hann':
+        return [istft(S, fs, wlen_sec, win, hop_percent, center, dtype, m) for S, m in zip(Ss, mls)]
+    Ss = [np.asarray(S) for S in Ss]
+    for S in Ss:
+        if S.ndim != 2 or S.shape[0] != 1 + nfft // 2:
+            raise ValueError("istft: expected a [%d, T] spectrogram" % (1 + nfft // 2))
+    # frame-major on the device, one copy: the rows of each S.T (free for a Fortran-ordered S, what stft() returns) end to end
+    frames = np.concatenate([S.T for S in Ss]).astype(np.complex64, copy=False)
+    dev = H._device()
+    spec = H.SpecBatch(torch.from_numpy(np.ascontiguousarray(frames)).to(dev), [S.shape[1] for S in Ss], [0] * len(Ss), nfft, hop, center, 2)
+    ys = H.istft_batch(spec, mls).numpy()
+    out = []
+    for y, m in zip(ys, mls):
+        if np.dtype(dtype) != y.dtype:
+            y = y.astype(dtype)
+        if m:
+            y = y[:int(m * fs)]        # quirk Q8, as istft()
+        out.append(y)
+    return out
