@@ -186,6 +186,11 @@ class McemBatch:
         device: |X|^2 is then formed there (dvae_mcem_spec_init, the same bits) and run() keeps the Wiener gains there for enhance().
         y_list: labels (y_dim, N_u) tensors/arrays or None."""
         spec = X_list if isinstance(X_list, STFT.SpecBatch) else None
+        counts = list(spec.counts) if spec is not None else [x.shape[1] for x in X_list]
+        for u, c in enumerate(counts):
+            # no columns to lay out: both W updates would form 0/0 and the frames kernel would never write the utterance's norms
+            if c <= 0:
+                raise ValueError(f"McemBatch.init_parameters: utterance {u} has no frames")
         if spec is not None:
             if spec.layout != 2 or not spec.frames.is_cuda:
                 raise TypeError("McemBatch.init_parameters: a SpecBatch of complex frames (layout 2) on the device required")
@@ -196,7 +201,7 @@ class McemBatch:
         self.X_list = None if spec is not None else X_list
         self._S_hat = self._N_hat = None
         self._bufs = None                    # the M-step workspace depends on the utterance count, not only on the padded frame total
-        self.counts = list(spec.counts) if spec is not None else [x.shape[1] for x in X_list]
+        self.counts = counts
         self.starts, self.ntot, self.seg_start, self.seg_count, self.tile_seg = self._layout(self.counts, dev)
         U, K = len(self.counts), self.K
         self.X2 = torch.ones((F_BINS, self.ntot), dtype=torch.float32, device=dev)
