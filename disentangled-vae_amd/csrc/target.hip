@@ -125,3 +125,263 @@ extern "C" int dvae_ibm_labels(const void* S, int64_t rows, int64_t cols, float 
     DVAE_LAUNCH_OK("ibm_mask_kernel");
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Ragged batches (dvae_peak_normalise_batch, dvae_vad_labels_batch, dvae_ibm_labels_batch): U utterances packed end to end, each
+// kernel one wave per work item (one utterance and a run of at most `chunk` of its samples / frames / bins, found by batch_item).
+// Every reduction is a max or a min, exact in any order, so "partials per item, then each wave combines its utterance's partials"
+// gives the single-signal kernels' extrema without atomics; the per-element arithmetic is theirs, operation for operation.  Every
+// table entry is checked against the scalar extents before memory is touched: a bad entry drops that utterance's work.
+
+namespace dvae {
+
+// numpy's max: a NaN wins
+__device__ __forceinline__ double max_nan(double a, double b) { return (b > a || b != b) ? b : a; }
+
+__device__ __forceinline__ double wave_max_nan(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max_nan(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_fmax(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// One work item of a batch whose utterance u spans `extent` units (samples, frames or bins) in runs of `chunk`: [lo, hi) of them,
+// with the utterance's partials at [p0, p1).  ok = false for an entry the host's checks would have refused.
+struct ItemRange { int u; int64_t lo, hi, p0, p1; bool ok; };
+__device__ __forceinline__ ItemRange item_range(const int64_t* __restrict__ tab, int U, int64_t n_items, int64_t item, int64_t extent, int chunk,
+                                                BatchItem it) {
+    ItemRange r{it.u, 0, 0, 0, 0, false};
+    const int64_t p0 = uni64(tab[it.u]), p1 = uni64(tab[it.u + 1]);
+    r.lo = it.local * chunk;
+    r.hi = r.lo + chunk < extent ? r.lo + chunk : extent;
+    r.p0 = p0;
+    r.p1 = p1;
+    r.ok = extent >= 1 && item < n_items && p0 >= 0 && p1 <= n_items && p1 - p0 == (extent + chunk - 1) / chunk && r.lo < extent;
+    return r;
+}
+
+// tab = [items (U + 1) | x0 (U) | len (U)]: utterance u is x[x0[u] : x0[u] + len[u]]
+__device__ __forceinline__ ItemRange peak_item(const int64_t* __restrict__ tab, int U, int64_t n, int64_t n_items, int chunk, int64_t& x0) {
+    const int64_t item = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const BatchItem it = batch_item(tab, U, item);
+    if (it.u < 0) return ItemRange{-1, 0, 0, 0, 0, false};
+    x0 = uni64(tab[U + 1 + it.u]);
+    const int64_t len = uni64(tab[2 * U + 1 + it.u]);
+    ItemRange r = item_range(tab, U, n_items, item, len, chunk, it);
+    r.ok = r.ok && x0 >= 0 && len <= n - x0;
+    return r;
+}
+
+// pass 1: partial[item] = max |x| over the item's samples
+__global__ __launch_bounds__(256) void peak_partial_kernel(const double* __restrict__ x, int64_t n, int U, const int64_t* __restrict__ tab,
+                                                           int64_t n_items, int chunk, double* __restrict__ partial) {
+    int64_t x0 = 0;
+    const ItemRange r = peak_item(tab, U, n, n_items, chunk, x0);
+    if (!r.ok) return;
+    const int lane = threadIdx.x & 63;
+    double m = 0.0;
+#pragma unroll 4
+    for (int64_t s = r.lo + lane; s < r.hi; s += 64) m = max_nan(m, fabs(x[x0 + s]));
+    m = wave_max_nan(m);
+    if (lane == 0) partial[(int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)] = m;
+}
+
+// pass 2: peak = max of the utterance's partials (written once per utterance), x /= peak in IEEE double division: numpy's
+// `speech / np.max(np.abs(speech))` bit for bit
+__global__ __launch_bounds__(256) void peak_divide_kernel(double* __restrict__ x, int64_t n, int U, const int64_t* __restrict__ tab,
+                                                          int64_t n_items, int chunk, const double* __restrict__ partial, double* __restrict__ peak) {
+    int64_t x0 = 0;
+    const ItemRange r = peak_item(tab, U, n, n_items, chunk, x0);
+    if (!r.ok) return;
+    const int lane = threadIdx.x & 63;
+    double m = 0.0;
+    for (int64_t p = r.p0 + lane; p < r.p1; p += 64) m = max_nan(m, partial[p]);
+    m = wave_max_nan(m);
+    if (r.lo == 0 && lane == 0) peak[r.u] = m;
+#pragma unroll 4
+    for (int64_t s = r.lo + lane; s < r.hi; s += 64) x[x0 + s] = x[x0 + s] / m;
+}
+
+// tab = [items (U + 1) | x0 (U) | n (U) | frame_off (U + 1)]: utterance u's samples are y[x0[u] : x0[u] + n[u]] (zero past n[u], as
+// frame_energy_kernel), its frames are vad[frame_off[u] : frame_off[u + 1]]
+__device__ __forceinline__ ItemRange vad_item(const int64_t* __restrict__ tab, int U, int64_t n, int nfft, int hop, int64_t n_items, int chunk,
+                                              int64_t T_total, int64_t& x0, int64_t& nu, int64_t& f0) {
+    const int64_t item = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const BatchItem it = batch_item(tab, U, item);
+    if (it.u < 0) return ItemRange{-1, 0, 0, 0, 0, false};
+    x0 = uni64(tab[U + 1 + it.u]);
+    nu = uni64(tab[2 * U + 1 + it.u]);
+    f0 = uni64(tab[3 * U + 1 + it.u]);
+    const int64_t Tu = uni64(tab[3 * U + 2 + it.u]) - f0;
+    ItemRange r = item_range(tab, U, n_items, item, Tu, chunk, it);
+    r.ok = r.ok && x0 >= 0 && nu >= 1 && nu <= n - x0 && f0 >= 0 && Tu <= T_total - f0 && (Tu - 1) * hop + nfft <= nu + hop;
+    return r;
+}
+
+// pass 1: energy[t] of each frame in frame_energy_kernel's summation order (lane-strided fma, then wave_sum); partial[item] = min
+template <typename T>
+__global__ __launch_bounds__(256) void vad_energy_batch_kernel(const T* __restrict__ y, int64_t n, int nfft, int hop, int U,
+                                                               const int64_t* __restrict__ tab, int64_t n_items, int chunk, int64_t T_total,
+                                                               double* __restrict__ energy, double* __restrict__ partial) {
+    int64_t x0 = 0, nu = 0, f0 = 0;
+    const ItemRange r = vad_item(tab, U, n, nfft, hop, n_items, chunk, T_total, x0, nu, f0);
+    if (!r.ok) return;
+    const int lane = threadIdx.x & 63;
+    const T* yu = y + x0;
+    double mn = INFINITY;
+    for (int64_t t = r.lo; t < r.hi; ++t) {
+        const int64_t s0 = t * hop;
+        double a = 0.0;
+        for (int i = lane; i < nfft; i += 64) {
+            const int64_t s = s0 + i;
+            const double v = s < nu ? (double)yu[s] : 0.0;
+            a = fma(v, v, a);
+        }
+        a = wave_sum(a);
+        if (lane == 0) energy[f0 + t] = a;
+        mn = fmin(mn, a);
+    }
+    if (lane == 0) partial[(int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)] = mn;
+}
+
+// pass 2: vad[t] = energy[t] > factor * (min over the utterance), as vad_threshold_kernel
+__global__ __launch_bounds__(256) void vad_threshold_batch_kernel(const double* __restrict__ energy, int64_t n, int nfft, int hop, int U,
+                                                                  const int64_t* __restrict__ tab, int64_t n_items, int chunk, int64_t T_total,
+                                                                  double factor, const double* __restrict__ partial, float* __restrict__ vad) {
+    int64_t x0 = 0, nu = 0, f0 = 0;
+    const ItemRange r = vad_item(tab, U, n, nfft, hop, n_items, chunk, T_total, x0, nu, f0);
+    if (!r.ok) return;
+    const int lane = threadIdx.x & 63;
+    double mn = INFINITY;
+    for (int64_t p = r.p0 + lane; p < r.p1; p += 64) mn = fmin(mn, partial[p]);
+    const double thr = factor * wave_min(mn);
+    for (int64_t t = r.lo + lane; t < r.hi; t += 64) vad[f0 + t] = energy[f0 + t] > thr ? 1.f : 0.f;
+}
+
+// tab = [items (U + 1) | e0 (U) | count (U) | cols (U) | g0 (U)]: utterance u is S[e0[u] : e0[u] + count[u]], a row-major (count / cols,
+// cols) matrix; with a gate, element i of it is multiplied by gate[g0[u] + i % cols[u]]
+__device__ __forceinline__ ItemRange ibm_item(const int64_t* __restrict__ tab, int U, int64_t n, int64_t n_items, int chunk, bool gated,
+                                              int64_t n_gate, int64_t& e0, int64_t& cols, int64_t& g0) {
+    const int64_t item = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const BatchItem it = batch_item(tab, U, item);
+    if (it.u < 0) return ItemRange{-1, 0, 0, 0, 0, false};
+    e0 = uni64(tab[U + 1 + it.u]);
+    const int64_t count = uni64(tab[2 * U + 1 + it.u]);
+    cols = uni64(tab[3 * U + 1 + it.u]);
+    g0 = uni64(tab[4 * U + 1 + it.u]);
+    ItemRange r = item_range(tab, U, n_items, item, count, chunk, it);
+    r.ok = r.ok && e0 >= 0 && count <= n - e0 && cols >= 1 && count % cols == 0 && (!gated || (g0 >= 0 && cols <= n_gate - g0));
+    return r;
+}
+
+// pass 1: partial[item] = max mag_f32 over the item's bins (ibm_max_kernel's)
+__global__ __launch_bounds__(256) void ibm_max_batch_kernel(const float2* __restrict__ S, int64_t n, int U, const int64_t* __restrict__ tab,
+                                                            int64_t n_items, int chunk, int64_t n_gate, const float* __restrict__ gate,
+                                                            float* __restrict__ partial) {
+    int64_t e0 = 0, cols = 1, g0 = 0;
+    const ItemRange r = ibm_item(tab, U, n, n_items, chunk, gate != nullptr, n_gate, e0, cols, g0);
+    if (!r.ok) return;
+    const int lane = threadIdx.x & 63;
+    float m = 0.f;
+#pragma unroll 4
+    for (int64_t i = r.lo + lane; i < r.hi; i += 64) {
+        const float2 v = S[e0 + i];
+        m = fmaxf(m, mag_f32(v.x, v.y));
+    }
+    m = wave_fmax(m);
+    if (lane == 0) partial[(int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)] = m;
+}
+
+// pass 2: the mask of ibm_mask_kernel against the utterance's own maximum
+__global__ __launch_bounds__(256) void ibm_mask_batch_kernel(const float2* __restrict__ S, int64_t n, int U, const int64_t* __restrict__ tab,
+                                                             int64_t n_items, int chunk, const float* __restrict__ partial, float eps, float threshold,
+                                                             const float* __restrict__ gate, int64_t n_gate, float* __restrict__ mask) {
+    int64_t e0 = 0, cols = 1, g0 = 0;
+    const ItemRange r = ibm_item(tab, U, n, n_items, chunk, gate != nullptr, n_gate, e0, cols, g0);
+    if (!r.ok) return;
+    const int lane = threadIdx.x & 63;
+    float m = 0.f;
+    for (int64_t p = r.p0 + lane; p < r.p1; p += 64) m = fmaxf(m, partial[p]);
+    const float thr = db_f32(wave_fmax(m), eps) - threshold;
+#pragma unroll 4
+    for (int64_t i = r.lo + lane; i < r.hi; i += 64) {
+        const float2 v = S[e0 + i];
+        float o = db_f32(mag_f32(v.x, v.y), eps) > thr ? 1.f : 0.f;
+        if (gate) o *= gate[g0 + i % cols];
+        mask[e0 + i] = o;
+    }
+}
+
+}  // namespace dvae
+
+static bool batch_launch_ok(int U, const int64_t* tables, int64_t n_items, int chunk) {
+    return U > 0 && tables && n_items > 0 && chunk > 0 && cdiv(n_items, 4) < ((int64_t)1 << 31);
+}
+
+extern "C" size_t dvae_peak_normalise_workspace_bytes(int64_t n_items) { return (size_t)(n_items > 0 ? n_items : 1) * sizeof(double); }
+
+extern "C" int dvae_peak_normalise_batch(double* x, int64_t n, int U, const int64_t* tables, int64_t n_items, int chunk, double* peak,
+                                         void* workspace, void* stream) {
+    DVAE_CHECK_ARG(x && peak && workspace && n > 0, "peak_normalise_batch: null argument or empty buffer");
+    DVAE_CHECK_ARG(batch_launch_ok(U, tables, n_items, chunk), "peak_normalise_batch: bad table (U %d, %lld items, chunk %d)", U,
+                   (long long)n_items, chunk);
+    hipStream_t s = (hipStream_t)stream;
+    double* partial = (double*)workspace;
+    const dim3 grid((unsigned)cdiv(n_items, 4));
+    hipLaunchKernelGGL(peak_partial_kernel, grid, dim3(256), 0, s, (const double*)x, n, U, tables, n_items, chunk, partial);
+    DVAE_LAUNCH_OK("peak_partial_kernel");
+    hipLaunchKernelGGL(peak_divide_kernel, grid, dim3(256), 0, s, x, n, U, tables, n_items, chunk, (const double*)partial, peak);
+    DVAE_LAUNCH_OK("peak_divide_kernel");
+    return 0;
+}
+
+extern "C" size_t dvae_vad_batch_workspace_bytes(int64_t T_total, int64_t n_items) {
+    return (size_t)((T_total > 0 ? T_total : 1) + (n_items > 0 ? n_items : 1)) * sizeof(double);
+}
+
+extern "C" int dvae_vad_labels_batch(const void* y, int in_f64, int64_t n, int nfft, int hop, double vad_threshold, int U, const int64_t* tables,
+                                     int64_t n_items, int chunk, int64_t T_total, float* vad, void* workspace, void* stream) {
+    DVAE_CHECK_ARG(y && vad && workspace && n > 0 && nfft > 0 && hop > 0 && T_total > 0, "vad_labels_batch: bad argument");
+    DVAE_CHECK_ARG(batch_launch_ok(U, tables, n_items, chunk) && n_items <= T_total, "vad_labels_batch: bad table (U %d, %lld items, chunk %d)", U,
+                   (long long)n_items, chunk);
+    hipStream_t s = (hipStream_t)stream;
+    double* energy = (double*)workspace;
+    double* partial = energy + T_total;
+    const dim3 grid((unsigned)cdiv(n_items, 4));
+    if (in_f64) hipLaunchKernelGGL(vad_energy_batch_kernel<double>, grid, dim3(256), 0, s, (const double*)y, n, nfft, hop, U, tables, n_items, chunk,
+                                   T_total, energy, partial);
+    else hipLaunchKernelGGL(vad_energy_batch_kernel<float>, grid, dim3(256), 0, s, (const float*)y, n, nfft, hop, U, tables, n_items, chunk, T_total,
+                            energy, partial);
+    DVAE_LAUNCH_OK("vad_energy_batch_kernel");
+    hipLaunchKernelGGL(vad_threshold_batch_kernel, grid, dim3(256), 0, s, (const double*)energy, n, nfft, hop, U, tables, n_items, chunk, T_total,
+                       pow(10.0, vad_threshold), (const double*)partial, vad);
+    DVAE_LAUNCH_OK("vad_threshold_batch_kernel");
+    return 0;
+}
+
+extern "C" size_t dvae_ibm_batch_workspace_bytes(int64_t n_items) { return (size_t)(n_items > 0 ? n_items : 1) * sizeof(float); }
+
+extern "C" int dvae_ibm_labels_batch(const void* S, int64_t n, float eps, float ibm_threshold, int U, const int64_t* tables, int64_t n_items, int chunk,
+                                     const float* vad_gate, int64_t n_gate, float* mask, void* workspace, void* stream) {
+    DVAE_CHECK_ARG(S && mask && workspace && n > 0, "ibm_labels_batch: null argument or empty buffer");
+    DVAE_CHECK_ARG(!vad_gate || n_gate > 0, "ibm_labels_batch: a gate needs its extent");
+    DVAE_CHECK_ARG(batch_launch_ok(U, tables, n_items, chunk), "ibm_labels_batch: bad table (U %d, %lld items, chunk %d)", U, (long long)n_items, chunk);
+    hipStream_t s = (hipStream_t)stream;
+    float* partial = (float*)workspace;
+    const dim3 grid((unsigned)cdiv(n_items, 4));
+    hipLaunchKernelGGL(ibm_max_batch_kernel, grid, dim3(256), 0, s, (const float2*)S, n, U, tables, n_items, chunk, n_gate, vad_gate, partial);
+    DVAE_LAUNCH_OK("ibm_max_batch_kernel");
+    hipLaunchKernelGGL(ibm_mask_batch_kernel, grid, dim3(256), 0, s, (const float2*)S, n, U, tables, n_items, chunk, (const float*)partial, eps,
+                       ibm_threshold, vad_gate, n_gate, mask);
+    DVAE_LAUNCH_OK("ibm_mask_batch_kernel");
+    return 0;
+}

@@ -48,6 +48,27 @@ class DeviceFrames:
         self._bad = torch.zeros(1, dtype=torch.int32, device=self.device)
 
     @classmethod
+    def from_rows(cls, X, Y=None):
+        """Adopt frames already in the training layout: X [N][513], Y [N][y_dim] (or None) float32 device rows, e.g. a FrameBatch's
+        (target.utterances_to_frames).  No transpose and no copy for contiguous rows."""
+        for name, t in (("X", X), ("Y", Y)):
+            if t is None:
+                continue
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2):
+                raise TypeError(f"DeviceFrames.from_rows: {name} must be a 2-D float32 CUDA tensor of rows")
+        if X.shape[1] != F_BINS:
+            raise ValueError(f"DeviceFrames.from_rows: X rows of {F_BINS} bins expected, got {X.shape[1]}")
+        if Y is not None and (Y.shape[0] != X.shape[0] or Y.device != X.device):
+            raise ValueError("X and Y hold different numbers of frames")
+        self = cls.__new__(cls)
+        self.device = X.device
+        self.x = X.contiguous()
+        self.y = Y.contiguous() if Y is not None else None
+        self._xs = self._ys = None
+        self._bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return self
+
+    @classmethod
     def from_hdf5(cls, path, split, device="cuda:0"):
         """The reference's training file (scripts/create_train_set.py:91-219): datasets X_<split>, Y_<split>."""
         import h5py

@@ -1,7 +1,7 @@
 """Training-set builder on the MI355X-native path: what scripts/create_train_set.py:129-219 does per split (read each
 clean utterance, peak-normalise, STFT, power spectrogram, VAD or IBM labels, append; channel mean / std of the
-training split), with every transform on the GPU (disentangled-vae_amd/target.py: utterance_to_frames) and the frames
-kept in HBM for the trainer.
+training split), with every transform on the GPU (disentangled-vae_amd/target.py: utterances_to_frames, a few launches per
+group of utterances) and the frames kept in HBM for the trainer.
 
     python examples/build_train_set.py --wav-list train.txt --labels ibm_labels --out train_set.npz
     python examples/build_train_set.py --synthetic 64 --labels vad_labels --out /tmp/set.npz
@@ -23,6 +23,23 @@ from scipy.io import wavfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 tdev = importlib.import_module("disentangled-vae_amd.target")
 DeviceFrames = importlib.import_module("disentangled-vae_amd.frames").DeviceFrames
+
+
+GROUP_UTTERANCES = 512           # utterances per batch: bounds the pinned host staging buffer ...
+GROUP_SAMPLES = 1 << 27          # ... to about 1 GB of float64 samples
+
+
+def groups(waves):
+    """Consecutive runs of at most GROUP_UTTERANCES utterances and GROUP_SAMPLES samples (a longer utterance goes alone)."""
+    g, n = [], 0
+    for w in waves:
+        if g and (len(g) == GROUP_UTTERANCES or n + len(w) > GROUP_SAMPLES):
+            yield g
+            g, n = [], 0
+        g.append(w)
+        n += len(w)
+    if g:
+        yield g
 
 
 def channel_stats(X):
@@ -58,9 +75,9 @@ def main():
         ap.error("give --wav-list or --synthetic N")
     t0 = time.perf_counter()
     Xs, Ys = [], []
-    for w in waves:
-        X, Y = tdev.utterance_to_frames(w, a.labels)           # [T, 513], [T, y_dim] on the GPU
-        Xs.append(X); Ys.append(Y)
+    for g in groups(waves):
+        fb = tdev.utterances_to_frames(g, a.labels)             # [sum T, 513], [sum T, y_dim] on the GPU
+        Xs.append(fb.X); Ys.append(fb.Y)
     X = torch.cat(Xs); Y = torch.cat(Ys)
     mean, std = channel_stats(X)
     torch.cuda.synchronize()

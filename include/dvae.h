@@ -251,6 +251,34 @@ size_t dvae_ibm_workspace_bytes(void);
 int dvae_ibm_labels(const void* S, int64_t rows, int64_t cols, float eps, float ibm_threshold, const float* vad_gate,
                     float* mask, void* workspace, void* stream);
 
+/* Ragged batches of the training-set front end (scripts/create_train_set.py:133-170 over a whole split): U utterances packed end to
+ * end, a work item is one utterance and a run of at most `chunk` of its samples / frames / bins, and `tables` (device int64) starts
+ * with the prefix of the per-utterance item counts, items[U + 1] (items[0] = 0, items[U] = n_items, items[u + 1] - items[u] =
+ * ceil(extent_u / chunk)).  The kernels check every table entry against the scalar extents before touching memory: a bad entry drops
+ * that utterance's work.  Two launches each on `stream`, no host synchronisation; the per-utterance results are bit-identical to the
+ * single-signal calls on the utterance alone.
+ *
+ * dvae_peak_normalise_batch: x[x0[u] : x0[u] + len[u]] /= max |x| over that range (IEEE double division: numpy's
+ *   `speech / np.max(np.abs(speech))`, create_train_set.py:137), in place; peak[u] = the maximum (0 for an all-zero utterance, which
+ *   then holds NaN; a NaN sample makes the peak NaN, as np.max).  Samples outside every range are not touched.
+ *   tables = [items (U + 1) | x0 (U) | len (U)], chunk in samples; workspace: dvae_peak_normalise_workspace_bytes(n_items).
+ * dvae_vad_labels_batch: dvae_vad_labels of every utterance (any nfft / hop): utterance u reads y[x0[u] : x0[u] + n[u]] (zeros past
+ *   n[u]; frames may reach n[u] + hop) and writes vad[frame_off[u] : frame_off[u + 1]].  tables = [items (U + 1) | x0 (U) | n (U) |
+ *   frame_off (U + 1)], chunk in frames, T_total = the length of vad; workspace: dvae_vad_batch_workspace_bytes(T_total, n_items).
+ * dvae_ibm_labels_batch: dvae_ibm_labels of every segment S[e0[u] : e0[u] + count[u]] (complex64, a row-major (count / cols, cols)
+ *   matrix: a frame-major [T_u, 513] slice of packed frames or a host [513, T_u] matrix) into the same elements of mask (n of each);
+ *   vad_gate (n_gate floats) or NULL: element i of segment u is multiplied by vad_gate[g0[u] + i % cols[u]].  tables = [items (U + 1)
+ *   | e0 (U) | count (U) | cols (U) | g0 (U)], chunk in bins; workspace: dvae_ibm_batch_workspace_bytes(n_items). */
+size_t dvae_peak_normalise_workspace_bytes(int64_t n_items);
+int dvae_peak_normalise_batch(double* x, int64_t n, int U, const int64_t* tables, int64_t n_items, int chunk, double* peak,
+                              void* workspace, void* stream);
+size_t dvae_vad_batch_workspace_bytes(int64_t T_total, int64_t n_items);
+int dvae_vad_labels_batch(const void* y, int in_f64, int64_t n, int nfft, int hop, double vad_threshold, int U, const int64_t* tables,
+                          int64_t n_items, int chunk, int64_t T_total, float* vad, void* workspace, void* stream);
+size_t dvae_ibm_batch_workspace_bytes(int64_t n_items);
+int dvae_ibm_labels_batch(const void* S, int64_t n, float eps, float ibm_threshold, int U, const int64_t* tables, int64_t n_items,
+                          int chunk, const float* vad_gate, int64_t n_gate, float* mask, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
