@@ -168,6 +168,135 @@ def bce_bwd(p, y, eps, scale):
 
 
 # ----------------------------------------------------------------------------
+# float64 truths of the layer-level kernels (tests/test_layer_oracle.py pins each against torch.float64 autograd of the
+# reference's own expressions; tests/test_gpu_layers_scale.py compares the HIP kernels with them)
+# ----------------------------------------------------------------------------
+
+def is_rows(x, r, eps):
+    """Per-frame Itakura-Saito divergence: packages/models/utils.py:68-71 (ikatura_saito_divergence), :79 (L_loss recon)."""
+    return np.sum(x / r - np.log(x + x.dtype.type(eps)) + np.log(r) - 1, axis=-1)
+
+
+def kl_rows(mu, logvar):
+    """Per-frame KL of packages/models/utils.py:80 (L_loss), :85 (U_loss); the same rows as kld_v2()."""
+    return -0.5 * np.sum(logvar - mu ** 2 - np.exp(logvar), axis=-1)
+
+
+def is_rows_bwd(x, r, g_rows):
+    """d/dr of sum_b g_rows[b] * is_rows(x, r)[b] (utils.py:71): g (1/r - x/r^2)."""
+    return g_rows[:, None] * (1 / r - x / (r * r))
+
+
+def kl_rows_bwd(mu, logvar, g_rows):
+    """(d/dmu, d/dlogvar) of sum_b g_rows[b] * kl_rows(mu, logvar)[b] (utils.py:80)."""
+    g = g_rows[:, None]
+    return g * mu, -0.5 * g * (1 - np.exp(logvar))
+
+
+def elbo_bwd_r(x, r, mu, logvar, g_recon, g_kl):
+    """(d/dr, d/dmu, d/dlogvar) of g_recon * recon + g_kl * KL of elbo() (utils.py:73-76): the row gradients with the weight g / B
+    of the two means."""
+    B = x.shape[0]
+    w = np.ones(B, dtype=x.dtype)
+    dmu, dlv = kl_rows_bwd(mu, logvar, w * (g_kl / B))
+    return is_rows_bwd(x, r, w * (g_recon / B)), dmu, dlv
+
+
+def binary_cross_entropy_2classes(r1, r2, x, eps):
+    """packages/models/utils.py:65-66."""
+    e = r1.dtype.type(eps)
+    return -np.mean(np.sum(x * np.log(r1 + e) + (1 - x) * np.log(r2 + e), axis=-1))
+
+
+def bce2_bwd(r1, r2, x, eps, scale):
+    """(d/dr1, d/dr2, d/dx) of scale * binary_cross_entropy_2classes (utils.py:65-66)."""
+    e = r1.dtype.type(eps)
+    s = -scale / r1.shape[0]
+    return s * x / (r1 + e), s * (1 - x) / (r2 + e), s * (np.log(r1 + e) - np.log(r2 + e))
+
+
+def bce_bwd_t(p, y, eps, scale):
+    """d/dx (the target) of scale * binary_cross_entropy(p, x, eps) (utils.py:55-56)."""
+    e = p.dtype.type(eps)
+    return -(scale / p.shape[0]) * (np.log(p + e) - np.log(1 - p + e))
+
+
+def bce_v2_bwd(p, eps, scale):
+    """d/dr of scale * binary_cross_entropy_v2 (utils.py:59-60)."""
+    e = p.dtype.type(eps)
+    return -(scale / p.shape[0]) * (0.5 / (p + e) - 0.5 / (1 - p + e))
+
+
+def bce_v3_bwd(p, eps, scale):
+    """d/dr of scale * binary_cross_entropy_v3 (utils.py:62-63): r appears as the weight and inside the log."""
+    e = p.dtype.type(eps)
+    return -(scale / p.shape[0]) * (np.log(p + e) + p / (p + e) - np.log(1 - p + e) - (1 - p) / (1 - p + e))
+
+
+def sqerr(mode, x, y, yhat):
+    """packages/models/utils.py:107-118.  mode 0: mean_square_error_signal(x, y, y_hat); 1: mean_square_error_mask(y, y_hat);
+    2: magnitude_spectrum_approxiamation_loss(x, s = y, y_hat) with complex x, s and a real mask."""
+    if mode == 2:
+        d = y - yhat * x
+        return np.mean(np.sum((d * np.conj(d)).real, axis=-1))
+    d = y - yhat
+    if mode == 0:
+        d = d * x
+    return np.mean(np.sum(d * d, axis=-1))
+
+
+def sqerr_bwd(mode, x, y, yhat, scale):
+    """(dyhat, dy, dx) of scale * sqerr(mode, ...); None where the mode has no such real input (mode 1: no x; mode 2: mask only)."""
+    s = 2 * scale / yhat.shape[0]
+    if mode == 2:
+        d = y - yhat * x
+        return -s * (d * np.conj(x)).real, None, None
+    e = y - yhat
+    if mode == 1:
+        return -s * e, s * e, None
+    return -s * e * x * x, s * e * x * x, s * e * e * x
+
+
+def reparam_bwd(dz, logvar, eps_noise):
+    """(dmu, dlogvar) of z = mu + exp(0.5 log_var) * epsilon (packages/models/models.py:9-22)."""
+    return dz, dz * eps_noise * 0.5 * np.exp(0.5 * logvar)
+
+
+ACT_FWD = {0: lambda v: v, 1: np.tanh, 2: lambda v: np.maximum(v, 0), 3: lambda v: 1 / (1 + np.exp(-v)), 4: np.exp}
+# derivative through the OUTPUT, as autograd of torch.tanh / relu / sigmoid / exp has it (relu'(0) = 0)
+ACT_GRAD = {0: lambda o: np.ones_like(o), 1: lambda o: 1 - o * o, 2: lambda o: (o > 0).astype(o.dtype), 3: lambda o: o * (1 - o), 4: lambda o: o}
+
+
+def mlp_stack_fwd(x0, layers, x1=None):
+    """act_L(... act_1([x0 | x1] @ W1.T + b1) ...): packages/models/models.py:57-63 (relu stack, sigmoid head), :102-105, :119-122
+    (tanh stacks, exp head), :201-202 (the concatenated second input).  layers: [(W, b or None, act code)].  Returns every layer's output."""
+    h = x0 if x1 is None else np.concatenate([x0, x1], axis=1)
+    outs = []
+    for W, b, act in layers:
+        pre = h @ W.T
+        if b is not None:
+            pre = pre + b
+        h = ACT_FWD[act](pre)
+        outs.append(h)
+    return outs
+
+
+def mlp_stack_bwd(x0, layers, outs, dout, x1=None):
+    """Gradients of sum(dout * outs[-1]).  Returns ([(dW, db or None)], dx0, dx1 or None)."""
+    xin = x0 if x1 is None else np.concatenate([x0, x1], axis=1)
+    grads = [None] * len(layers)
+    d = dout
+    for i in reversed(range(len(layers))):
+        W, b, act = layers[i]
+        dpre = d * ACT_GRAD[act](outs[i])
+        inp = xin if i == 0 else outs[i - 1]
+        grads[i] = (dpre.T @ inp, None if b is None else dpre.sum(axis=0))
+        d = dpre @ W
+    k0 = x0.shape[1]
+    return grads, d[:, :k0], (None if x1 is None else d[:, k0:])
+
+
+# ----------------------------------------------------------------------------
 # whole-model forward / backward
 # ----------------------------------------------------------------------------
 
