@@ -379,3 +379,13 @@ class McemBatch:
         if getattr(self, "WFs", None) is None or self.WFs.shape[1] != self.ntot:
             raise RuntimeError("McemBatch.enhance: run() first")
         return STFT.istft_batch(self.spec, max_len, gain=(self.WFs, self.WFn), gain_cols=self.starts, center=center)
+
+    def score(self, s, n=None, max_len=None, trim=0):
+        """enhance() and the scale-invariant scores of its speech estimate against the clean speech s (and the noise n), nothing but
+        the result leaving the device (scripts/run_metrics.py:117-131): s / n are WaveBatches or lists of 1-D arrays / tensors, one
+        entry per utterance, as long as the estimates (max_len as for enhance()); trim: samples dropped at both ends of every
+        utterance.  -> float64 CUDA tensor [U, 3] of SI-SDR, SI-SIR, SI-SAR in dB (metrics.energy_ratios_batch), or [U] of
+        SI-SDR without n (metrics.si_sdr_batch)."""
+        from . import metrics as M
+        s_hat, _ = self.enhance(max_len)
+        return M.si_sdr_batch(s_hat, s, trim) if n is None else M.energy_ratios_batch(s_hat, s, n, trim)

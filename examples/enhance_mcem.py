@@ -5,6 +5,7 @@ device between the batch STFT and the waveforms.
 
     python examples/enhance_mcem.py --wav a.wav b.wav --checkpoint models/M2_epoch_118_vloss_407.90.pt --out enhanced/
     python examples/enhance_mcem.py --synthetic 8                       # no data at hand: modulated-noise "speech" + noise
+    python examples/enhance_mcem.py --synthetic 8 --score               # and SI-SDR of mixture and estimate, scored on the device
 
 The labels y fed to the M2 decoder are the time-domain VAD of the mixture (packages/processing/target.py); the
 reference's evaluate script takes them from a video classifier or from the clean signal (oracle), neither of which
@@ -26,15 +27,18 @@ from packages.processing.target import clean_speech_VAD
 
 McemBatch = importlib.import_module("disentangled-vae_amd.mcem").McemBatch
 stft_batch = importlib.import_module("disentangled-vae_amd.stft").stft_batch
+si_sdr_batch = importlib.import_module("disentangled-vae_amd.metrics").si_sdr_batch
 STFT = dict(fs=16000, wlen_sec=64e-3, win="hann", hop_percent=0.25, center=False)      # evaluate_ntcd_M2.py:37-45
 
 
 def synthetic_mixture(seconds, seed):
+    """-> (mixture, speech, noise), mixture = speech + noise."""
     rng = np.random.default_rng(seed)
     n = int(16000 * seconds)
     env = np.repeat((rng.random(n // 800 + 1) > 0.5).astype(np.float64), 800)[:n]      # 50 ms on/off "speech"
     s = env * rng.standard_normal(n) * np.sin(2 * np.pi * 220 * np.arange(n) / 16000 + rng.random())
-    return s + 0.2 * rng.standard_normal(n)
+    noise = 0.2 * rng.standard_normal(n)
+    return s + noise, s, noise
 
 
 def main():
@@ -45,14 +49,19 @@ def main():
     ap.add_argument("--niter", type=int, default=100)
     ap.add_argument("--precision", choices=["fp32", "bf16"], default="fp32")
     ap.add_argument("--out", default="enhanced")
+    ap.add_argument("--score", action="store_true", help="with --synthetic (whose speech is known): SI-SDR of mixture and estimate per utterance")
+    ap.add_argument("--trim", type=int, default=800, help="samples cut at both ends before scoring (run_metrics.py:117-121: 0.05 s)")
     a = ap.parse_args()
-    names, waves = [], []
+    if a.score and (a.wav or not a.synthetic):
+        ap.error("--score needs the clean speech, which only --synthetic mixtures come with")
+    names, waves, clean = [], [], []
     for p in a.wav:
         fs, w = wavfile.read(p)
         assert fs == 16000, f"{p}: 16 kHz expected"
         waves.append(w.astype(np.float64) / (32768.0 if w.dtype == np.int16 else 1.0)); names.append(os.path.splitext(os.path.basename(p))[0])
     for i in range(a.synthetic if not a.wav else 0):
-        waves.append(synthetic_mixture(3.0 + 0.25 * (i % 5), i)); names.append(f"synthetic_{i:02d}")
+        mix, speech, _ = synthetic_mixture(3.0 + 0.25 * (i % 5), i)
+        waves.append(mix); clean.append(speech); names.append(f"synthetic_{i:02d}")
     if not waves:
         ap.error("give --wav files or --synthetic N")
     torch.manual_seed(0)
@@ -82,6 +91,14 @@ def main():
     frames = sum(X.counts)
     print(f"{len(waves)} utterances, {frames} frames, {a.niter} EM iterations: {dt:.2f} s wall ({len(waves) / dt:.1f} utterances/s); "
           f"cost {cost[0].mean():.3f} -> {cost[-1].mean():.3f}")
+    if a.score:
+        # scored on the device (si_sdr_leroux of every utterance in three launches); only the two [U] results come back
+        sdr_est = mb.score(clean, max_len=[len(w) for w in waves], trim=a.trim).cpu().numpy()
+        sdr_mix = si_sdr_batch(waves, clean, trim=a.trim).cpu().numpy()
+        print(f"{'utterance':<16}{'SI-SDR mixture':>16}{'SI-SDR estimate':>17}   (dB)")
+        for name, m, e in zip(names, sdr_mix, sdr_est):
+            print(f"{name:<16}{m:>16.2f}{e:>17.2f}")
+        print(f"{'mean':<16}{sdr_mix.mean():>16.2f}{sdr_est.mean():>17.2f}")
 
 
 if __name__ == "__main__":

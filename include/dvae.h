@@ -279,6 +279,30 @@ size_t dvae_ibm_batch_workspace_bytes(int64_t n_items);
 int dvae_ibm_labels_batch(const void* S, int64_t n, float eps, float ibm_threshold, int U, const int64_t* tables, int64_t n_items,
                           int chunk, const float* vad_gate, int64_t n_gate, float* mask, void* workspace, void* stream);
 
+/* ---- scoring (packages/metrics.py:12-82: si_sdr_components, energy_ratios, si_sdr_leroux) ----
+ * dvae_si_ratios_batch: the scale-invariant energy ratios of U utterances in three launches on `stream`, no host synchronisation,
+ *   no atomics.  s_hat (the estimate), s (clean speech) and n (noise, or NULL: the n-free form of si_sdr_leroux) are packed device
+ *   buffers of n_s_hat / n_s / n_n elements, float32 or float64 by their flags; all arithmetic is in double.  With
+ *   alpha_s = <s_hat, s> / |s|^2 and alpha_n = <s_hat, n> / |n|^2 (IEEE division), per utterance
+ *     ratios[u] = 10 log10 of { |alpha_s s|^2 / |s_hat - alpha_s s|^2,  |alpha_s s|^2 / |alpha_n n|^2,
+ *                               |alpha_s s|^2 / |s_hat - alpha_s s - alpha_n n|^2 }            (SI-SDR, SI-SIR, SI-SAR in dB)
+ *     sums[u]   = { <s_hat, s>, |s|^2, <s_hat, n>, |n|^2, |s_hat - alpha_s s|^2, |s_hat - alpha_s s - alpha_n n|^2,
+ *                   alpha_s^2 |s|^2, alpha_n^2 |n|^2 }
+ *   The residuals are formed per sample with the reference's operations: e_art = (s_hat - alpha_s s) - alpha_n n, and the SI-SDR
+ *   denominator is |alpha_n n + e_art|^2 with n, |s_hat - alpha_s s|^2 without.  Without n the entries that need it are NaN.  IEEE
+ *   semantics throughout, as numpy gives the reference: an all-zero s or n gives NaN (in all three ratios), a perfect estimate +inf.  ratios [U, 3] or sums [U, 8] may be NULL, not both.
+ *   tables (device int64) = [items (U + 1) | s_hat0 (U) | s0 (U) | n0 (U) | len (U)]: utterance u is s_hat[s_hat0[u] : s_hat0[u] +
+ *   len[u]] and likewise in s and n (n0 is ignored without n); a work item is one utterance and a run of at most DVAE_SI_CHUNK of its
+ *   samples, items[u + 1] - items[u] = ceil(len[u] / DVAE_SI_CHUNK), items[U] = n_items.  The chunk is fixed, and an utterance's
+ *   partial sums are added in item order, so its results do not depend on what else is in the batch and repeat bit for bit.  The
+ *   kernels check every table entry against the scalar extents before touching memory: a bad entry leaves NaN in that utterance's
+ *   rows.  workspace: dvae_si_ratios_workspace_bytes(n_items). */
+#define DVAE_SI_CHUNK 4096
+size_t dvae_si_ratios_workspace_bytes(int64_t n_items);
+int dvae_si_ratios_batch(const void* s_hat, int64_t n_s_hat, int s_hat_f64, const void* s, int64_t n_s, int s_f64, const void* n,
+                         int64_t n_n, int n_f64, int U, const int64_t* tables, int64_t n_items, double* ratios, double* sums,
+                         void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,3 +46,7 @@ def mcem_dev():
 
 def target_dev():
     return _mod("target")
+
+
+def metrics_dev():
+    return _mod("metrics")
