@@ -7,8 +7,15 @@
 namespace dvae {
 namespace fused {
 
-// Philox4x32-10 (Salmon et al., SC'11) -> four standard normals by Box-Muller.  Counter = (frame lo, frame hi, step lo,
-// step hi << 8 | draw), key = seed: every frame of every step has its own stream, independent of tiling and grid.
+// Philox4x32-10 (Salmon et al., SC'11) -> four standard normals by Box-Muller.  Every frame of every step has its own stream,
+// independent of tiling and grid.  The contract, restated in float64 by oracle/noise_oracle.py and held per element by
+// tests/test_gpu_noise.py (measured on the MI355X: within 2.3e-6 * max(1, |value|) of the float64 transform):
+//   key      (seed lo, seed hi)
+//   counter  (frame lo, frame hi, step lo, step hi << 8 | draw): frame = position in the batch (not the gathered row), step < 2^56
+//            (training step n: n; the k-th evaluation that draws its own noise: 2^40 + k), draw 0 .. 3
+//   uniform  u = ((float)(w >> 8) + 0.5f) * 2^-24: the sum rounds to even from 2^23 on, so u lies in [2^-25, 1]; u = 1 gives radius 0
+//   normals  r = sqrt(-2 ln u0), t = 2 pi u1: out = (r cos t, r sin t), and the same from (u2, u3)
+//   layout   draw 0 -> latent features 0 .. 3, draw 1 -> 8 .. 11, draw 2 -> 4 .. 7, draw 3 -> 12 .. 15 (frame_noise8)
 __device__ __forceinline__ void philox_normal4(unsigned long long seed, unsigned long long frame, unsigned long long step, unsigned draw,
                                                float (&out)[4]) {
     unsigned c0 = (unsigned)frame, c1 = (unsigned)(frame >> 32), c2 = (unsigned)step, c3 = ((unsigned)(step >> 32) << 8) | draw;

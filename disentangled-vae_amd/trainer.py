@@ -450,7 +450,12 @@ class Trainer:
 
     def noise(self, step):
         """The [B, 16] reparametrisation noise the rows kernel draws for training step `step` (1-based) when no
-        eps_noise is passed: Philox4x32-10 keyed by the trainer's seed (and rank), counter (frame, step)."""
+        eps_noise is passed; the k-th evaluate() without eps_noise draws noise(2**40 + k) (k counted over the trainer and its forks).
+        Philox4x32-10 -> Box-Muller (csrc/rows_common.hpp; float64 restatement: oracle/noise_oracle.py):
+          key      (seed lo, seed hi) of plan.rng_seed = seed + rank * 0x9E3779B97F4A7C15 mod 2^64 (a fork keeps its parent's);
+          counter  (frame lo, frame hi, step lo, step hi << 8 | draw): frame = position in the batch, step < 2^56, draw 0 .. 3;
+          layout   draw 0 -> latent features 0 .. 3, draw 1 -> 8 .. 11, draw 2 -> 4 .. 7, draw 3 -> 12 .. 15, four normals per draw
+                   (r_a cos, r_a sin, r_b cos, r_b sin) from the uniforms ((w >> 8) + 0.5) * 2^-24 of the block's four words."""
         out = torch.empty((self.B, 16), dtype=torch.float32, device=self.device)
         N.check(self.lib.dvae_train_noise(ctypes.byref(self.plan), int(step), N.ptr(out), N.stream()), "dvae_train_noise")
         return out
