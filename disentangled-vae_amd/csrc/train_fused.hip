@@ -1640,16 +1640,6 @@ static int make_layout(const dvae_train_plan_t& p, Layout& L) {
 }
 
 static bool g_prof = false;
-static thread_local bool g_eval_only = false;
-// dvae_module_forward / dvae_module_backward: rows-kernel mode and its extra operands for the next dvae_train_grads call
-struct ModeArgs {
-    int mode = 0;
-    float *out_r = nullptr, *out_mu = nullptr, *out_lv = nullptr, *out_z = nullptr;
-    const float *g_r = nullptr, *g_mu = nullptr, *g_lv = nullptr, *g_z = nullptr;
-    int ld_r = 0, ld_gr = 0;
-};
-static thread_local ModeArgs g_mode;
-static thread_local long long g_rng_step_override = -1;   // dvae_train_step: its `step` argument numbers the noise draw   // dvae_train_eval: skip the wgrad launch
 static unsigned long long* g_dbg = nullptr;   // set by dvae_train_debug_stamps
 static double g_ms[4] = {0, 0, 0, 0};
 static int64_t g_calls[4] = {0, 0, 0, 0};
@@ -1659,7 +1649,7 @@ static int g_npending = 0;
 
 struct ProfScope {
     hipStream_t s; int which; hipEvent_t a, b; bool on;
-    ProfScope(hipStream_t s_, int w) : s(s_), which(w), on(g_prof && g_npending < 4096) {
+    __attribute__((noinline)) ProfScope(hipStream_t s_, int w) : s(s_), which(w), on(g_prof && g_npending < 4096) {      // (one copy, not one per launch site)
         if (on) { (void)hipEventCreate(&a); (void)hipEventCreate(&b); (void)hipEventRecord(a, s); }
     }
     ~ProfScope() {
@@ -1673,9 +1663,13 @@ struct ProfScope {
 using namespace dvae;
 using namespace dvae::fused;
 
+static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+static long long env_ll(const char* name, long long dflt) { const char* v = getenv(name); return v ? atoll(v) : dflt; }
 // weight-gradient kernel form: 4 = workgroup k-split 4 x 4 blocks (default), 2 = 2 x 2 register ring (DVAE_WGRAD=ring),
-// 1 = LDS-staged 4 x 4 blocks (DVAE_WGRAD=lds; bf16 policies only)
-static int wgrad_form(const char* wk) {
+// 1 = LDS-staged 4 x 4 blocks (DVAE_WGRAD=lds; bf16 policies only).  *set: the variable is there at all
+static int wgrad_form_env(bool* set = nullptr) {
+    const char* wk = getenv("DVAE_WGRAD");
+    if (set) *set = wk != nullptr;
     if (wk && strcmp(wk, "ring") == 0) return 2;
     if (wk && strcmp(wk, "lds") == 0) return 1;
     return 4;
@@ -1710,9 +1704,8 @@ extern "C" int dvae_train_plan(int model, int y_dim, int precision, int64_t B, i
     const int64_t ntiles = (B + TB - 1) / TB;
     // rows kernel generation: the 8-wave chain + helper kernel wherever it exists (M1 / M2 with bf16 or bf16x3 operands: 48 vs 55 us
     // per 8192 frames under bf16x3, 31 vs 33 us under bf16); DVAE_ROWS=1 forces the 4-wave kernel
-    const char* rk = getenv("DVAE_ROWS");
-    int want = 2;
-    if (rk && (atoi(rk) == 1 || atoi(rk) == 2 || atoi(rk) == 3)) want = atoi(rk);
+    int want = env_int("DVAE_ROWS", 2);
+    if (want < 1 || want > 3) want = 2;
     plan->rows_kernel = (want == 3 && rows3_supported(precision, model)) ? 3 : ((want >= 2 && rows2_supported(precision, model)) ? 2 : 1);
     if (!kDiagBuild && plan->rows_kernel == 1 && is_bf(precision)) {
         set_error("train_plan: DVAE_ROWS=1 (the 4-wave rows kernel) under the bf16 policies needs the diagnostic build (build.py --diag)");
@@ -1726,10 +1719,11 @@ extern "C" int dvae_train_plan(int model, int y_dim, int precision, int64_t B, i
     const int64_t maxg = plan->rows_kernel >= 2 ? 256 : 256 * (precision == DVAE_PREC_BF16 ? 2 : 1);
     plan->rows_grid = ntiles < maxg ? ntiles : maxg;
     int ks = ksplit_hint;
+    const bool wg4 = wgrad_form_env() == 4;
     // bf16: 8 slices up to 8192 frames (more slices = more slabs for the apply pass to sum); 12 beyond: 80 groups x 12 = 960
     // single-wave jobs fill the 1024 wave slots in one round (wgrad 164 -> 124 us at 65 536 frames, 2.49 -> 1.80 ms at 2^20).
     // fp32: the MFMA-bound wgrad needs a wave on every SIMD (>= 1024 wave jobs): 16.
-    if (ks <= 0 && wgrad_form(getenv("DVAE_WGRAD")) == 4) {
+    if (ks <= 0 && wg4) {
         // workgroup k-split kernel: one workgroup per (4 x 4 tile block, frame slice) and per CU: as many slices as fill the 256 CUs
         // in one round (M2 y513: 22 blocks x 11), at least 128 frames (two k-steps per wave) each, at most 16 (the apply pass sums them)
         dvae_train_plan_t tmp = *plan;
@@ -1765,7 +1759,7 @@ extern "C" int dvae_train_plan(int model, int y_dim, int precision, int64_t B, i
     // decoder-side tensors (and M2_info's side nets), then those of the encoder -- each cut to fill the CUs by itself, so that the exchange
     // of the first group's gradient can run while the second launch computes (dvae_train_grads_group; Trainer, dp.py).  Always class-sliced.
     const bool want_groups = getenv("DVAE_EXCHANGE_GROUPS") != nullptr && atoi(getenv("DVAE_EXCHANGE_GROUPS")) == 2;
-    if ((want_classes || want_groups) && ksplit_hint <= 0 && wgrad_form(getenv("DVAE_WGRAD")) == 4 && plan->Bp > 128 && getenv("DVAE_W4_UNIFORM") == nullptr &&
+    if ((want_classes || want_groups) && ksplit_hint <= 0 && wg4 && plan->Bp > 128 && getenv("DVAE_W4_UNIFORM") == nullptr &&
         getenv("DVAE_FOLD_APPLY") == nullptr && getenv("DVAE_DEFER_APPLY") == nullptr)
         w4_plan_classes(plan, want_groups);
     Layout L;
@@ -1785,7 +1779,6 @@ extern "C" int dvae_train_plan(int model, int y_dim, int precision, int64_t B, i
     return 0;
 }
 
-static int used_slabs(const dvae_train_plan_t* plan);
 static int64_t kper_of(const dvae_train_plan_t* p) {
     const int ks = is_bf(p->precision) ? 16 : 8;
     const int64_t unit = 4 * ks;
@@ -1964,8 +1957,6 @@ struct W4Grids { int g[3]; };      // table 0 (the one launch of an ungrouped pl
 static std::unordered_map<const void*, W4Grids> g_w4_grid;
 static void w4_grid_put(const void* ws, const W4Grids& grids) { std::lock_guard<std::mutex> lk(g_fold_mu); g_w4_grid[ws] = grids; }
 static int w4_grid_get(const void* ws, int table) { std::lock_guard<std::mutex> lk(g_fold_mu); auto it = g_w4_grid.find(ws); return it == g_w4_grid.end() ? -1 : it->second.g[table]; }
-// dvae_train_grads_group: which part of the step the next dvae_train_grads call runs (-1: all of it)
-static thread_local int g_w4_group = -1;
 static unsigned fold_seq_next(const void* ws) { std::lock_guard<std::mutex> lk(g_fold_mu); return ++g_fold_seq[ws]; }
 static void fold_seq_reset(const void* ws) { std::lock_guard<std::mutex> lk(g_fold_mu); g_fold_seq.erase(ws); }
 
@@ -1977,9 +1968,8 @@ static std::unordered_map<const void*, DeferState> g_defer_state;
 static DeferState defer_state_get(const void* ws) { std::lock_guard<std::mutex> lk(g_defer_mu); return g_defer_state[ws]; }
 static void defer_state_put(const void* ws, const DeferState& st) { std::lock_guard<std::mutex> lk(g_defer_mu); g_defer_state[ws] = st; }
 static void defer_state_reset(const void* ws) { std::lock_guard<std::mutex> lk(g_defer_mu); g_defer_state.erase(ws); }
-// dvae_train_step_deferred -> dvae_train_grads: run the rows kernel in its deferred form
+// dvae_train_step_deferred -> run_grads: run the rows kernel in its deferred form
 struct DeferRequest { bool on = false, have = false; PendingUpdate u{}; unsigned seq_arrive = 0, seq_done = 0; float* losses3 = nullptr; };
-static thread_local DeferRequest g_defer_req;
 
 // tasks of the deferred update (apply_common.hpp: DeferTask): 32 x 32 tiles of every tensor with kernel-layout copies, per column block
 // (a tile never straddles the split of the forward copy), and 1024-element chunks of the tensors without copies
@@ -2118,6 +2108,12 @@ static int64_t w4_kper(const dvae_train_plan_t& p, int slices) {
 // least 128 frames per slice
 static inline bool w4_classed(const dvae_train_plan_t& p) { return (p.reserved0 & ~W4_GROUPED) > 0; }
 static inline bool w4_grouped(const dvae_train_plan_t& p) { return (p.reserved0 & W4_GROUPED) != 0; }
+// gradient slabs a step fills, for the optimizer launch to sum
+static int used_slabs(const dvae_train_plan_t* plan) {
+    if (w4_classed(*plan)) return plan->ksplit;                          // class-sliced schedule: the largest slice count of any block
+    const int64_t kper = kper_of(plan);
+    return (int)((plan->Bp + kper - 1) / kper);
+}
 // group of a block in the two-launch schedule: 0 = launched first (decoder layers 3-5 and, M2_info, the side nets 6-11: tensors 8 and up, the
 // upper part of the flat gradient), 1 = the encoder (layers 0-2: tensors 0-7, the lower part)
 static inline int w4_group_of(const Block4& b) { return b.layer <= 2 ? 1 : 0; }
@@ -2321,13 +2317,12 @@ extern "C" int dvae_train_init(const dvae_train_plan_t* plan, const float* param
     return dvae_train_repack(plan, params, ws, stream);
 }
 
+static int current_device() { int dev = 0; (void)hipGetDevice(&dev); return dev < 0 || dev >= 64 ? 0 : dev; }      // (index of the per-device tables: 64 entries)
 template <typename P, int YP, bool YENC, bool INFO = false>
 static int launch_rows(const RowsArgs& a, int grid, hipStream_t s) {
     const size_t lds = Pl<P>::bytes;
     static bool attr_done[64] = {};                      // per device: the attribute belongs to the device's copy of the code object
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64) dev = 0;
+    const int dev = current_device();
     if (!attr_done[dev]) {
         hipError_t e = hipFuncSetAttribute((const void*)vae_rows_kernel<P, YP, YENC, INFO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) { set_error("hipFuncSetAttribute(rows kernel, %zu B LDS): %s", lds, hipGetErrorString(e)); return (int)e; }
@@ -2338,17 +2333,11 @@ static int launch_rows(const RowsArgs& a, int grid, hipStream_t s) {
     return 0;
 }
 
-// dvae_train_step -> dvae_train_grads: "run the optimizer step in the weight-gradient launch if you can" (done: it did)
-struct FoldRequest {
-    bool want = false, done = false;
-    float* params = nullptr; float* m = nullptr; float* v = nullptr; float* losses3 = nullptr;
-    int step = 0; double lr = 0, beta1 = 0, beta2 = 0, adam_eps = 0;
-};
-static thread_local FoldRequest g_fold;
+// dvae_train_step -> run_grads: "run the optimizer step in the weight-gradient launch if you can" (done: the answer, it did)
+struct FoldRequest { bool want = false, done = false; PendingUpdate u{}; float* losses3 = nullptr; };
 
 static int device_cu_count(int dev) {
     static int cus[64] = {};
-    if (dev < 0 || dev >= 64) dev = 0;
     if (cus[dev] == 0) {
         int n = 0;
         if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 1;
@@ -2380,12 +2369,11 @@ static bool defer_possible(const dvae_train_plan_t* plan, const void* ws) {
     if (!(plan->rows_kernel == 2 && rows2_supported(plan->precision, plan->model))) return false;
     if (!(plan->model == DVAE_MODEL_M1 || plan->model == DVAE_MODEL_M2)) return false;
     if (plan->row_index != 0 && plan->row_count <= 0) return false;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
+    const int dev = current_device();
     const int nt = defer_state_get(ws).ntasks;
     if (nt <= 0 || nt > DEFER_MAX_TASKS) return false;
     if (plan->rows_grid > device_cu_count(dev) || 8 * plan->rows_grid < 4 * nt) return false;      // at most two 8-row units per chain wave
-    if (wgrad_form(getenv("DVAE_WGRAD")) != 4 || plan->Bp <= 128) return false;      // the loss scalars come from an extra workgroup of wgrad4_kernel
+    if (wgrad_form_env() != 4 || plan->Bp <= 128) return false;      // the loss scalars come from an extra workgroup of wgrad4_kernel
     const int64_t kper = kper_of(plan);
     return (plan->Bp + kper - 1) / kper <= 12;
 }
@@ -2393,28 +2381,79 @@ static bool defer_possible(const dvae_train_plan_t* plan, const void* ws) {
 extern "C" int dvae_train_can_defer(const dvae_train_plan_t* plan, const void* ws) {
     if (!plan || !ws) return 0;
     // OPT-IN (DVAE_DEFER_APPLY=1): bit-identical and, on the MI355X, not faster -- see DESIGN.md (round 4, item 3) for the ablation
-    const char* de = getenv("DVAE_DEFER_APPLY");
-    if (!kDiagBuild || !(de && atoi(de) == 1) || getenv("DVAE_FOLD_APPLY") != nullptr) return 0;      // (the deferred rows kernel exists in -DDVAE_DIAG builds only)
+    if (!kDiagBuild || env_int("DVAE_DEFER_APPLY", 0) != 1 || getenv("DVAE_FOLD_APPLY") != nullptr) return 0;      // (the deferred rows kernel exists in -DDVAE_DIAG builds only)
     return defer_possible(plan, ws) ? 1 : 0;
 }
 
-extern "C" int dvae_train_grads(const dvae_train_plan_t* plan, const float* params, void* ws, const float* x, int ldx,
-                                const float* y, int ldy, const float* eps_noise, float elbo_eps, int reduce_slabs, void* stream) {
-    DVAE_CHECK_ARG(plan && params && ws && x && ldx >= XD, "train_grads: bad argument");
-    DVAE_CHECK_ARG(plan->y_dim == 0 || (y != nullptr && ldy >= plan->y_dim), "train_grads: y missing or ldy < y_dim");
-    if (!g_defer_req.on) { const int frc = dvae_train_flush(plan, ws, stream); if (frc) return frc; }
-    Layout L;
-    make_layout(*plan, L);
-    hipStream_t s = (hipStream_t)stream;
-    char* w = (char*)ws;
-    const bool bf = plan->precision == DVAE_PREC_BF16, x3 = plan->precision == DVAE_PREC_BF16X3;
-    const int esz = (bf || x3) ? 2 : 4;
-    RowsArgs a;
+// What one gradient pass runs beyond the arguments of dvae_train_grads (the defaults: dvae_train_grads itself); the entry points fill in theirs
+struct GradsOptions {
+    int mode = 0;                       // rows kernel: 0 the train step, 1 dvae_module_forward (writes out_*), 2 dvae_module_backward (reads g_*)
+    float *out_r = nullptr, *out_mu = nullptr, *out_lv = nullptr, *out_z = nullptr;
+    const float *g_r = nullptr, *g_mu = nullptr, *g_lv = nullptr, *g_z = nullptr;
+    int ld_r = 0, ld_gr = 0;
+    bool rows_only = false;             // dvae_train_eval: no weight-gradient launch (mode 1 stops after the rows kernel too)
+    long long rng_step = -1;            // dvae_train_step, dvae_train_step_deferred: their `step` argument numbers the noise draw; -1 = plan->rng_step
+    int group = -1;                     // dvae_train_grads_group: -1 the whole step, 0 rows + first wgrad launch, 1 second wgrad launch
+    DeferRequest defer;                 // dvae_train_step_deferred
+    FoldRequest fold;                   // dvae_train_step; fold.done comes back
+};
+
+namespace {      // (internal: the constructor is a real function)
+// The environment of one gradient pass, read once at the top of run_grads -- per call: tests flip these between calls.
+struct StepEnv {
+    // DVAE_WGRAD (wgrad_form_env).  =lds selects the workgroup-blocked kernel for the bf16 policies (operands staged once per 4 x 4 block in
+    // LDS: half the L2 -> CU operand traffic).  Measured (M2 y513, 8192 frames): 39.3 vs 32.9 us under bf16x3, 25.0 vs 21.4 us under bf16 --
+    // SLOWER than the register-ring kernel at every k-split tried, and both kernels take the same time on a stash that is already cache-warm:
+    // the weight-gradient pass is bound neither by operand traffic nor by cold reads.  The register-ring kernel stays default.
+    bool wgrad_set = false;
+    int wgrad_form = wgrad_form_env(&wgrad_set);
+    int ablate = env_int("DVAE_ABLATE", 0);
+    // DVAE_RAW_INPUTS=1 (opt-in, tested): the weight-gradient kernel takes x and the labels straight from the fp32 input matrices and the
+    // rows kernel writes no stash for them (35 MB of writes less in its HBM-bound opening window).  Measured (M2 y513, 8192 frames, bf16x3,
+    // same box, alternating): rows 46.0 -> 44.0 us, but the weight-gradient kernel 29.0 -> 34.6 us -- its input-fed blocks convert and
+    // transpose 8 KB per k-step and wave through LDS behind a two-deep ring -- so the stash stays the default (step 78.6 vs 81.8 us).
+    // Round 4, large batches: from ~1e5 frames on the rows kernel runs many tiles per workgroup and sets the step time (4.7 ns per frame against
+    // 2.5 for the weight-gradient kernel, which is HBM-bound there), so the 6.3 KB per frame of input stash it no longer writes pay:
+    // B = 262 144: 139.3 -> 143.2 M frames/s, B = 2^20: 137.0 -> 142.8 (x only: 143.3 / 139.1; profiles/r04_bigb_raw.txt).  Chosen
+    // automatically from DVAE_RAW_AUTO_B frames on (131 072); DVAE_RAW_INPUTS=0 keeps the stash, =x / =1 force a variant at any size.
+    // -1 unset, 0 "0"; else the mask of inputs read raw: 1 "x" (only the x tile; the label stash stays: one plane for binary labels), 3 any other value
+    int raw_inputs = -1;
+    int64_t raw_auto_b = env_ll("DVAE_RAW_AUTO_B", 131072);
+    bool ylo_always = getenv("DVAE_YLO_ALWAYS") != nullptr;
+    int wgrad_repeat = std::max(env_int("DVAE_WGRAD_REPEAT", 1), 1);      // diagnostic: re-run the weight-gradient launch on the warm stash
+    int gpw = env_int("DVAE_GPW", 2);                                     // diagnostic override: groups (waves) per workgroup of the 2 x 2 kernel, 1..4
+    unsigned fold_max_polls = 1u << 20;                                   // DVAE_FOLD_MAX_POLLS
+    int defer_diag = env_int("DVAE_DEFER_DIAG", 0);
+    long long defer_timeout_ms = std::max(env_ll("DVAE_DEFER_TIMEOUT_MS", 2000), 0ll);      // bound of the arrival wait (the whole grid is resident: it is microseconds)
+    StepEnv() {
+        if (const char* v = getenv("DVAE_RAW_INPUTS")) raw_inputs = strcmp(v, "0") == 0 ? 0 : (strcmp(v, "x") == 0 ? 1 : 3);
+        if (gpw < 1 || gpw > 4) gpw = 2;
+        if (const char* v = getenv("DVAE_FOLD_MAX_POLLS")) fold_max_polls = (unsigned)strtoul(v, nullptr, 10);
+    }
+};
+}
+
+// A grouped step is two calls: the launch of group 1 belongs to the rows kernel of the group 0 call on the same workspace and reuses its
+// launch id, or its label blocks would misread the epoch word.  The one state that crosses calls, per thread.
+static thread_local struct GroupPairing { unsigned last_id = 0; const void* last_ws = nullptr; } g_pairing;
+
+// f(P{}) for the operand policy P of plan->precision
+template <typename F>
+static auto with_policy(int precision, F&& f) {
+    if (precision == DVAE_PREC_BF16X3) return f(PolX3{});
+    if (precision == DVAE_PREC_BF16) return f(PolBF16{});
+    return f(PolF32{});
+}
+
+// the rows kernel's arguments from plan, layout and options (all but ylo_skip, which run_grads decides); host arithmetic only
+static int fill_rows_args(const dvae_train_plan_t* plan, const Layout& L, const GradsOptions& o, const StepEnv& env, const float* params, char* w,
+                          const float* x, int ldx, const float* y, int ldy, const float* eps_noise, float elbo_eps, RowsArgs& a) {
+    const int esz = is_bf(plan->precision) ? 2 : 4;
     memset(&a, 0, sizeof(a));
     a.rows = (const int64_t*)(uintptr_t)plan->row_index;
     a.n_rows = plan->row_count; a.bad_rows = (int*)(uintptr_t)plan->bad_row_counter;
     DVAE_CHECK_ARG(a.rows == nullptr || a.n_rows > 0, "train_grads: row_index set but row_count <= 0");
-    a.rng_seed = plan->rng_seed; a.rng_step = g_rng_step_override >= 0 ? (unsigned long long)g_rng_step_override : plan->rng_step;
+    a.rng_seed = plan->rng_seed; a.rng_step = o.rng_step >= 0 ? (unsigned long long)o.rng_step : plan->rng_step;
     a.x = x; a.y = y; a.eps = eps_noise; a.ldx = ldx; a.ldy = plan->y_dim ? ldy : 0; a.ydim = plan->y_dim;
     a.fastx = (ldx == XD) && (((uintptr_t)x & 15) == 0);
     a.fasty = (plan->y_dim == XD) && (ldy == XD) && (((uintptr_t)y & 15) == 0);
@@ -2437,63 +2476,37 @@ extern "C" int dvae_train_grads(const dvae_train_plan_t* plan, const float* para
     a.partials = (double*)(w + L.o_partials);
     a.wcopy = wc; a.wcopy_bytes = L.wcopy_elems * esz * planes_of(plan->precision);
     a.spl = L.stash_rows * plan->Bp; a.wpl_bytes = (unsigned)(L.wcopy_elems * esz);
-    a.dbg = g_dbg;
-    { const char* ab = getenv("DVAE_ABLATE"); a.ablate = ab ? atoi(ab) : 0; }
-    if (g_defer_req.on) {
-        const PendingUpdate& u = g_defer_req.u;
-        a.defer.on = 1; a.defer.have = g_defer_req.have ? 1 : 0;
-        { const char* e = getenv("DVAE_DEFER_DIAG"); a.defer.diag = e ? atoi(e) : 0; }
-        a.defer.a = g_defer_req.have ? make_apply_args(plan, L, u.params, u.m, u.v, w, u.n_slabs, true, u.step, u.lr, u.beta1, u.beta2, u.adam_eps, 1.0, g_defer_req.losses3)
-                                     : make_apply_args(plan, L, const_cast<float*>(params), nullptr, nullptr, w, 1, false, 1, 0, 0, 0, 0, 0, g_defer_req.losses3);
-        a.defer.tasks = (const DeferTask*)(w + L.o_defer); a.defer.ntasks = defer_state_get(ws).ntasks;
+    a.dbg = g_dbg; a.ablate = env.ablate;
+    if (o.defer.on) {
+        const PendingUpdate& u = o.defer.u;
+        a.defer.on = 1; a.defer.have = o.defer.have ? 1 : 0;
+        a.defer.diag = env.defer_diag;
+        a.defer.a = o.defer.have ? make_apply_args(plan, L, u.params, u.m, u.v, w, u.n_slabs, true, u.step, u.lr, u.beta1, u.beta2, u.adam_eps, 1.0, o.defer.losses3)
+                                 : make_apply_args(plan, L, const_cast<float*>(params), nullptr, nullptr, w, 1, false, 1, 0, 0, 0, 0, 0, o.defer.losses3);
+        a.defer.tasks = (const DeferTask*)(w + L.o_defer); a.defer.ntasks = defer_state_get(w).ntasks;
         a.defer.shard = (unsigned*)(w + L.o_defer + DEFER_O_SHARD);
         a.defer.done = (unsigned*)(w + L.o_defer + DEFER_O_DONE); a.defer.err = a.defer.done + 1;
-        a.defer.seq_arrive = g_defer_req.seq_arrive; a.defer.seq_done = g_defer_req.seq_done;
-        long long ms = 2000;                                   // bound of the arrival wait (the whole grid is resident: it is microseconds)
-        { const char* e = getenv("DVAE_DEFER_TIMEOUT_MS"); if (e) ms = atoll(e); }
-        a.defer.timeout_ticks = (unsigned long long)(ms < 0 ? 0 : ms) * 100000ull;
+        a.defer.seq_arrive = o.defer.seq_arrive; a.defer.seq_done = o.defer.seq_done;
+        a.defer.timeout_ticks = (unsigned long long)env.defer_timeout_ms * 100000ull;
     }
-    // DVAE_RAW_INPUTS=1 (opt-in, tested): the weight-gradient kernel takes x and the labels straight from the fp32 input matrices and the
-    // rows kernel writes no stash for them (35 MB of writes less in its HBM-bound opening window).  Measured (M2 y513, 8192 frames, bf16x3,
-    // same box, alternating): rows 46.0 -> 44.0 us, but the weight-gradient kernel 29.0 -> 34.6 us -- its input-fed blocks convert and
-    // transpose 8 KB per k-step and wave through LDS behind a two-deep ring -- so the stash stays the default (step 78.6 vs 81.8 us).
-    // Round 4, large batches: from ~1e5 frames on the rows kernel runs many tiles per workgroup and sets the step time (4.7 ns per frame against
-    // 2.5 for the weight-gradient kernel, which is HBM-bound there), so the 6.3 KB per frame of input stash it no longer writes pay:
-    // B = 262 144: 139.3 -> 143.2 M frames/s, B = 2^20: 137.0 -> 142.8 (x only: 143.3 / 139.1; profiles/r04_bigb_raw.txt).  Chosen
-    // automatically from DVAE_RAW_AUTO_B frames on (131 072); DVAE_RAW_INPUTS=0 keeps the stash, =x / =1 force a variant at any size.
-    const char* raw_env = getenv("DVAE_RAW_INPUTS");
     const bool raw_possible = plan->rows_kernel >= 2 && rows2_supported(plan->precision, plan->model) && a.rows == nullptr &&
-                              wgrad_form(getenv("DVAE_WGRAD")) == 4 && g_mode.mode != 1;
-    int64_t raw_auto_b = 131072;
-    { const char* e = getenv("DVAE_RAW_AUTO_B"); if (e) raw_auto_b = atoll(e); }
-    const bool raw_auto = raw_env == nullptr && raw_possible && g_mode.mode == 0 && plan->B >= raw_auto_b;
-    const bool raw_inputs = raw_possible && ((raw_env != nullptr && strcmp(raw_env, "0") != 0) || raw_auto);
-    // DVAE_RAW_INPUTS=x: only the x tile is read raw (the label stash stays: one plane for binary labels); any other value: x and labels
-    const int raw_mask = !raw_inputs ? 0 : ((raw_env != nullptr && strcmp(raw_env, "x") == 0) ? 1 : 3);
+                              env.wgrad_form == 4 && o.mode != 1;
+    const bool raw_auto = env.raw_inputs < 0 && raw_possible && o.mode == 0 && plan->B >= env.raw_auto_b;
+    const int raw_mask = !raw_possible ? 0 : (raw_auto ? 3 : std::max(env.raw_inputs, 0));
     a.stash_inputs = 3 & ~raw_mask;
-    a.mode = g_mode.mode;
-    {   // label lo plane on demand: 8-wave kernel + the workgroup k-split weight-gradient kernel, split-bf16 operands, labels from the stash
-        static std::atomic<unsigned> launch_counter{1};
-        const char* wk0 = getenv("DVAE_WGRAD");
-        const bool wg4 = wgrad_form(wk0) == 4 && (plan->Bp > 128 || raw_inputs || wk0 != nullptr);
-        a.ylo_epoch = (unsigned*)(w + L.o_flags);
-        a.ylo_dirty = (int*)(w + L.o_flags + 1024);
-        // (the second launch of a grouped step belongs to the rows kernel of the first call: same id, or its label blocks would misread the epoch word)
-        static thread_local unsigned last_id = 0;
-        static thread_local const void* last_ws = nullptr;
-        if (g_w4_group == 1) {
-            DVAE_CHECK_ARG(last_ws == ws && last_id != 0, "train_grads_group: group 1 must follow a group 0 call on the same workspace");
-            a.launch_id = last_id;
-        } else {
-            a.launch_id = launch_counter.fetch_add(1, std::memory_order_relaxed);
-            if (a.launch_id == 0) a.launch_id = launch_counter.fetch_add(1, std::memory_order_relaxed);      // 0 = the memset value of a fresh workspace
-            last_id = a.launch_id; last_ws = ws;
-        }
-        a.ylo_skip = (x3 && plan->y_dim > 0 && plan->rows_kernel >= 2 && rows2_supported(plan->precision, plan->model) && wg4 && !(raw_mask & 2) &&
-                      getenv("DVAE_YLO_ALWAYS") == nullptr) ? 1 : 0;
+    a.mode = o.mode;
+    a.ylo_epoch = (unsigned*)(w + L.o_flags); a.ylo_dirty = (int*)(w + L.o_flags + 1024);
+    static std::atomic<unsigned> launch_counter{1};
+    if (o.group == 1) {
+        DVAE_CHECK_ARG(g_pairing.last_ws == w && g_pairing.last_id != 0, "train_grads_group: group 1 must follow a group 0 call on the same workspace");
+        a.launch_id = g_pairing.last_id;
+    } else {
+        a.launch_id = launch_counter.fetch_add(1, std::memory_order_relaxed);
+        if (a.launch_id == 0) a.launch_id = launch_counter.fetch_add(1, std::memory_order_relaxed);      // 0 = the memset value of a fresh workspace
+        g_pairing = GroupPairing{a.launch_id, w};
     }
-    a.out_r = g_mode.out_r; a.out_mu = g_mode.out_mu; a.out_lv = g_mode.out_lv; a.out_z = g_mode.out_z; a.ld_r = g_mode.ld_r;
-    a.g_r = g_mode.g_r; a.g_mu = g_mode.g_mu; a.g_lv = g_mode.g_lv; a.g_z = g_mode.g_z; a.ld_gr = g_mode.ld_gr;
+    a.out_r = o.out_r; a.out_mu = o.out_mu; a.out_lv = o.out_lv; a.out_z = o.out_z; a.ld_r = o.ld_r;
+    a.g_r = o.g_r; a.g_mu = o.g_mu; a.g_lv = o.g_lv; a.g_z = o.g_z; a.ld_gr = o.ld_gr;
     DVAE_CHECK_ARG(a.mode == 0 || plan->rows_kernel == 2, "rows-kernel modes 1 / 2 exist in the 8-wave kernel only (plan->rows_kernel == 2)");
     char* st = w + L.o_stash;
     auto ST = [&](int64_t row) { return (void*)(st + row * plan->Bp * esz); };
@@ -2503,149 +2516,156 @@ extern "C" int dvae_train_grads(const dvae_train_plan_t* plan, const float* para
         a.c1T = ST(L.c1T); a.c2T = ST(L.c2T); a.dc1T = ST(L.dc1T); a.dc2T = ST(L.dc2T); a.dc3T = ST(L.dc3T);
         a.a1T = ST(L.a1T); a.a2T = ST(L.a2T); a.da1T = ST(L.da1T); a.da2T = ST(L.da2T); a.da3T = ST(L.da3T);
     }
+    return 0;
+}
+
+static int launch_rows_kernel(const dvae_train_plan_t* plan, const RowsArgs& a, hipStream_t s) {
     const int grid = (int)plan->rows_grid;
-    const bool m2 = plan->model == DVAE_MODEL_M2;
-    const int gsel = g_w4_group;                                          // dvae_train_grads_group: -1 the whole step, 0 rows + first wgrad launch, 1 second wgrad launch
-    DVAE_CHECK_ARG(gsel < 0 || (w4_grouped(*plan) && g_mode.mode == 0 && !g_eval_only), "train_grads_group: the plan was not made for two weight-gradient launches (DVAE_EXCHANGE_GROUPS=2 when the plan is made)");
-    int rc = 0;
-    if (gsel != 1) {
-        ProfScope ps(s, 0);
-        if (plan->rows_kernel == 3 && rows3_supported(plan->precision, plan->model)) {
-            rc = launch_rows3(plan->model, plan->y_dim, a, grid, s);
-        } else if (plan->rows_kernel == 2 && rows2_supported(plan->precision, plan->model)) {
-            rc = launch_rows2(plan->precision, plan->model, plan->y_dim, a, grid, s);
+    if (plan->rows_kernel == 3 && rows3_supported(plan->precision, plan->model)) return launch_rows3(plan->model, plan->y_dim, a, grid, s);
+    if (plan->rows_kernel == 2 && rows2_supported(plan->precision, plan->model)) return launch_rows2(plan->precision, plan->model, plan->y_dim, a, grid, s);
+    auto rows4 = [&](auto pol) {      // the 4-wave kernel of one operand policy, in the plan's model variant
+        using P = decltype(pol);
+        if (plan->model == DVAE_MODEL_M2_INFO) return launch_rows<P, 16, false, true>(a, grid, s);
+        if (plan->model != DVAE_MODEL_M2) return launch_rows<P, 0, false>(a, grid, s);
+        if (plan->y_dim == 1) return launch_rows<P, 16, true>(a, grid, s);
+        return launch_rows<P, 528, true>(a, grid, s);
+    };
 #ifdef DVAE_DIAG
-        } else if (x3) {
-            if (L.info) rc = launch_rows<PolX3, 16, false, true>(a, grid, s);
-            else if (!m2) rc = launch_rows<PolX3, 0, false>(a, grid, s);
-            else if (plan->y_dim == 1) rc = launch_rows<PolX3, 16, true>(a, grid, s);
-            else rc = launch_rows<PolX3, 528, true>(a, grid, s);
-        } else if (bf) {
-            if (L.info) rc = launch_rows<PolBF16, 16, false, true>(a, grid, s);
-            else if (!m2) rc = launch_rows<PolBF16, 0, false>(a, grid, s);
-            else if (plan->y_dim == 1) rc = launch_rows<PolBF16, 16, true>(a, grid, s);
-            else rc = launch_rows<PolBF16, 528, true>(a, grid, s);
+    return with_policy(plan->precision, rows4);
 #else
-        } else if (x3 || bf) {
-            set_error("train_grads: the 4-wave rows kernel under the bf16 policies exists in the diagnostic build only (build.py --diag)");
-            rc = DVAE_E_UNSUPPORTED;
-#endif
-        } else {
-            if (L.info) rc = launch_rows<PolF32, 16, false, true>(a, grid, s);
-            else if (!m2) rc = launch_rows<PolF32, 0, false>(a, grid, s);
-            else if (plan->y_dim == 1) rc = launch_rows<PolF32, 16, true>(a, grid, s);
-            else rc = launch_rows<PolF32, 528, true>(a, grid, s);
-        }
+    if (is_bf(plan->precision)) {
+        set_error("train_grads: the 4-wave rows kernel under the bf16 policies exists in the diagnostic build only (build.py --diag)");
+        return DVAE_E_UNSUPPORTED;
     }
-    if (rc) return rc;
-    if (g_eval_only || a.mode == 1) return 0;
+    return rows4(PolF32{});
+#endif
+}
+
+// the weight-gradient launch(es) over the stash the rows kernel left, then the optional slab reduction; wg4: the workgroup k-split kernel
+static int launch_wgrad_pass(const dvae_train_plan_t* plan, const Layout& L, GradsOptions& o, const StepEnv& env, const RowsArgs& a, bool wg4,
+                             char* w, int reduce_slabs, hipStream_t s) {
+    const bool x3 = plan->precision == DVAE_PREC_BF16X3;
     const int64_t kper = kper_of(plan);
-    const int ks = w4_classed(*plan) ? plan->ksplit : (int)((plan->Bp + kper - 1) / kper);      // slabs the launch fills (class-sliced: the largest slice count)
+    const int ks = used_slabs(plan);                                      // slabs the launch fills
     DVAE_CHECK_ARG(ks <= plan->ksplit, "train_grads: internal k-split mismatch");
-    DVAE_CHECK_ARG(!w4_classed(*plan) || wgrad_form(getenv("DVAE_WGRAD")) == 4,
+    DVAE_CHECK_ARG(!w4_classed(*plan) || env.wgrad_form == 4,
                    "train_grads: the plan was made for the workgroup k-split weight-gradient kernel (class-sliced schedule); DVAE_WGRAD changed since");
     float* slabs = (float*)(w + L.o_grads);
-    // DVAE_WGRAD=lds selects the workgroup-blocked kernel for the bf16 policies (operands staged once per 4 x 4 block in LDS: half the
-    // L2 -> CU operand traffic).  Measured (M2 y513, 8192 frames): 39.3 vs 32.9 us under bf16x3, 25.0 vs 21.4 us under bf16 -- SLOWER than the
-    // register-ring kernel at every k-split tried, and both kernels take the same time on a stash that is already cache-warm: the
-    // weight-gradient pass is bound neither by operand traffic nor by cold reads.  The register-ring kernel stays default.
-    const char* wk = getenv("DVAE_WGRAD");
-    int wrep = 1;
-    { const char* e = getenv("DVAE_WGRAD_REPEAT"); if (e) { wrep = atoi(e); if (wrep < 1) wrep = 1; } }   // diagnostic: re-run on the warm stash
-    for (int rep = 0; rep < wrep; ++rep)
-    if (wgrad_form(wk) == 4 && (plan->Bp > 128 || raw_inputs || wk != nullptr)) {      // one 128-frame slice: the 2 x 2 kernel's short epilogue wins (11.2 vs 12.8 us)
-      // one launch (table 0), or the launches of a grouped plan: tables 1 and 2, both (gsel < 0) or the one asked for
-      const int tb0 = !w4_grouped(*plan) ? 0 : (gsel == 1 ? 2 : 1), tb1 = !w4_grouped(*plan) ? 0 : (gsel == 0 ? 1 : 2);
-      for (int tb = tb0; tb <= tb1; ++tb) {
-        ProfScope ps(s, rep == 0 ? 1 : 2);
-        const int w4grid = w4_grid_get(w, tb);
-        DVAE_CHECK_ARG(w4grid > 0, "train_grads: workspace was not set up by dvae_train_init");
-        const dim3 g3((unsigned)w4grid);                                  // one workgroup per item of the host's table (w4_build_items)
-        RawIn ri;
-        ri.x = x; ri.y = y; ri.ldx = ldx; ri.ldy = plan->y_dim ? ldy : 0; ri.B = plan->B;
-        const int use_raw = raw_mask;
-        static bool attr_done[64][3] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64) dev = 0;
-        const int pi = x3 ? 2 : (bf ? 1 : 0);
-        if (!attr_done[dev][pi]) {
-            if (x3) DVAE_HIP(hipFuncSetAttribute((const void*)wgrad4_kernel<PolX3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Wg4<PolX3>::BYTES));
-            else if (bf) DVAE_HIP(hipFuncSetAttribute((const void*)wgrad4_kernel<PolBF16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Wg4<PolBF16>::BYTES));
-            else DVAE_HIP(hipFuncSetAttribute((const void*)wgrad4_kernel<PolF32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Wg4<PolF32>::BYTES));
-            attr_done[dev][pi] = true;
-        }
-        const Block4* bl = (const Block4*)(w + L.o_blocks4);
-        const W4Item* w4items = (const W4Item*)(w + L.o_items4) + (size_t)tb * W4_MAX_ITEMS;
-        // the optimizer step in this launch's tail (dvae_train_step asked for it): only when every workgroup of the grid is resident at
-        // once -- one per CU, the tail's wait depends on it -- and the block counters fit the flag header
-        ApplyArgs fa_apply;
-        memset(&fa_apply, 0, sizeof(fa_apply));
-        FoldArgs fold{nullptr, 0u, 0u};
-        if (g_fold.want && !w4_classed(*plan) && wrep == 1 && a.mode == 0 && ks > 1 && ks <= 16 && L.nblocks4 <= FOLD_MAXB && (int)g3.x <= device_cu_count(dev)) {
-            fa_apply = make_apply_args(plan, L, g_fold.params, g_fold.m, g_fold.v, w, ks, true, g_fold.step, g_fold.lr, g_fold.beta1, g_fold.beta2,
-                                       g_fold.adam_eps, 1.0, g_fold.losses3);
-            fold.cnt = (unsigned*)(w + L.o_flags);
-            fold.target = (unsigned)ks * fold_seq_next(w);
-            fold.max_polls = 1u << 20;
-            { const char* e = getenv("DVAE_FOLD_MAX_POLLS"); if (e) fold.max_polls = (unsigned)strtoul(e, nullptr, 10); }
-            g_fold.done = true;
-        }
-        int fin_block = -1;
-        const unsigned* fin_err = nullptr;
-        dim3 g3l = g3;
-        if (a.defer.on) {                                             // + one workgroup that turns the rows kernel's partial sums into the loss scalars
-            fa_apply = a.defer.a;
-            fin_block = (int)g3.x; fin_err = a.defer.err;
-            g3l = dim3(g3.x + 1);
-        }
-        if (x3) hipLaunchKernelGGL((wgrad4_kernel<PolX3>), g3l, dim3(256), Wg4<PolX3>::BYTES, s, bl, w4items, ks, plan->Bp, a.spl, slabs, plan->n_params, ri, use_raw, a.ylo_skip ? a.ylo_epoch : nullptr, a.launch_id, fa_apply, fold, fin_block, fin_err);
-        else if (bf) hipLaunchKernelGGL((wgrad4_kernel<PolBF16>), g3l, dim3(256), Wg4<PolBF16>::BYTES, s, bl, w4items, ks, plan->Bp, a.spl, slabs, plan->n_params, ri, use_raw, (const unsigned*)nullptr, 0u, fa_apply, fold, fin_block, fin_err);
-        else hipLaunchKernelGGL((wgrad4_kernel<PolF32>), g3l, dim3(256), Wg4<PolF32>::BYTES, s, bl, w4items, ks, plan->Bp, a.spl, slabs, plan->n_params, ri, use_raw, (const unsigned*)nullptr, 0u, fa_apply, fold, fin_block, fin_err);
-        DVAE_LAUNCH_OK("wgrad4_kernel");
-      }
+    const int dev = current_device();
+    for (int rep = 0; rep < env.wgrad_repeat; ++rep) {
+        if (wg4) {
+            // one launch (table 0), or the launches of a grouped plan: tables 1 and 2, both (group < 0) or the one asked for
+            const int tb0 = !w4_grouped(*plan) ? 0 : (o.group == 1 ? 2 : 1), tb1 = !w4_grouped(*plan) ? 0 : (o.group == 0 ? 1 : 2);
+            for (int tb = tb0; tb <= tb1; ++tb) {
+                ProfScope ps(s, rep == 0 ? 1 : 2);
+                const int w4grid = w4_grid_get(w, tb);
+                DVAE_CHECK_ARG(w4grid > 0, "train_grads: workspace was not set up by dvae_train_init");
+                const dim3 g3((unsigned)w4grid);                                  // one workgroup per item of the host's table (w4_build_items)
+                const RawIn ri{a.x, a.y, a.ldx, a.ldy, a.B};
+                const int use_raw = 3 & ~a.stash_inputs;
+                const Block4* bl = (const Block4*)(w + L.o_blocks4);
+                const W4Item* w4items = (const W4Item*)(w + L.o_items4) + (size_t)tb * W4_MAX_ITEMS;
+                // the optimizer step in this launch's tail (dvae_train_step asked for it): only when every workgroup of the grid is resident at
+                // once -- one per CU, the tail's wait depends on it -- and the block counters fit the flag header
+                ApplyArgs fa_apply;
+                memset(&fa_apply, 0, sizeof(fa_apply));
+                FoldArgs fold{nullptr, 0u, 0u};
+                const PendingUpdate& u = o.fold.u;
+                if (o.fold.want && !w4_classed(*plan) && env.wgrad_repeat == 1 && a.mode == 0 && ks > 1 && ks <= 16 && L.nblocks4 <= FOLD_MAXB && (int)g3.x <= device_cu_count(dev)) {
+                    fa_apply = make_apply_args(plan, L, u.params, u.m, u.v, w, ks, true, u.step, u.lr, u.beta1, u.beta2, u.adam_eps, 1.0, o.fold.losses3);
+                    fold.cnt = (unsigned*)(w + L.o_flags);
+                    fold.target = (unsigned)ks * fold_seq_next(w);
+                    fold.max_polls = env.fold_max_polls;
+                    o.fold.done = true;
+                }
+                int fin_block = -1;
+                const unsigned* fin_err = nullptr;
+                dim3 g3l = g3;
+                if (a.defer.on) {                                             // + one workgroup that turns the rows kernel's partial sums into the loss scalars
+                    fa_apply = a.defer.a;
+                    fin_block = (int)g3.x; fin_err = a.defer.err;
+                    g3l = dim3(g3.x + 1);
+                }
+                const int rc = with_policy(plan->precision, [&](auto pol) -> int {
+                    using P = decltype(pol);
+                    static bool attr_done[64] = {};      // per device: the attribute belongs to the device's copy of the code object
+                    if (!attr_done[dev]) { DVAE_HIP(hipFuncSetAttribute((const void*)wgrad4_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Wg4<P>::BYTES)); attr_done[dev] = true; }
+                    hipLaunchKernelGGL((wgrad4_kernel<P>), g3l, dim3(256), Wg4<P>::BYTES, s, bl, w4items, ks, plan->Bp, a.spl, slabs, plan->n_params, ri, use_raw,
+                                       a.ylo_skip ? a.ylo_epoch : nullptr, x3 ? a.launch_id : 0u /* the split-bf16 kernel alone reads them */, fa_apply, fold, fin_block, fin_err);
+                    return 0;
+                });
+                if (rc) return rc;
+                DVAE_LAUNCH_OK("wgrad4_kernel");
+            }
+        } else if (is_bf(plan->precision) && env.wgrad_form == 1) {
 #ifdef DVAE_DIAG
-    } else if ((bf || x3) && wk && strcmp(wk, "lds") == 0) {
-        ProfScope ps(s, rep == 0 ? 1 : 2);
-        const dim3 g3((unsigned)(L.nblocks * ks));
-        static bool attr_done[64][2] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64) dev = 0;
-        if (x3) {
-            if (!attr_done[dev][1]) { DVAE_HIP(hipFuncSetAttribute((const void*)wgrad_lds_kernel<PolX3>, hipFuncAttributeMaxDynamicSharedMemorySize, WgLds<PolX3>::BYTES)); attr_done[dev][1] = true; }
-            hipLaunchKernelGGL((wgrad_lds_kernel<PolX3>), g3, dim3(256), WgLds<PolX3>::BYTES, s, (const BlockDesc*)(w + L.o_blocks), L.nblocks, ks, plan->Bp, a.spl, kper, slabs, plan->n_params);
-        } else {
-            if (!attr_done[dev][0]) { DVAE_HIP(hipFuncSetAttribute((const void*)wgrad_lds_kernel<PolBF16>, hipFuncAttributeMaxDynamicSharedMemorySize, WgLds<PolBF16>::BYTES)); attr_done[dev][0] = true; }
-            hipLaunchKernelGGL((wgrad_lds_kernel<PolBF16>), g3, dim3(256), WgLds<PolBF16>::BYTES, s, (const BlockDesc*)(w + L.o_blocks), L.nblocks, ks, plan->Bp, a.spl, kper, slabs, plan->n_params);
-        }
-        DVAE_LAUNCH_OK("wgrad_lds_kernel");
+            ProfScope ps(s, rep == 0 ? 1 : 2);
+            const dim3 g3((unsigned)(L.nblocks * ks));
+            auto lds = [&](auto pol) -> int {      // (two policies: there is no fp32 form of this kernel)
+                using P = decltype(pol);
+                static bool attr_done[64] = {};
+                if (!attr_done[dev]) { DVAE_HIP(hipFuncSetAttribute((const void*)wgrad_lds_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, WgLds<P>::BYTES)); attr_done[dev] = true; }
+                hipLaunchKernelGGL((wgrad_lds_kernel<P>), g3, dim3(256), WgLds<P>::BYTES, s, (const BlockDesc*)(w + L.o_blocks), L.nblocks, ks, plan->Bp, a.spl, kper, slabs, plan->n_params);
+                return 0;
+            };
+            const int rc = x3 ? lds(PolX3{}) : lds(PolBF16{});
+            if (rc) return rc;
+            DVAE_LAUNCH_OK("wgrad_lds_kernel");
 #else
-    } else if ((bf || x3) && wk && strcmp(wk, "lds") == 0) {
-        set_error("train_grads: DVAE_WGRAD=lds exists in the diagnostic build only (build.py --diag)");
-        return DVAE_E_UNSUPPORTED;
+            set_error("train_grads: DVAE_WGRAD=lds exists in the diagnostic build only (build.py --diag)");
+            return DVAE_E_UNSUPPORTED;
 #endif
-    } else {
-    int GPW = 2;                                            // groups (waves) per workgroup
-    { const char* e = getenv("DVAE_GPW"); if (e) { GPW = atoi(e); if (GPW < 1 || GPW > 4) GPW = 2; } }   // diagnostic override
-    const dim3 g2((unsigned)(((L.ntiles + GPW - 1) / GPW) * ks));
-    {
-        ProfScope ps(s, rep == 0 ? 1 : 2);
-        if (x3) hipLaunchKernelGGL((wgrad_kernel<PolX3>), g2, dim3(64 * GPW), 0, s, (const GroupDesc*)(w + L.o_tiles), L.ntiles, ks, plan->Bp, a.spl, kper, slabs, plan->n_params);
-        else if (bf) hipLaunchKernelGGL((wgrad_kernel<PolBF16>), g2, dim3(64 * GPW), 0, s, (const GroupDesc*)(w + L.o_tiles), L.ntiles, ks, plan->Bp, a.spl, kper, slabs, plan->n_params);
-        else hipLaunchKernelGGL((wgrad_kernel<PolF32>), g2, dim3(64 * GPW), 0, s, (const GroupDesc*)(w + L.o_tiles), L.ntiles, ks, plan->Bp, a.spl, kper, slabs, plan->n_params);
-    }
-    DVAE_LAUNCH_OK("wgrad_kernel");
+        } else {
+            ProfScope ps(s, rep == 0 ? 1 : 2);
+            const dim3 g2((unsigned)(((L.ntiles + env.gpw - 1) / env.gpw) * ks));
+            with_policy(plan->precision, [&](auto pol) {
+                hipLaunchKernelGGL((wgrad_kernel<decltype(pol)>), g2, dim3(64 * env.gpw), 0, s, (const GroupDesc*)(w + L.o_tiles), L.ntiles, ks, plan->Bp, a.spl, kper, slabs, plan->n_params);
+            });
+            DVAE_LAUNCH_OK("wgrad_kernel");
+        }
     }
     if (reduce_slabs && ks > 1) {
         ProfScope ps(s, 2);
-        int64_t lo = 0, hi = plan->n_params;                              // a group's launch reduces its own part of the flat gradient
-        if (gsel == 0) lo = plan->tensor_offset[8];
-        if (gsel == 1) hi = plan->tensor_offset[8];
+        int64_t lo, hi;                                                   // a group's launch reduces its own part of the flat gradient
+        dvae_train_group_range(plan, o.group, &lo, &hi, nullptr);
         hipLaunchKernelGGL(slab_reduce_kernel, dim3(512), dim3(256), 0, s, slabs + lo, hi - lo, ks, plan->n_params);
         DVAE_LAUNCH_OK("slab_reduce_kernel");
     }
     return 0;
+}
+
+// The gradient pass behind every entry point below: rows kernel, then the weight-gradient launches.  A pending deferred update is applied
+// first -- unless this call IS the deferred step, whose rows kernel applies it in its opening.
+static int run_grads(const dvae_train_plan_t* plan, const float* params, void* ws, const float* x, int ldx, const float* y, int ldy,
+                     const float* eps_noise, float elbo_eps, int reduce_slabs, void* stream, GradsOptions& o) {
+    DVAE_CHECK_ARG(plan && params && ws && x && ldx >= XD, "train_grads: bad argument");
+    DVAE_CHECK_ARG(plan->y_dim == 0 || (y != nullptr && ldy >= plan->y_dim), "train_grads: y missing or ldy < y_dim");
+    if (!o.defer.on) { const int frc = dvae_train_flush(plan, ws, stream); if (frc) return frc; }
+    const StepEnv env;
+    Layout L;
+    make_layout(*plan, L);
+    hipStream_t s = (hipStream_t)stream;
+    RowsArgs a;
+    { const int rc = fill_rows_args(plan, L, o, env, params, (char*)ws, x, ldx, y, ldy, eps_noise, elbo_eps, a); if (rc) return rc; }
+    // the weight-gradient launch is the workgroup k-split kernel -- but for one 128-frame slice: there the 2 x 2 kernel's short epilogue wins (11.2 vs 12.8 us)
+    const bool wg4 = env.wgrad_form == 4 && (plan->Bp > 128 || a.stash_inputs != 3 /* raw inputs */ || env.wgrad_set);
+    // label lo plane on demand: 8-wave kernel + the workgroup k-split weight-gradient kernel, split-bf16 operands, labels from the stash
+    a.ylo_skip = (plan->precision == DVAE_PREC_BF16X3 && plan->y_dim > 0 && plan->rows_kernel >= 2 && rows2_supported(plan->precision, plan->model) && wg4 &&
+                  (a.stash_inputs & 2) && !env.ylo_always) ? 1 : 0;
+    DVAE_CHECK_ARG(o.group < 0 || (w4_grouped(*plan) && o.mode == 0 && !o.rows_only), "train_grads_group: the plan was not made for two weight-gradient launches (DVAE_EXCHANGE_GROUPS=2 when the plan is made)");
+    if (o.group != 1) {
+        ProfScope ps(s, 0);
+        const int rc = launch_rows_kernel(plan, a, s);
+        if (rc) return rc;
+    }
+    if (o.rows_only || a.mode == 1) return 0;
+    return launch_wgrad_pass(plan, L, o, env, a, wg4, (char*)ws, reduce_slabs, s);
+}
+
+extern "C" int dvae_train_grads(const dvae_train_plan_t* plan, const float* params, void* ws, const float* x, int ldx,
+                                const float* y, int ldy, const float* eps_noise, float elbo_eps, int reduce_slabs, void* stream) {
+    GradsOptions o;
+    return run_grads(plan, params, ws, x, ldx, y, ldy, eps_noise, elbo_eps, reduce_slabs, stream, o);
 }
 
 // The step's gradient pass in two calls, for a plan made under DVAE_EXCHANGE_GROUPS=2: group 0 = the rows kernel + the weight-gradient launch of
@@ -2655,10 +2675,9 @@ extern "C" int dvae_train_grads_group(const dvae_train_plan_t* plan, const float
                                       const float* eps_noise, float elbo_eps, int group, int reduce_slabs, void* stream) {
     DVAE_CHECK_ARG(plan && (group == 0 || group == 1), "train_grads_group: group must be 0 or 1");
     DVAE_CHECK_ARG(w4_grouped(*plan), "train_grads_group: the plan was not made for two weight-gradient launches (DVAE_EXCHANGE_GROUPS=2 when the plan is made)");
-    g_w4_group = group;
-    const int rc = dvae_train_grads(plan, params, ws, x, ldx, y, ldy, eps_noise, elbo_eps, reduce_slabs, stream);
-    g_w4_group = -1;
-    return rc;
+    GradsOptions o;
+    o.group = group;
+    return run_grads(plan, params, ws, x, ldx, y, ldy, eps_noise, elbo_eps, reduce_slabs, stream, o);
 }
 
 // float range [lo, hi) of a group's part of the flat gradient (group < 0: everything); *ngroups = 2 for a plan made for two launches, else 1
@@ -2669,12 +2688,6 @@ extern "C" int dvae_train_group_range(const dvae_train_plan_t* plan, int group, 
     if (group == 1) *hi = plan->tensor_offset[8];
     if (ngroups) *ngroups = w4_grouped(*plan) ? 2 : 1;
     return 0;
-}
-
-static int used_slabs(const dvae_train_plan_t* plan) {
-    if (w4_classed(*plan)) return plan->ksplit;                          // class-sliced schedule: the largest slice count of any block
-    const int64_t kper = kper_of(plan);
-    return (int)((plan->Bp + kper - 1) / kper);
 }
 
 extern "C" int dvae_train_apply(const dvae_train_plan_t* plan, float* params, float* m, float* v, void* ws, int n_slabs,
@@ -2695,7 +2708,6 @@ extern "C" int dvae_train_step(const dvae_train_plan_t* plan, float* params, flo
                                const float* x, int ldx, const float* y, int ldy, const float* eps_noise, float elbo_eps,
                                int step, double lr, double beta1, double beta2, double adam_eps, float* losses3, void* stream) {
     DVAE_CHECK_ARG(plan && params && m && v && ws && step >= 1, "train_step: bad argument");
-    g_rng_step_override = step;
     // DVAE_FOLD_APPLY=1: the optimizer step in the tail of the weight-gradient launch (two launches per step; results bit-identical,
     // tested).  Opt-in, because it is SLOWER on the MI355X (M2 y513, 8192 frames, bf16x3, same box, alternating): the weight-gradient
     // kernel goes 28.7 -> 47.1 us while the separate optimizer launch it replaces costs 9.5 us gross.  Ablation of the 18.4 us tail
@@ -2704,17 +2716,13 @@ extern "C" int dvae_train_step(const dvae_train_plan_t* plan, float* params, flo
     // both phases are latency-bound, whereas apply_kernel does the same work at full occupancy in ~6 us behind a ~3 us launch gap.
     // (First attempt with release / acquire fences instead of write-through stores + coherent loads: 75 us -- every fence writes back
     // or invalidates the XCD's whole L2 under the workgroups that are still multiplying.)
-    const char* fe = getenv("DVAE_FOLD_APPLY");                       // read per call (tests flip it)
-    const bool fold_on = kDiagBuild && fe && atoi(fe) != 0;      // (the folded tail exists in -DDVAE_DIAG builds only)
-    g_fold = FoldRequest();
-    g_fold.want = fold_on; g_fold.params = params; g_fold.m = m; g_fold.v = v; g_fold.step = step; g_fold.lr = lr; g_fold.beta1 = beta1;
-    g_fold.beta2 = beta2; g_fold.adam_eps = adam_eps; g_fold.losses3 = losses3;
-    int rc = dvae_train_grads(plan, params, ws, x, ldx, y, ldy, eps_noise, elbo_eps, 0, stream);
-    const bool folded = g_fold.done;
-    g_fold = FoldRequest();
-    g_rng_step_override = -1;
+    const bool fold_on = kDiagBuild && env_int("DVAE_FOLD_APPLY", 0) != 0;      // read per call (tests flip it); the folded tail exists in -DDVAE_DIAG builds only
+    GradsOptions o;
+    o.rng_step = step;
+    o.fold = FoldRequest{fold_on, false, PendingUpdate{params, m, v, step, lr, beta1, beta2, adam_eps, 0 /* the launch's own slabs */}, losses3};
+    const int rc = run_grads(plan, params, ws, x, ldx, y, ldy, eps_noise, elbo_eps, 0, stream, o);
     if (rc) return rc;
-    if (folded) return 0;
+    if (o.fold.done) return 0;
     return dvae_train_apply(plan, params, m, v, ws, 0, step, lr, beta1, beta2, adam_eps, 1.0, losses3, stream);
 }
 
@@ -2727,13 +2735,10 @@ extern "C" int dvae_train_step_deferred(const dvae_train_plan_t* plan, float* pa
     if (!dvae_train_can_defer(plan, ws))
         return dvae_train_step(plan, params, m, v, ws, x, ldx, y, ldy, eps_noise, elbo_eps, step, lr, beta1, beta2, adam_eps, losses3, stream);   // flushes first
     DeferState st = defer_state_get(ws);
-    g_defer_req = DeferRequest();
-    g_defer_req.on = true; g_defer_req.have = st.pending; g_defer_req.u = st.u; g_defer_req.losses3 = losses3;
-    g_defer_req.seq_arrive = st.seq_arrive + (st.pending ? 1u : 0u); g_defer_req.seq_done = st.seq_done + 1u;
-    g_rng_step_override = step;
-    const int rc = dvae_train_grads(plan, params, ws, x, ldx, y, ldy, eps_noise, elbo_eps, 0, stream);
-    g_defer_req = DeferRequest();
-    g_rng_step_override = -1;
+    GradsOptions o;
+    o.rng_step = step;
+    o.defer = DeferRequest{true, st.pending, st.u, st.seq_arrive + (st.pending ? 1u : 0u), st.seq_done + 1u, losses3};
+    const int rc = run_grads(plan, params, ws, x, ldx, y, ldy, eps_noise, elbo_eps, 0, stream, o);
     if (rc) return rc;
     st.seq_arrive += st.pending ? 1u : 0u; st.seq_done += 1u;
     st.pending = true;
@@ -2750,11 +2755,9 @@ extern "C" int dvae_module_forward(const dvae_train_plan_t* plan, const float* p
     DVAE_CHECK_ARG(plan->rows_kernel == 2 && plan->row_index == 0, "module_forward: needs the 8-wave rows kernel and no gather table");
     { const int frc = dvae_train_flush(plan, ws, stream); if (frc) return frc; }
     if (repack) { int rc = dvae_train_repack(plan, params, ws, stream); if (rc) return rc; }
-    g_mode = ModeArgs();
-    g_mode.mode = 1; g_mode.out_r = out_r; g_mode.ld_r = ld_r; g_mode.out_mu = out_mu; g_mode.out_lv = out_lv; g_mode.out_z = out_z;
-    const int rc = dvae_train_grads(plan, params, ws, x, ldx, y, ldy, eps_noise, 0.f, 0, stream);
-    g_mode = ModeArgs();
-    return rc;
+    GradsOptions o;
+    o.mode = 1; o.out_r = out_r; o.ld_r = ld_r; o.out_mu = out_mu; o.out_lv = out_lv; o.out_z = out_z;
+    return run_grads(plan, params, ws, x, ldx, y, ldy, eps_noise, 0.f, 0, stream, o);
 }
 
 extern "C" int dvae_module_backward(const dvae_train_plan_t* plan, const float* params, void* ws, const float* x, int ldx,
@@ -2764,10 +2767,9 @@ extern "C" int dvae_module_backward(const dvae_train_plan_t* plan, const float* 
     DVAE_CHECK_ARG(plan && params && ws && x && eps_noise && grad_flat, "module_backward: bad argument");
     DVAE_CHECK_ARG(plan->rows_kernel == 2 && plan->row_index == 0, "module_backward: needs the 8-wave rows kernel and no gather table");
     DVAE_CHECK_ARG(g_r == nullptr || ld_gr >= XD, "module_backward: ld_gr < 513");
-    g_mode = ModeArgs();
-    g_mode.mode = 2; g_mode.g_r = g_r; g_mode.ld_gr = ld_gr; g_mode.g_mu = g_mu; g_mode.g_lv = g_lv; g_mode.g_z = g_z;
-    const int rc = dvae_train_grads(plan, params, ws, x, ldx, y, ldy, eps_noise, 0.f, 0, stream);
-    g_mode = ModeArgs();
+    GradsOptions o;
+    o.mode = 2; o.g_r = g_r; o.ld_gr = ld_gr; o.g_mu = g_mu; o.g_lv = g_lv; o.g_z = g_z;
+    const int rc = run_grads(plan, params, ws, x, ldx, y, ldy, eps_noise, 0.f, 0, stream, o);
     if (rc) return rc;
     Layout L;
     make_layout(*plan, L);
@@ -2789,12 +2791,9 @@ extern "C" int dvae_train_eval(const dvae_train_plan_t* plan, const float* param
     // forward + loss sums only: the rows kernel also writes the stash, which is simply not consumed
     Layout L;
     make_layout(*plan, L);
-    const int saved = 0;
-    (void)saved;
-    // run the rows kernel through dvae_train_grads' argument setup, but stop before the wgrad launch
-    g_eval_only = true;
-    int rc = dvae_train_grads(plan, params, ws, x, ldx, y, ldy, eps_noise, elbo_eps, 0, stream);
-    g_eval_only = false;
+    GradsOptions o;
+    o.rows_only = true;
+    const int rc = run_grads(plan, params, ws, x, ldx, y, ldy, eps_noise, elbo_eps, 0, stream, o);
     if (rc) return rc;
     ApplyArgs a;
     memset(&a, 0, sizeof(a));
