@@ -389,3 +389,12 @@ class McemBatch:
         from . import metrics as M
         s_hat, _ = self.enhance(max_len)
         return M.si_sdr_batch(s_hat, s, trim) if n is None else M.energy_ratios_batch(s_hat, s, n, trim)
+
+    def estoi(self, s, max_len=None, trim=0, extended=True, fs=16000):
+        """enhance() and the intelligibility of its speech estimate against the clean speech s (run_metrics.py:117-138:
+        stoi(s_t, s_hat_t, fs, extended=True)), the waveform never leaving the device: s a WaveBatch or a list of 1-D arrays / tensors
+        as long as the estimates (max_len as for enhance()); trim: samples dropped at both ends of every utterance; extended=False:
+        STOI.  -> float64 CUDA tensor [U] (metrics.stoi_batch)."""
+        from . import metrics as M
+        s_hat, _ = self.enhance(max_len)
+        return M.stoi_batch(s, s_hat, fs, extended, trim)

@@ -5,7 +5,7 @@ device between the batch STFT and the waveforms.
 
     python examples/enhance_mcem.py --wav a.wav b.wav --checkpoint models/M2_epoch_118_vloss_407.90.pt --out enhanced/
     python examples/enhance_mcem.py --synthetic 8                       # no data at hand: modulated-noise "speech" + noise
-    python examples/enhance_mcem.py --synthetic 8 --score               # and SI-SDR of mixture and estimate, scored on the device
+    python examples/enhance_mcem.py --synthetic 8 --score               # and SI-SDR and ESTOI of mixture and estimate, scored on the device
 
 The labels y fed to the M2 decoder are the time-domain VAD of the mixture (packages/processing/target.py); the
 reference's evaluate script takes them from a video classifier or from the clean signal (oracle), neither of which
@@ -28,6 +28,7 @@ from packages.processing.target import clean_speech_VAD
 McemBatch = importlib.import_module("disentangled-vae_amd.mcem").McemBatch
 stft_batch = importlib.import_module("disentangled-vae_amd.stft").stft_batch
 si_sdr_batch = importlib.import_module("disentangled-vae_amd.metrics").si_sdr_batch
+estoi_batch = importlib.import_module("disentangled-vae_amd.metrics").estoi_batch
 STFT = dict(fs=16000, wlen_sec=64e-3, win="hann", hop_percent=0.25, center=False)      # evaluate_ntcd_M2.py:37-45
 
 
@@ -49,7 +50,7 @@ def main():
     ap.add_argument("--niter", type=int, default=100)
     ap.add_argument("--precision", choices=["fp32", "bf16"], default="fp32")
     ap.add_argument("--out", default="enhanced")
-    ap.add_argument("--score", action="store_true", help="with --synthetic (whose speech is known): SI-SDR of mixture and estimate per utterance")
+    ap.add_argument("--score", action="store_true", help="with --synthetic (whose speech is known): SI-SDR and ESTOI of mixture and estimate per utterance")
     ap.add_argument("--trim", type=int, default=800, help="samples cut at both ends before scoring (run_metrics.py:117-121: 0.05 s)")
     a = ap.parse_args()
     if a.score and (a.wav or not a.synthetic):
@@ -95,10 +96,13 @@ def main():
         # scored on the device (si_sdr_leroux of every utterance in three launches); only the two [U] results come back
         sdr_est = mb.score(clean, max_len=[len(w) for w in waves], trim=a.trim).cpu().numpy()
         sdr_mix = si_sdr_batch(waves, clean, trim=a.trim).cpu().numpy()
-        print(f"{'utterance':<16}{'SI-SDR mixture':>16}{'SI-SDR estimate':>17}   (dB)")
-        for name, m, e in zip(names, sdr_mix, sdr_est):
-            print(f"{name:<16}{m:>16.2f}{e:>17.2f}")
-        print(f"{'mean':<16}{sdr_mix.mean():>16.2f}{sdr_est.mean():>17.2f}")
+        # and the intelligibility (ESTOI as include/dvae.h writes it out, six launches): the clean speech first, as pystoi takes it
+        ei_est = mb.estoi(clean, max_len=[len(w) for w in waves], trim=a.trim).cpu().numpy()
+        ei_mix = estoi_batch(clean, waves, STFT["fs"], trim=a.trim).cpu().numpy()
+        print(f"{'utterance':<16}{'SI-SDR mixture':>16}{'SI-SDR estimate':>17}   (dB){'ESTOI mixture':>16}{'ESTOI estimate':>16}")
+        for name, m, e, im, ie in zip(names, sdr_mix, sdr_est, ei_mix, ei_est):
+            print(f"{name:<16}{m:>16.2f}{e:>17.2f}{'':>7}{im:>16.3f}{ie:>16.3f}")
+        print(f"{'mean':<16}{sdr_mix.mean():>16.2f}{sdr_est.mean():>17.2f}{'':>7}{ei_mix.mean():>16.3f}{ei_est.mean():>16.3f}")
 
 
 if __name__ == "__main__":

@@ -303,6 +303,45 @@ int dvae_si_ratios_batch(const void* s_hat, int64_t n_s_hat, int s_hat_f64, cons
                          int64_t n_n, int n_f64, int U, const int64_t* tables, int64_t n_items, double* ratios, double* sums,
                          void* workspace, void* stream);
 
+/* ---- intelligibility: STOI (Taal et al. 2011) and ESTOI (Jensen & Taal 2016) ----
+ * dvae_estoi_batch: the score d[u] of U utterances (x clean, y processed, equal lengths) in six
+ *   launches on `stream` whatever U is, no host synchronisation, no atomics, double arithmetic throughout.  The contract is the
+ *   algorithm below, laid out the way the pystoi package does it and restated in numpy by tests/estoi_ref.py; the package itself is
+ *   not available to this repository, so parity with it is unpinned.  FS = 10000, frames of 256 at hop 128, w = hanning(258)[1:-1],
+ *   EPS = 2^-52.
+ *   1 resample (taps != NULL): output k of ceil(len p / q) = p sum_j taps[j] xu[k q + j - L], xu = the signal zero-stuffed by p and
+ *     zero outside it, taps [2 L + 1] built by the host (scipy.signal.resample_poly(x, p, q, window=taps)); p / q = FS / fs reduced.
+ *     taps == NULL (p = q = 1, L = 0): the samples as they are.
+ *   2 silent frames: frames of x and y at i = 0, 128, ... with i + 256 <= n; e_j = 20 log10(|w x_j| + EPS); frame j of BOTH signals is
+ *     kept iff (max e - 40) - e_j < 0; the kept windowed frames are overlap-added at hop 128 in kept order.
+ *   3 spectra: frames of the result at i = 0, 128, ... with i + 256 < n (strict), windowed by w again, 512-point real FFT, power.
+ *   4 bands: tob[m][b] = sqrt(sum of the power of bins [bands[b], bands[b + 1])), b < DVAE_ESTOI_BANDS (bands: 16 device int64,
+ *     0 <= bands[b] <= bands[b + 1] <= 256).
+ *   5 segments m = 30 ... M of the 15 x 30 blocks of frames m - 30 ... m - 1; fewer than 30 frames: d = 1e-5.
+ *     extended (ESTOI): rows minus their mean, divided by (norm + EPS), then the same by column; d = mean over segments of sum(xn yn) / 30.
+ *     otherwise (STOI): alpha = |x_row| / (|y_row| + EPS), y' = min(alpha y, x (1 + 10^(15 / 20))), rows of x and y' minus their mean and
+ *     divided by (norm + EPS); d = mean over segments of sum(y'n xn) / 15.
+ *   x / y are packed device buffers of n_x / n_y elements, float32 or float64 by their flags.  tables (device int64) = [items_res (U + 1)
+ *   | items_frame (U + 1) | items_seg (U + 1) | x0 (U) | y0 (U) | len (U) | r0 (U) | f0 (U)]: utterance u is x[x0[u] : x0[u] + len[u]] and
+ *   y[y0[u] : ...]; with n10 = ceil(len p / q) and J = frames of rule 2 in n10 samples, its resampled signals live at r0[u] of the n_res
+ *   workspace samples and its per-frame data at f0[u] of the n_frames workspace rows (r0, f0: prefixes of n10 and J), and it has
+ *   max(1, ceil(n10 / (DVAE_ESTOI_RES_RUN p))), max(1, ceil(J / DVAE_ESTOI_FRAME_RUN)) and max(1, ceil(max(J - 30, 0) /
+ *   DVAE_ESTOI_SEG_RUN)) work items in the three prefixes (whose last entries are n_res_items, n_frame_items, n_seg_items).  The runs
+ *   are fixed and every reduction has a fixed order, so an utterance's score does not depend on what else is in the batch and repeats
+ *   bit for bit.  The kernels check every table entry against the scalar extents before touching memory: a bad entry leaves NaN in
+ *   d[u] (and -1 in info[u]).  d [U] float64; info [U, 3] int64 or NULL: resampled length, kept frames, segments; tob [2, n_frames,
+ *   DVAE_ESTOI_BANDS] float64 or NULL: a debug output, the bands of x then y, utterance u's M rows from row f0[u] (the rest of its J
+ *   rows untouched).  workspace: dvae_estoi_workspace_bytes(n_res, n_frames, n_seg_items, U). */
+#define DVAE_ESTOI_BANDS 15
+#define DVAE_ESTOI_RES_RUN 256
+#define DVAE_ESTOI_FRAME_RUN 16
+#define DVAE_ESTOI_SEG_RUN 8
+size_t dvae_estoi_workspace_bytes(int64_t n_res, int64_t n_frames, int64_t n_seg_items, int U);
+int dvae_estoi_batch(const void* x, int64_t n_x, int x_f64, const void* y, int64_t n_y, int y_f64, int U, const int64_t* tables,
+                     int64_t n_res_items, int64_t n_frame_items, int64_t n_seg_items, int64_t n_res, int64_t n_frames,
+                     const double* taps, int p, int q, int L, const double* window, const int64_t* bands, int extended, double* d,
+                     int64_t* info, double* tob, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
