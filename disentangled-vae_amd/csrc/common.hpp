@@ -85,6 +85,14 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// numpy's max: a NaN wins (max_nan(a, b) with a the running maximum)
+__device__ __forceinline__ double max_nan(double a, double b) { return (b > a || b != b) ? b : a; }
+__device__ __forceinline__ double wave_max_nan(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max_nan(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // Ragged batches: `pref` [U + 1] is the prefix of the per-utterance work-item counts (pref[0] = 0); item i belongs to the utterance u

@@ -135,14 +135,6 @@ extern "C" int dvae_ibm_labels(const void* S, int64_t rows, int64_t cols, float 
 
 namespace dvae {
 
-// numpy's max: a NaN wins
-__device__ __forceinline__ double max_nan(double a, double b) { return (b > a || b != b) ? b : a; }
-
-__device__ __forceinline__ double wave_max_nan(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max_nan(v, __shfl_xor(v, o, 64));
-    return v;
-}
 __device__ __forceinline__ double wave_min(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));

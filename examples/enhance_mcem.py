@@ -6,6 +6,8 @@ device between the batch STFT and the waveforms.
     python examples/enhance_mcem.py --wav a.wav b.wav --checkpoint models/M2_epoch_118_vloss_407.90.pt --out enhanced/
     python examples/enhance_mcem.py --synthetic 8                       # no data at hand: modulated-noise "speech" + noise
     python examples/enhance_mcem.py --synthetic 8 --score               # and SI-SDR and ESTOI of mixture and estimate, scored on the device
+    python examples/enhance_mcem.py --synthetic 8 --snr -5 0 5 --score  # every utterance mixed on the device at each SNR (create_test_set.py's
+                                                                        # mixing: disentangled-vae_amd/mix.py); --score adds SI-SIR and SI-SAR
 
 The labels y fed to the M2 decoder are the time-domain VAD of the mixture (packages/processing/target.py); the
 reference's evaluate script takes them from a video classifier or from the clean signal (oracle), neither of which
@@ -29,6 +31,7 @@ McemBatch = importlib.import_module("disentangled-vae_amd.mcem").McemBatch
 stft_batch = importlib.import_module("disentangled-vae_amd.stft").stft_batch
 si_sdr_batch = importlib.import_module("disentangled-vae_amd.metrics").si_sdr_batch
 estoi_batch = importlib.import_module("disentangled-vae_amd.metrics").estoi_batch
+mix_at_snr_batch = importlib.import_module("disentangled-vae_amd.mix").mix_at_snr_batch
 STFT = dict(fs=16000, wlen_sec=64e-3, win="hann", hop_percent=0.25, center=False)      # evaluate_ntcd_M2.py:37-45
 
 
@@ -42,6 +45,19 @@ def synthetic_mixture(seconds, seed):
     return s + noise, s, noise
 
 
+def synthetic_noise_banks(seconds, seed, count=2):
+    """`count` long noise recordings: white noise through one-pole low-pass filters of different corners."""
+    rng = np.random.default_rng(seed)
+    banks = []
+    for b in range(count):
+        w = rng.standard_normal(int(16000 * seconds))
+        a = 0.5 + 0.4 * b / max(count - 1, 1)
+        for i in range(1, 4):
+            w[i:] += a ** i * w[:-i]                      # a short FIR stand-in for the filter: no sample-by-sample loop
+        banks.append(0.1 * w)
+    return banks
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--wav", nargs="*", default=[])
@@ -51,10 +67,14 @@ def main():
     ap.add_argument("--precision", choices=["fp32", "bf16"], default="fp32")
     ap.add_argument("--out", default="enhanced")
     ap.add_argument("--score", action="store_true", help="with --synthetic (whose speech is known): SI-SDR and ESTOI of mixture and estimate per utterance")
+    ap.add_argument("--snr", type=float, nargs="+", default=None, help="with --synthetic: mix every utterance with synthetic noise at each of "
+                    "these SNRs (dB) on the device instead of adding a fixed 0.2 * randn on the host")
     ap.add_argument("--trim", type=int, default=800, help="samples cut at both ends before scoring (run_metrics.py:117-121: 0.05 s)")
     a = ap.parse_args()
     if a.score and (a.wav or not a.synthetic):
         ap.error("--score needs the clean speech, which only --synthetic mixtures come with")
+    if a.snr is not None and (a.wav or not a.synthetic):
+        ap.error("--snr mixes the --synthetic utterances")
     names, waves, clean = [], [], []
     for p in a.wav:
         fs, w = wavfile.read(p)
@@ -74,8 +94,24 @@ def main():
         p.requires_grad = False
 
     t0 = time.perf_counter()
-    # every mixture's STFT in one launch, kept on the device: (513, N_u) complex64 per utterance, frame-major and packed
-    X = stft_batch(waves, pad_mode="reflect", pad_at_end=True, **STFT)
+    mix = None
+    if a.snr is not None:
+        # every utterance at every SNR in one call, the noise segments drawn from two banks: speech, noise (at the mixture's scale) and
+        # mixture stay on the device, the mixtures laid out for the batch STFT with their end pad written by the kernel
+        mixer = importlib.import_module("disentangled-vae_amd.mix")
+        banks = synthetic_noise_banks(8.0, 1000)
+        speech = [clean[u] for u in range(len(clean)) for _ in a.snr]
+        names = [f"{names[u]}_snr{snr:+g}" for u in range(len(clean)) for snr in a.snr]
+        noise_index = [u % len(banks) for u in range(len(clean)) for _ in a.snr]
+        snr_db = [snr for _ in clean for snr in a.snr]
+        starts = mixer.draw_noise_starts(np.random.default_rng(0), [len(b) for b in banks], noise_index, [len(s) for s in speech])
+        mix = mix_at_snr_batch(speech, banks, noise_index, starts, snr_db, stft_layout=True)
+        X = mix.spec()
+        waves = mix.mixture.numpy()                       # one download: the VAD labels below are made on the host
+        clean = mix.speech
+    else:
+        # every mixture's STFT in one launch, kept on the device: (513, N_u) complex64 per utterance, frame-major and packed
+        X = stft_batch(waves, pad_mode="reflect", pad_at_end=True, **STFT)
     Y = [clean_speech_VAD(w, fs=16000, wlen_sec=64e-3, hop_percent=0.25, center=False, pad_mode="reflect", pad_at_end=True,
                           vad_threshold=1.70) for w in waves]                                              # (1, N_u)
     mb = McemBatch(vae, niter=a.niter, nsamples_E_step=10, burnin_E_step=30, nsamples_WF=25, burnin_WF=75, var_RW=0.01,
@@ -95,14 +131,21 @@ def main():
     if a.score:
         # scored on the device (si_sdr_leroux of every utterance in three launches); only the two [U] results come back
         sdr_est = mb.score(clean, max_len=[len(w) for w in waves], trim=a.trim).cpu().numpy()
-        sdr_mix = si_sdr_batch(waves, clean, trim=a.trim).cpu().numpy()
+        sdr_mix = si_sdr_batch(waves if mix is None else mix.mixture, clean, trim=a.trim).cpu().numpy()
         # and the intelligibility (ESTOI as include/dvae.h writes it out, six launches): the clean speech first, as pystoi takes it
         ei_est = mb.estoi(clean, max_len=[len(w) for w in waves], trim=a.trim).cpu().numpy()
-        ei_mix = estoi_batch(clean, waves, STFT["fs"], trim=a.trim).cpu().numpy()
+        ei_mix = estoi_batch(clean, waves if mix is None else mix.mixture, STFT["fs"], trim=a.trim).cpu().numpy()
         print(f"{'utterance':<16}{'SI-SDR mixture':>16}{'SI-SDR estimate':>17}   (dB){'ESTOI mixture':>16}{'ESTOI estimate':>16}")
         for name, m, e, im, ie in zip(names, sdr_mix, sdr_est, ei_mix, ei_est):
             print(f"{name:<16}{m:>16.2f}{e:>17.2f}{'':>7}{im:>16.3f}{ie:>16.3f}")
         print(f"{'mean':<16}{sdr_mix.mean():>16.2f}{sdr_est.mean():>17.2f}{'':>7}{ei_mix.mean():>16.3f}{ei_est.mean():>16.3f}")
+        if mix is not None:
+            # the mixer's noise is at the mixture's scale, which is what SI-SIR and SI-SAR need (energy_ratios, packages/metrics.py:39-60)
+            ratios = mb.score(mix.speech, mix.noise, max_len=[len(w) for w in waves], trim=a.trim).cpu().numpy()
+            achieved = mix.stats[:, 5].cpu().numpy()
+            print(f"{'utterance':<24}{'SNR (dB)':>10}{'SI-SDR':>10}{'SI-SIR':>10}{'SI-SAR':>10}")
+            for name, snr, r in zip(names, achieved, ratios):
+                print(f"{name:<24}{snr:>10.2f}{r[0]:>10.2f}{r[1]:>10.2f}{r[2]:>10.2f}")
 
 
 if __name__ == "__main__":

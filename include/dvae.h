@@ -303,6 +303,37 @@ int dvae_si_ratios_batch(const void* s_hat, int64_t n_s_hat, int s_hat_f64, cons
                          int64_t n_n, int n_f64, int U, const int64_t* tables, int64_t n_items, double* ratios, double* sums,
                          void* workspace, void* stream);
 
+/* ---- noisy mixtures at a target SNR (scripts/create_test_set.py:95-115: process_save_utt) ----
+ * dvae_mix_snr_batch: speech, noise and mixture of U utterances in at most five launches on `stream` whatever U is, no host
+ *   synchronisation, no atomics.  speech and noise are packed device buffers of n_speech / n_noise elements, float32 or float64 by
+ *   their flags; all arithmetic is in double, every operation rounded on its own in the reference's order.  Per utterance, over its
+ *   len samples:
+ *   1 p = max |speech|, s = speech / p (IEEE division per sample); normalise_speech == 0: s = speech, and p is reported as 1.
+ *   2 Ps = sum s^2, Pn = sum noise^2 (squares rounded, then added).
+ *   3 k = (Ps snr_factor[u]) / Pn, g = sqrt(k), v = noise g.  snr_factor (device, [U]) is np.power(10, -snr_dB / 10) from the host:
+ *     the reference's own bits, no pow in the kernel.
+ *   4 norm = max(|s|, |v|, |s + v|).
+ *   5 out_speech = s / norm, out_noise = v / norm, out_mix = (s + v) / norm: the rounded sum divided, not the sum of the quotients.
+ *   6 stats[u] = {p, Ps, Pn, k, norm, 10 log10(sum out_speech^2 / sum out_noise^2)} (the achieved SNR, from the double quotients
+ *     before any rounding to float32); stats [U, 6] may be NULL.
+ *   The three outputs are three buffers of n_out elements each, float64, or float32 when out_f64 == 0 (one more rounding of the
+ *   double result).  Maxima propagate NaN as numpy's; no clamping, no epsilon: an all-zero noise segment gives NaN outputs (0 inf),
+ *   an all-zero speech under normalise_speech NaN.
+ *   tables (device int64) = [items (U + 1) | speech0 (U) | noise0 (U) | out0 (U) | len (U) | out_extent (U)]: utterance u reads
+ *   speech[speech0[u] : speech0[u] + len[u]] and noise[noise0[u] : ...] and writes [out0[u], out0[u] + out_extent[u]) of all three
+ *   outputs: len[u] samples, then zeros (out_extent[u] >= len[u]: room for the end pad of a later STFT).  Input ranges may overlap or
+ *   repeat; output ranges may not overlap, and no output may alias an input.  Output samples outside every range are not touched.  A
+ *   work item is one utterance and a run of at most DVAE_MIX_CHUNK of its samples, items[u + 1] - items[u] = ceil(len[u] /
+ *   DVAE_MIX_CHUNK), items[U] = n_items.  The chunk is fixed, the sums are added in item order and a maximum is exact in any order, so
+ *   an utterance's results do not depend on what else is in the batch and repeat bit for bit.  The kernels check every table entry
+ *   against n_speech, n_noise and n_out before touching memory: a bad entry leaves NaN in that utterance's stats row and writes
+ *   nothing else for it.  workspace: dvae_mix_snr_workspace_bytes(n_items, U). */
+#define DVAE_MIX_CHUNK 4096
+size_t dvae_mix_snr_workspace_bytes(int64_t n_items, int U);
+int dvae_mix_snr_batch(const void* speech, int64_t n_speech, int speech_f64, const void* noise, int64_t n_noise, int noise_f64, int U,
+                       const int64_t* tables, int64_t n_items, const double* snr_factor, int normalise_speech, void* out_speech,
+                       void* out_noise, void* out_mix, int64_t n_out, int out_f64, double* stats, void* workspace, void* stream);
+
 /* ---- intelligibility: STOI (Taal et al. 2011) and ESTOI (Jensen & Taal 2016) ----
  * dvae_estoi_batch: the score d[u] of U utterances (x clean, y processed, equal lengths) in six
  *   launches on `stream` whatever U is, no host synchronisation, no atomics, double arithmetic throughout.  The contract is the
