@@ -95,23 +95,4 @@ __device__ __forceinline__ double wave_max_nan(double v) {
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// Ragged batches: `pref` [U + 1] is the prefix of the per-utterance work-item counts (pref[0] = 0); item i belongs to the utterance u
-// with pref[u] <= i < pref[u + 1] (a binary search with wave-uniform addresses: scalar loads).  u = -1 past the last item.
-struct BatchItem { int u; int64_t local; };
-__device__ __forceinline__ int64_t uni64(int64_t v) {          // a wave-uniform 64-bit value in scalar registers
-    const uint64_t w = (uint64_t)v;
-    return (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(w >> 32)) << 32) |
-                     (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)w));
-}
-__device__ __forceinline__ BatchItem batch_item(const int64_t* __restrict__ pref, int U, int64_t item) {
-    if (U < 1 || item < 0 || item >= uni64(pref[U])) return BatchItem{-1, 0};
-    int lo = 0, hi = U;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (uni64(pref[mid]) <= item) lo = mid; else hi = mid;
-    }
-    const int64_t local = item - uni64(pref[lo]);
-    return local < 0 ? BatchItem{-1, 0} : BatchItem{lo, local};
-}
-
 }  // namespace dvae

@@ -24,7 +24,7 @@
 // Every table entry is rechecked against the scalar extents before memory is touched (es_utterance, by every kernel): a bad entry
 // drops that utterance's work and the finish writes NaN (info -1).
 #include <math.h>
-#include "common.hpp"
+#include "ragged.hpp"
 
 namespace dvae {
 
@@ -91,17 +91,13 @@ __device__ __forceinline__ bool es_utterance(const EsIn& in, int u, EsUtt& r) {
 
 // the wave's item of class c -> utterance and local index (u = -1: nothing to do)
 __device__ __forceinline__ bool es_item(const EsIn& in, int c, EsUtt& r, int& u, int64_t& local, int64_t& item) {
-    item = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    item = wave_item();
     if (item >= in.n_items[c]) return false;
     const BatchItem it = batch_item(in.tab + c * (in.U + 1), in.U, item);
     if (it.u < 0) return false;
     u = it.u;
     local = it.local;
     return es_utterance(in, it.u, r);
-}
-
-__device__ __forceinline__ double es_load(const void* p, int f64, int64_t i) {
-    return f64 ? ((const double*)p)[i] : (double)((const float*)p)[i];
 }
 
 __device__ __forceinline__ double es_half_sum(double v) {        // over the lane's 32-lane half, the same value in every lane of it
@@ -123,8 +119,8 @@ __global__ __launch_bounds__(256) void es_resample_kernel(EsIn in, double* __res
         for (int s = 0; s < kEsResRun / 64; ++s) {
             const int64_t k = base + s * 64 + lane;
             if (k < r.n10) {
-                xr[r.r0 + k] = es_load(in.p[0], in.f64[0], r.off[0] + k);
-                yr[r.r0 + k] = es_load(in.p[1], in.f64[1], r.off[1] + k);
+                xr[r.r0 + k] = load_f64(in.p[0], in.f64[0], r.off[0] + k);
+                yr[r.r0 + k] = load_f64(in.p[1], in.f64[1], r.off[1] + k);
             }
         }
         return;
@@ -141,8 +137,8 @@ __global__ __launch_bounds__(256) void es_resample_kernel(EsIn in, double* __res
                 const double h = in.taps[j0 + t * up];
                 const int64_t i = src0 + t;
                 const bool inside = i >= 0 && i < r.len;
-                const double xv = inside ? es_load(in.p[0], in.f64[0], r.off[0] + i) : 0.0;
-                const double yv = inside ? es_load(in.p[1], in.f64[1], r.off[1] + i) : 0.0;
+                const double xv = inside ? load_f64(in.p[0], in.f64[0], r.off[0] + i) : 0.0;
+                const double yv = inside ? load_f64(in.p[1], in.f64[1], r.off[1] + i) : 0.0;
                 ax = fma(h, xv, ax);
                 ay = fma(h, yv, ay);
             }

@@ -16,7 +16,7 @@
 // Every table entry is rechecked against the scalar extents before memory is touched; a bad entry drops that utterance's work in
 // passes 1 and 2 and the finish writes NaN into its rows.
 #include <math.h>
-#include "common.hpp"
+#include "ragged.hpp"
 
 namespace dvae {
 
@@ -63,25 +63,21 @@ __device__ __forceinline__ SiItem si_item(const SiInputs& in, const int64_t* __r
     return r;
 }
 
-__device__ __forceinline__ double si_load(const void* p, int f64, int64_t i) {
-    return f64 ? ((const double*)p)[i] : (double)((const float*)p)[i];
-}
-
 // pass 1: dots[item] = {sum sh s, sum s s, sum sh n, sum n n} over the item's samples
 template <bool HasN>
 __global__ __launch_bounds__(256) void si_dots_kernel(SiInputs in, int U, const int64_t* __restrict__ tab, int64_t n_items, double* __restrict__ dots) {
-    const int64_t item = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t item = wave_item();
     const SiItem r = si_item<HasN>(in, tab, U, n_items, item);
     if (!r.ok) return;
     const int lane = threadIdx.x & 63;
     double hs = 0.0, ss = 0.0, hn = 0.0, nn = 0.0;
 #pragma unroll 4
     for (int64_t i = r.lo + lane; i < r.hi; i += 64) {
-        const double h = si_load(in.p[0], in.f64[0], r.off[0] + i), s = si_load(in.p[1], in.f64[1], r.off[1] + i);
+        const double h = load_f64(in.p[0], in.f64[0], r.off[0] + i), s = load_f64(in.p[1], in.f64[1], r.off[1] + i);
         hs = fma(h, s, hs);
         ss = fma(s, s, ss);
         if (HasN) {
-            const double n = si_load(in.p[2], in.f64[2], r.off[2] + i);
+            const double n = load_f64(in.p[2], in.f64[2], r.off[2] + i);
             hn = fma(h, n, hn);
             nn = fma(n, n, nn);
         }
@@ -114,7 +110,7 @@ __device__ __forceinline__ void si_total_dots(const double* __restrict__ dots, i
 template <bool HasN>
 __global__ __launch_bounds__(256) void si_residuals_kernel(SiInputs in, int U, const int64_t* __restrict__ tab, int64_t n_items,
                                                            const double* __restrict__ dots, double* __restrict__ res) {
-    const int64_t item = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t item = wave_item();
     const SiItem r = si_item<HasN>(in, tab, U, n_items, item);
     if (!r.ok) return;
     const int lane = threadIdx.x & 63;
@@ -124,7 +120,7 @@ __global__ __launch_bounds__(256) void si_residuals_kernel(SiInputs in, int U, c
     double e1 = 0.0, e2 = 0.0;
 #pragma unroll 4
     for (int64_t i = r.lo + lane; i < r.hi; i += 64) {
-        const double h = si_load(in.p[0], in.f64[0], r.off[0] + i), s = si_load(in.p[1], in.f64[1], r.off[1] + i);
+        const double h = load_f64(in.p[0], in.f64[0], r.off[0] + i), s = load_f64(in.p[1], in.f64[1], r.off[1] + i);
         double d1, d2 = 0.0;
         {
             // every operation rounded on its own, in the reference's order (numpy rounds each array it forms): s_target = alpha_s s,
@@ -134,7 +130,7 @@ __global__ __launch_bounds__(256) void si_residuals_kernel(SiInputs in, int U, c
             const double s_target = alpha_s * s;
             d1 = h - s_target;
             if (HasN) {
-                const double e_noise = alpha_n * si_load(in.p[2], in.f64[2], r.off[2] + i);
+                const double e_noise = alpha_n * load_f64(in.p[2], in.f64[2], r.off[2] + i);
                 d2 = d1 - e_noise;
                 d1 = e_noise + d2;
             }
@@ -228,8 +224,7 @@ extern "C" int dvae_si_ratios_batch(const void* s_hat, int64_t n_s_hat, int s_ha
     DVAE_CHECK_ARG(s_hat && s && workspace && n_s_hat > 0 && n_s > 0, "si_ratios_batch: null argument or empty buffer");
     DVAE_CHECK_ARG(!n || n_n > 0, "si_ratios_batch: the noise buffer needs its extent");
     DVAE_CHECK_ARG(ratios || sums, "si_ratios_batch: no output asked for");
-    DVAE_CHECK_ARG(U > 0 && tables && n_items >= U && cdiv(n_items, 4) < ((int64_t)1 << 31), "si_ratios_batch: bad table (U %d, %lld items)", U,
-                   (long long)n_items);
+    DVAE_CHECK_ARG(batch_launch_ok(U, tables, n_items) && n_items >= U, "si_ratios_batch: bad table (U %d, %lld items)", U, (long long)n_items);
     SiInputs in{{s_hat, s, n}, {n_s_hat, n_s, n ? n_n : 0}, {s_hat_f64 != 0, s_f64 != 0, n_f64 != 0}};
     if (n) return si_launch<true>(in, U, tables, n_items, ratios, sums, (double*)workspace, (hipStream_t)stream);
     return si_launch<false>(in, U, tables, n_items, ratios, sums, (double*)workspace, (hipStream_t)stream);

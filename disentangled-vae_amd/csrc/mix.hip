@@ -17,7 +17,7 @@
 // reference.  Input ranges may overlap or repeat (they are only read).  Every table entry is rechecked against the scalar extents
 // before memory is touched; a bad entry drops that utterance's work in passes 1 to 4 and the finish writes NaN into its stats row.
 #include <math.h>
-#include "common.hpp"
+#include "ragged.hpp"
 
 namespace dvae {
 
@@ -65,7 +65,7 @@ __device__ __forceinline__ bool mix_utterance(const MixArgs& a, int u, MixItem& 
 
 __device__ __forceinline__ MixItem mix_item(const MixArgs& a) {
     MixItem r{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, false};
-    const int64_t item = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t item = wave_item();
     const BatchItem it = batch_item(a.tab, a.U, item);
     if (it.u < 0 || item >= a.n_items) return r;
     if (!mix_utterance(a, it.u, r)) return r;
@@ -76,14 +76,6 @@ __device__ __forceinline__ MixItem mix_item(const MixArgs& a) {
 }
 
 __device__ __forceinline__ int64_t mix_item_index() { return (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); }
-
-__device__ __forceinline__ double mix_load(const void* p, int f64, int64_t i) {
-    return f64 ? ((const double*)p)[i] : (double)((const float*)p)[i];
-}
-
-__device__ __forceinline__ void mix_store(void* p, int f64, int64_t i, double v) {
-    if (f64) ((double*)p)[i] = v; else ((float*)p)[i] = (float)v;
-}
 
 // the maximum of the utterance's partials (exact in any order: lanes stride them)
 __device__ __forceinline__ double mix_total_max(const double* __restrict__ partial, const MixItem& r, int lane) {
@@ -113,7 +105,7 @@ __device__ __forceinline__ MixScalars mix_scalars(const MixArgs& a, const MixWor
 
 // s = speech / p (create_test_set.py:96; the samples as they are without normalise_speech)
 __device__ __forceinline__ double mix_speech(const MixArgs& a, const MixItem& r, int64_t i, double p) {
-    const double x = mix_load(a.speech, a.speech_f64, r.s0 + i);
+    const double x = load_f64(a.speech, a.speech_f64, r.s0 + i);
     return a.normalise ? x / p : x;
 }
 
@@ -124,7 +116,7 @@ __global__ __launch_bounds__(256) void mix_peak_kernel(MixArgs a, MixWork w) {
     const int lane = threadIdx.x & 63;
     double m = 0.0;
 #pragma unroll 4
-    for (int64_t i = r.lo + lane; i < r.hi; i += 64) m = max_nan(m, fabs(mix_load(a.speech, a.speech_f64, r.s0 + i)));
+    for (int64_t i = r.lo + lane; i < r.hi; i += 64) m = max_nan(m, fabs(load_f64(a.speech, a.speech_f64, r.s0 + i)));
     m = wave_max_nan(m);
     if (lane == 0) w.peak[mix_item_index()] = m;
 }
@@ -139,7 +131,7 @@ __global__ __launch_bounds__(256) void mix_power_kernel(MixArgs a, MixWork w) {
 #pragma unroll 4
     for (int64_t i = r.lo + lane; i < r.hi; i += 64) {
 #pragma clang fp contract(off)
-        const double s = mix_speech(a, r, i, m.p), n = mix_load(a.noise, a.noise_f64, r.n0 + i);
+        const double s = mix_speech(a, r, i, m.p), n = load_f64(a.noise, a.noise_f64, r.n0 + i);
         ps += s * s;
         pn += n * n;
     }
@@ -162,7 +154,7 @@ __global__ __launch_bounds__(256) void mix_norm_kernel(MixArgs a, MixWork w) {
     for (int64_t i = r.lo + lane; i < r.hi; i += 64) {
 #pragma clang fp contract(off)
         const double s = mix_speech(a, r, i, m.p);
-        const double v = mix_load(a.noise, a.noise_f64, r.n0 + i) * m.g;
+        const double v = load_f64(a.noise, a.noise_f64, r.n0 + i) * m.g;
         t = max_nan(max_nan(max_nan(t, fabs(s)), fabs(v)), fabs(s + v));
     }
     t = wave_max_nan(t);
@@ -182,19 +174,19 @@ __global__ __launch_bounds__(256) void mix_write_kernel(MixArgs a, MixWork w, vo
     for (int64_t i = r.lo + lane; i < r.hi; i += 64) {
 #pragma clang fp contract(off)
         const double s = mix_speech(a, r, i, m.p);
-        const double v = mix_load(a.noise, a.noise_f64, r.n0 + i) * m.g;
+        const double v = load_f64(a.noise, a.noise_f64, r.n0 + i) * m.g;
         const double os = s / norm, ov = v / norm, ox = (s + v) / norm;
-        mix_store(out_speech, a.out_f64, r.o0 + i, os);
-        mix_store(out_noise, a.out_f64, r.o0 + i, ov);
-        mix_store(out_mix, a.out_f64, r.o0 + i, ox);
+        store_f64(out_speech, a.out_f64, r.o0 + i, os);
+        store_f64(out_noise, a.out_f64, r.o0 + i, ov);
+        store_f64(out_mix, a.out_f64, r.o0 + i, ox);
         qs += os * os;
         qn += ov * ov;
     }
     if (r.hi == r.len) {
         for (int64_t i = r.len + lane; i < r.extent; i += 64) {
-            mix_store(out_speech, a.out_f64, r.o0 + i, 0.0);
-            mix_store(out_noise, a.out_f64, r.o0 + i, 0.0);
-            mix_store(out_mix, a.out_f64, r.o0 + i, 0.0);
+            store_f64(out_speech, a.out_f64, r.o0 + i, 0.0);
+            store_f64(out_noise, a.out_f64, r.o0 + i, 0.0);
+            store_f64(out_mix, a.out_f64, r.o0 + i, 0.0);
         }
     }
     qs = wave_sum(qs);
@@ -249,8 +241,7 @@ extern "C" int dvae_mix_snr_batch(const void* speech, int64_t n_speech, int spee
     DVAE_CHECK_ARG(speech && noise && workspace && snr_factor && n_speech > 0 && n_noise > 0, "mix_snr_batch: null argument or empty buffer");
     DVAE_CHECK_ARG(out_speech && out_noise && out_mix && n_out > 0, "mix_snr_batch: the three outputs and their extent are required");
     DVAE_CHECK_ARG(out_speech != out_noise && out_speech != out_mix && out_noise != out_mix, "mix_snr_batch: the three outputs must be three buffers");
-    DVAE_CHECK_ARG(U > 0 && tables && n_items >= U && cdiv(n_items, 4) < ((int64_t)1 << 31), "mix_snr_batch: bad table (U %d, %lld items)", U,
-                   (long long)n_items);
+    DVAE_CHECK_ARG(batch_launch_ok(U, tables, n_items) && n_items >= U, "mix_snr_batch: bad table (U %d, %lld items)", U, (long long)n_items);
     const MixArgs a{speech, noise, n_speech, n_noise, n_out, speech_f64 != 0, noise_f64 != 0, out_f64 != 0, normalise_speech != 0, U, tables, n_items,
                     snr_factor};
     double* ws = (double*)workspace;

@@ -9,7 +9,7 @@
 // frame-by-frame accumulation order exactly (deterministic, no atomics).
 #include <float.h>
 #include <stdlib.h>
-#include "common.hpp"
+#include "ragged.hpp"
 
 namespace dvae {
 

@@ -4,7 +4,7 @@
 // so every float32 operation of the numpy code is reproduced as "exact value rounded once to float32"
 // (double arithmetic, then one rounding): that is what a correctly rounded float32 libm returns.
 #include <math.h>
-#include "common.hpp"
+#include "ragged.hpp"
 
 namespace dvae {
 
@@ -146,24 +146,9 @@ __device__ __forceinline__ float wave_fmax(float v) {
     return v;
 }
 
-// One work item of a batch whose utterance u spans `extent` units (samples, frames or bins) in runs of `chunk`: [lo, hi) of them,
-// with the utterance's partials at [p0, p1).  ok = false for an entry the host's checks would have refused.
-struct ItemRange { int u; int64_t lo, hi, p0, p1; bool ok; };
-__device__ __forceinline__ ItemRange item_range(const int64_t* __restrict__ tab, int U, int64_t n_items, int64_t item, int64_t extent, int chunk,
-                                                BatchItem it) {
-    ItemRange r{it.u, 0, 0, 0, 0, false};
-    const int64_t p0 = uni64(tab[it.u]), p1 = uni64(tab[it.u + 1]);
-    r.lo = it.local * chunk;
-    r.hi = r.lo + chunk < extent ? r.lo + chunk : extent;
-    r.p0 = p0;
-    r.p1 = p1;
-    r.ok = extent >= 1 && item < n_items && p0 >= 0 && p1 <= n_items && p1 - p0 == (extent + chunk - 1) / chunk && r.lo < extent;
-    return r;
-}
-
 // tab = [items (U + 1) | x0 (U) | len (U)]: utterance u is x[x0[u] : x0[u] + len[u]]
 __device__ __forceinline__ ItemRange peak_item(const int64_t* __restrict__ tab, int U, int64_t n, int64_t n_items, int chunk, int64_t& x0) {
-    const int64_t item = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t item = wave_item();
     const BatchItem it = batch_item(tab, U, item);
     if (it.u < 0) return ItemRange{-1, 0, 0, 0, 0, false};
     x0 = uni64(tab[U + 1 + it.u]);
@@ -207,7 +192,7 @@ __global__ __launch_bounds__(256) void peak_divide_kernel(double* __restrict__ x
 // frame_energy_kernel), its frames are vad[frame_off[u] : frame_off[u + 1]]
 __device__ __forceinline__ ItemRange vad_item(const int64_t* __restrict__ tab, int U, int64_t n, int nfft, int hop, int64_t n_items, int chunk,
                                               int64_t T_total, int64_t& x0, int64_t& nu, int64_t& f0) {
-    const int64_t item = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t item = wave_item();
     const BatchItem it = batch_item(tab, U, item);
     if (it.u < 0) return ItemRange{-1, 0, 0, 0, 0, false};
     x0 = uni64(tab[U + 1 + it.u]);
@@ -263,7 +248,7 @@ __global__ __launch_bounds__(256) void vad_threshold_batch_kernel(const double* 
 // cols) matrix; with a gate, element i of it is multiplied by gate[g0[u] + i % cols[u]]
 __device__ __forceinline__ ItemRange ibm_item(const int64_t* __restrict__ tab, int U, int64_t n, int64_t n_items, int chunk, bool gated,
                                               int64_t n_gate, int64_t& e0, int64_t& cols, int64_t& g0) {
-    const int64_t item = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t item = wave_item();
     const BatchItem it = batch_item(tab, U, item);
     if (it.u < 0) return ItemRange{-1, 0, 0, 0, 0, false};
     e0 = uni64(tab[U + 1 + it.u]);
@@ -315,16 +300,12 @@ __global__ __launch_bounds__(256) void ibm_mask_batch_kernel(const float2* __res
 
 }  // namespace dvae
 
-static bool batch_launch_ok(int U, const int64_t* tables, int64_t n_items, int chunk) {
-    return U > 0 && tables && n_items > 0 && chunk > 0 && cdiv(n_items, 4) < ((int64_t)1 << 31);
-}
-
 extern "C" size_t dvae_peak_normalise_workspace_bytes(int64_t n_items) { return (size_t)(n_items > 0 ? n_items : 1) * sizeof(double); }
 
 extern "C" int dvae_peak_normalise_batch(double* x, int64_t n, int U, const int64_t* tables, int64_t n_items, int chunk, double* peak,
                                          void* workspace, void* stream) {
     DVAE_CHECK_ARG(x && peak && workspace && n > 0, "peak_normalise_batch: null argument or empty buffer");
-    DVAE_CHECK_ARG(batch_launch_ok(U, tables, n_items, chunk), "peak_normalise_batch: bad table (U %d, %lld items, chunk %d)", U,
+    DVAE_CHECK_ARG(batch_launch_ok(U, tables, n_items) && chunk > 0, "peak_normalise_batch: bad table (U %d, %lld items, chunk %d)", U,
                    (long long)n_items, chunk);
     hipStream_t s = (hipStream_t)stream;
     double* partial = (double*)workspace;
@@ -343,7 +324,7 @@ extern "C" size_t dvae_vad_batch_workspace_bytes(int64_t T_total, int64_t n_item
 extern "C" int dvae_vad_labels_batch(const void* y, int in_f64, int64_t n, int nfft, int hop, double vad_threshold, int U, const int64_t* tables,
                                      int64_t n_items, int chunk, int64_t T_total, float* vad, void* workspace, void* stream) {
     DVAE_CHECK_ARG(y && vad && workspace && n > 0 && nfft > 0 && hop > 0 && T_total > 0, "vad_labels_batch: bad argument");
-    DVAE_CHECK_ARG(batch_launch_ok(U, tables, n_items, chunk) && n_items <= T_total, "vad_labels_batch: bad table (U %d, %lld items, chunk %d)", U,
+    DVAE_CHECK_ARG(batch_launch_ok(U, tables, n_items) && chunk > 0 && n_items <= T_total, "vad_labels_batch: bad table (U %d, %lld items, chunk %d)", U,
                    (long long)n_items, chunk);
     hipStream_t s = (hipStream_t)stream;
     double* energy = (double*)workspace;
@@ -366,7 +347,7 @@ extern "C" int dvae_ibm_labels_batch(const void* S, int64_t n, float eps, float 
                                      const float* vad_gate, int64_t n_gate, float* mask, void* workspace, void* stream) {
     DVAE_CHECK_ARG(S && mask && workspace && n > 0, "ibm_labels_batch: null argument or empty buffer");
     DVAE_CHECK_ARG(!vad_gate || n_gate > 0, "ibm_labels_batch: a gate needs its extent");
-    DVAE_CHECK_ARG(batch_launch_ok(U, tables, n_items, chunk), "ibm_labels_batch: bad table (U %d, %lld items, chunk %d)", U, (long long)n_items, chunk);
+    DVAE_CHECK_ARG(batch_launch_ok(U, tables, n_items) && chunk > 0, "ibm_labels_batch: bad table (U %d, %lld items, chunk %d)", U, (long long)n_items, chunk);
     hipStream_t s = (hipStream_t)stream;
     float* partial = (float*)workspace;
     const dim3 grid((unsigned)cdiv(n_items, 4));

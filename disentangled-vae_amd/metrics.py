@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import native as N
-from . import stft as H
+from . import ragged as R
 
 SI_CHUNK = 4096            # samples per work item (DVAE_SI_CHUNK): fixed, so an utterance's sums never depend on the rest of the batch
 NAMES = ("s_hat", "s", "n")
@@ -31,96 +31,9 @@ def ratio_tables(views, totals, trim=0):
     views = [v for v in views if v is not None]
     if len(views) not in (2, 3) or len(totals) < len(views):
         raise ValueError("si_ratios_batch: views of s_hat and s (and n), with the element count of each buffer")
-    trim = int(trim)
-    if trim < 0:
-        raise ValueError(f"si_ratios_batch: trim must not be negative (got {trim})")
-    offs = [np.asarray(o, np.int64).reshape(-1) for o, _ in views]
-    lens = [np.asarray(n, np.int64).reshape(-1) for _, n in views]
-    U = offs[0].size
-    if U == 0:
-        raise ValueError("si_ratios_batch: no utterances")
-    for name, o, n in zip(NAMES, offs, lens):
-        if o.size != U or n.size != U:
-            raise ValueError(f"si_ratios_batch: {name} holds {max(o.size, n.size)} utterances, s_hat {U}")
-    for name, n in zip(NAMES[1:], lens[1:]):
-        bad = np.flatnonzero(n != lens[0])
-        if bad.size:
-            u = int(bad[0])
-            raise ValueError(f"si_ratios_batch: utterance {u}: s_hat has {int(lens[0][u])} samples, {name} {int(n[u])}")
-    short = np.flatnonzero(lens[0] <= 2 * trim)
-    if short.size:
-        u = int(short[0])
-        raise ValueError(f"si_ratios_batch: utterance {u} has {int(lens[0][u])} samples: "
-                         + (f"not longer than 2 * trim = {2 * trim}" if trim else "at least one is needed"))
-    for name, o, total in zip(NAMES, offs, totals):
-        bad = np.flatnonzero((o < 0) | (o + lens[0] > int(total)))
-        if bad.size:
-            u = int(bad[0])
-            raise ValueError(f"si_ratios_batch: utterance {u} of {name} ([{int(o[u])}, {int(o[u] + lens[0][u])})) leaves its buffer ({int(total)} elements)")
-    length = lens[0] - 2 * trim
-    cols = [o + trim for o in offs] + [np.zeros(U, np.int64)] * (3 - len(offs))
-    return np.concatenate([H._items(length, SI_CHUNK)] + cols + [length]).astype(np.int64)
-
-
-def _utterances(x, name):
-    """A WaveBatch as it is; anything else as a list of 1-D arrays / tensors (one array or tensor: a batch of one)."""
-    if isinstance(x, H.WaveBatch):
-        y = x.y
-        if not (torch.is_tensor(y) and y.is_cuda and y.dim() == 1 and y.dtype in (torch.float32, torch.float64)):
-            raise TypeError(f"si_ratios_batch: {name}: a WaveBatch over a 1-D float32 / float64 CUDA tensor is required")
-        return x
-    x = [x] if torch.is_tensor(x) or isinstance(x, np.ndarray) else list(x)
-    if not x:
-        raise ValueError(f"si_ratios_batch: {name}: no utterances")
-    for u, a in enumerate(x):
-        if getattr(a, "ndim", None) != 1:
-            raise ValueError(f"si_ratios_batch: {name}: utterance {u} is not a 1-D array or tensor")
-    return x
-
-
-def _view(x):
-    """(offsets, lengths, element count) of the packed buffer that _buffer makes of x."""
-    if isinstance(x, H.WaveBatch):
-        return x.offsets, x.lengths, x.y.numel()
-    lengths = [int(a.shape[0]) for a in x]
-    return np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64), lengths, int(np.sum(lengths))
-
-
-def _buffer(x, name, dev):
-    """The packed 1-D float32 / float64 CUDA tensor of x: a WaveBatch's own, device tensors concatenated, host arrays packed into
-    one pinned buffer and uploaded once."""
-    if isinstance(x, H.WaveBatch):
-        return x.y.contiguous()
-    if all(torch.is_tensor(a) and a.is_cuda for a in x):
-        dt = torch.float32 if all(a.dtype == torch.float32 for a in x) else torch.float64
-        return torch.cat([a.to(dt) for a in x]).contiguous()
-    if any(torch.is_tensor(a) and a.is_cuda for a in x):
-        raise TypeError(f"si_ratios_batch: {name} mixes host and device utterances")
-    xs = [a.detach().numpy() if torch.is_tensor(a) else np.asarray(a) for a in x]
-    for u, a in enumerate(xs):
-        if not np.issubdtype(a.dtype, np.floating):
-            raise TypeError(f"si_ratios_batch: {name}: utterance {u} is not floating point ({a.dtype})")
-    # float32 samples convert to double exactly, and the kernels compute in double whatever they read: one buffer type serves all
-    dt = torch.float32 if all(a.dtype == np.float32 for a in xs) else torch.float64
-    host = torch.empty(sum(len(a) for a in xs), dtype=dt, pin_memory=True)
-    h, o = host.numpy(), 0
-    for a in xs:
-        h[o:o + len(a)] = a
-        o += len(a)
-    return host.to(dev, non_blocking=True)
-
-
-def _device(args):
-    for a in args:
-        if isinstance(a, H.WaveBatch) and torch.is_tensor(a.y) and a.y.is_cuda:
-            return a.y.device
-        if torch.is_tensor(a) and a.is_cuda:
-            return a.device
-        if isinstance(a, (list, tuple)):
-            for t in a:
-                if torch.is_tensor(t) and t.is_cuda:
-                    return t.device
-    return H._device()
+    offs, length, U = R.paired_views("si_ratios_batch", NAMES, views, totals, trim)
+    cols = offs + [np.zeros(U, np.int64)] * (3 - len(offs))
+    return np.concatenate([R.item_prefix(length, SI_CHUNK)] + cols + [length]).astype(np.int64)
 
 
 def si_ratios_packed(bufs, tab, want_ratios=True, want_sums=False):
@@ -128,12 +41,7 @@ def si_ratios_packed(bufs, tab, want_ratios=True, want_sums=False):
     device), tab the table of ratio_tables over them.  -> (ratios [U, 3] or None, sums [U, 8] or None), float64 on the device."""
     lib = N.load()
     bufs = [b for b in bufs if b is not None]
-    dev = bufs[0].device
-    for name, b in zip(NAMES, bufs):
-        if not (torch.is_tensor(b) and b.is_cuda and b.dim() == 1 and b.dtype in (torch.float32, torch.float64) and b.is_contiguous()):
-            raise TypeError(f"si_ratios_batch: {name}: a contiguous 1-D float32 / float64 CUDA tensor is required")
-        if b.device != dev:
-            raise ValueError(f"si_ratios_batch: {name} lives on {b.device}, s_hat on {dev}")
+    dev = R.check_packed("si_ratios_batch", list(zip(NAMES, bufs)))
     tab = np.asarray(tab, np.int64)
     U = (tab.size - 1) // 5
     if U < 1 or tab.size != 5 * U + 1:
@@ -143,9 +51,9 @@ def si_ratios_packed(bufs, tab, want_ratios=True, want_sums=False):
         ratios = torch.empty((U, 3), dtype=torch.float64, device=dev) if want_ratios else None
         sums = torch.empty((U, 8), dtype=torch.float64, device=dev) if want_sums else None
         ws = torch.empty(lib.dvae_si_ratios_workspace_bytes(n_items), dtype=torch.uint8, device=dev)
-        tab_dev = H._upload(tab, dev)
+        tab_dev = R.upload(tab, dev)
         n = bufs[2] if len(bufs) == 3 else None
-        f64 = lambda b: 1 if b is not None and b.dtype == torch.float64 else 0
+        f64 = R.f64_flag
         N.check(lib.dvae_si_ratios_batch(N.ptr(bufs[0]), bufs[0].numel(), f64(bufs[0]), N.ptr(bufs[1]), bufs[1].numel(), f64(bufs[1]),
                                          N.ptr(n), n.numel() if n is not None else 0, f64(n), U, N.ptr(tab_dev), n_items,
                                          N.ptr(ratios), N.ptr(sums), N.ptr(ws), N.stream()), "dvae_si_ratios_batch")
@@ -153,13 +61,13 @@ def si_ratios_packed(bufs, tab, want_ratios=True, want_sums=False):
 
 
 def _score(s_hat, s, n, trim, return_sums):
-    args = [_utterances(a, name) for a, name in zip((s_hat, s, n), NAMES) if a is not None]
+    args = [R.as_list(a, f"si_ratios_batch: {name}") for a, name in zip((s_hat, s, n), NAMES) if a is not None]
     # the table is built (and refuses) before anything is uploaded or the library is loaded
-    views = [_view(a) for a in args]
+    views = [R.view(a) for a in args]
     tab = ratio_tables([(o, l) for o, l, _ in views], [t for _, _, t in views], trim)
-    dev = _device(args)
+    dev = R.find_device(*args)
     with torch.cuda.device(dev):
-        bufs = [_buffer(a, name, dev) for a, name in zip(args, NAMES)]
+        bufs = [R.pack(a, f"si_ratios_batch: {name}", dev) for a, name in zip(args, NAMES)]
     return si_ratios_packed(bufs, tab, True, return_sums)
 
 
@@ -245,40 +153,14 @@ def stoi_tables(views, totals, fs, trim=0):
     taps, p, q, L = stoi_taps(fs)
     if len(views) != 2 or len(totals) < 2:
         raise ValueError("stoi_batch: views of x and y, with the element count of each buffer")
-    trim = int(trim)
-    if trim < 0:
-        raise ValueError(f"stoi_batch: trim must not be negative (got {trim})")
-    offs = [np.asarray(o, np.int64).reshape(-1) for o, _ in views]
-    lens = [np.asarray(n, np.int64).reshape(-1) for _, n in views]
-    U = offs[0].size
-    if U == 0:
-        raise ValueError("stoi_batch: no utterances")
-    for name, o, n in zip(STOI_NAMES, offs, lens):
-        if o.size != U or n.size != U:
-            raise ValueError(f"stoi_batch: {name} holds {max(o.size, n.size)} utterances, x {U}")
-    bad = np.flatnonzero(lens[1] != lens[0])
-    if bad.size:
-        u = int(bad[0])
-        raise ValueError(f"stoi_batch: utterance {u}: x has {int(lens[0][u])} samples, y {int(lens[1][u])}")
-    short = np.flatnonzero(lens[0] <= 2 * trim)
-    if short.size:
-        u = int(short[0])
-        raise ValueError(f"stoi_batch: utterance {u} has {int(lens[0][u])} samples: "
-                         + (f"not longer than 2 * trim = {2 * trim}" if trim else "at least one is needed"))
-    for name, o, total in zip(STOI_NAMES, offs, totals):
-        bad = np.flatnonzero((o < 0) | (o + lens[0] > int(total)))
-        if bad.size:
-            u = int(bad[0])
-            raise ValueError(f"stoi_batch: utterance {u} of {name} ([{int(o[u])}, {int(o[u] + lens[0][u])})) leaves its buffer ({int(total)} elements)")
-    length = lens[0] - 2 * trim
+    offs, length, U = R.paired_views("stoi_batch", STOI_NAMES, views, totals, trim)
     if np.any(length > 1 << 31):
         raise ValueError("stoi_batch: an utterance of more than 2^31 samples")
     n10 = -(-length * p // q)
     J = stoi_frames_silent(n10)
     items = [np.maximum(1, -(-n10 // (STOI_RES_RUN * p))), np.maximum(1, -(-J // STOI_FRAME_RUN)),
              np.maximum(1, -(-np.maximum(J - STOI_SEG, 0) // STOI_SEG_RUN))]
-    pref = lambda a: np.concatenate([[0], np.cumsum(a)]).astype(np.int64)
-    table = np.concatenate([pref(i) for i in items] + [o + trim for o in offs] + [length, pref(n10)[:-1], pref(J)[:-1]]).astype(np.int64)
+    table = np.concatenate([R.prefix(i) for i in items] + offs + [length, R.prefix(n10)[:-1], R.prefix(J)[:-1]]).astype(np.int64)
     return {"table": table, "taps": taps, "p": p, "q": q, "L": L, "bands": stoi_band_edges(), "window": stoi_window(), "U": U,
             "n_res": int(n10.sum()), "n_frames": int(J.sum()), "resampled": n10, "frames": J}
 
@@ -290,7 +172,7 @@ def _stoi_device_consts(t, dev):
     """The window, the band edges and the taps of one sampling ratio on one device, uploaded once."""
     key = (str(dev), t["p"], t["q"])
     if key not in _stoi_consts:
-        _stoi_consts[key] = (H._upload(t["window"], dev), H._upload(t["bands"], dev), None if t["taps"] is None else H._upload(t["taps"], dev))
+        _stoi_consts[key] = (R.upload(t["window"], dev), R.upload(t["bands"], dev), None if t["taps"] is None else R.upload(t["taps"], dev))
     return _stoi_consts[key]
 
 
@@ -299,12 +181,7 @@ def stoi_packed(bufs, t, extended=False, return_info=False, return_tob=False, ta
     returned over them (table: another int64 table in place of t's).  -> d [U] float64 on the device (and info [U, 3] int64, and the
     debug output tob [2, n_frames, 15], NaN where no frame was written)."""
     lib = N.load()
-    dev = bufs[0].device
-    for name, b in zip(STOI_NAMES, bufs):
-        if not (torch.is_tensor(b) and b.is_cuda and b.dim() == 1 and b.dtype in (torch.float32, torch.float64) and b.is_contiguous()):
-            raise TypeError(f"stoi_batch: {name}: a contiguous 1-D float32 / float64 CUDA tensor is required")
-        if b.device != dev:
-            raise ValueError(f"stoi_batch: {name} lives on {b.device}, x on {dev}")
+    dev = R.check_packed("stoi_batch", list(zip(STOI_NAMES, bufs)))
     tab = np.asarray(t["table"] if table is None else table, np.int64)
     U = t["U"]
     if tab.size != 8 * U + 3:
@@ -316,8 +193,8 @@ def stoi_packed(bufs, t, extended=False, return_info=False, return_tob=False, ta
         tob = torch.full((2, max(t["n_frames"], 1), STOI_BANDS), float("nan"), dtype=torch.float64, device=dev) if return_tob else None
         ws = torch.empty(lib.dvae_estoi_workspace_bytes(t["n_res"], t["n_frames"], n_items[2], U), dtype=torch.uint8, device=dev)
         window, bands, taps = _stoi_device_consts(t, dev)
-        tab_dev = H._upload(tab, dev)
-        f64 = lambda b: 1 if b.dtype == torch.float64 else 0
+        tab_dev = R.upload(tab, dev)
+        f64 = R.f64_flag
         N.check(lib.dvae_estoi_batch(N.ptr(bufs[0]), bufs[0].numel(), f64(bufs[0]), N.ptr(bufs[1]), bufs[1].numel(), f64(bufs[1]), U,
                                      N.ptr(tab_dev), n_items[0], n_items[1], n_items[2], t["n_res"], t["n_frames"], N.ptr(taps), t["p"], t["q"],
                                      t["L"], N.ptr(window), N.ptr(bands), 1 if extended else 0, N.ptr(d), N.ptr(info), N.ptr(tob), N.ptr(ws),
@@ -332,12 +209,12 @@ def stoi_batch(x, y, fs, extended=False, trim=0, return_info=False):
     fs their sampling rate (a positive integer; anything but 10 kHz is resampled on the device).  trim: samples dropped at both ends of
     every utterance.  -> float64 CUDA tensor [U] (and the int64 [U, 3] of resampled length, kept frames and segments with
     return_info).  An utterance with fewer than 30 spectral frames scores 1e-5."""
-    args = [_utterances(a, name) for a, name in zip((x, y), STOI_NAMES)]
-    views = [_view(a) for a in args]
+    args = [R.as_list(a, f"si_ratios_batch: {name}") for a, name in zip((x, y), STOI_NAMES)]     # (the messages have always said si_ratios_batch)
+    views = [R.view(a) for a in args]
     t = stoi_tables([(o, l) for o, l, _ in views], [n for _, _, n in views], fs, trim)      # refuses before anything is uploaded
-    dev = _device(args)
+    dev = R.find_device(*args)
     with torch.cuda.device(dev):
-        bufs = [_buffer(a, name, dev) for a, name in zip(args, STOI_NAMES)]
+        bufs = [R.pack(a, f"si_ratios_batch: {name}", dev) for a, name in zip(args, STOI_NAMES)]
     return stoi_packed(bufs, t, extended, return_info)
 
 

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import native as N
+from . import ragged as R
 from . import stft as H
 
 MIX_CHUNK = 4096           # samples per work item (DVAE_MIX_CHUNK): fixed, so an utterance's sums never depend on the rest of the batch
@@ -73,7 +74,7 @@ def mix_tables(speech_view, noise_view, starts, lengths, totals, out_layout=None
         raise ValueError(f"mix_at_snr_batch: utterance {u}: noise bank {int(index[u])} leaves the noise buffer ({int(totals[1])} elements)")
     if out_layout is None:
         extent = length
-        out0 = np.concatenate([[0], np.cumsum((extent + 63) // 64 * 64)[:-1]]).astype(np.int64)
+        out0 = R.prefix((extent + 63) // 64 * 64)[:-1]
     else:
         out0 = _per_utterance("out0", out_layout[0], U).astype(np.int64)
         extent = _per_utterance("out_extent", out_layout[1], U).astype(np.int64)
@@ -89,7 +90,7 @@ def mix_tables(speech_view, noise_view, starts, lengths, totals, out_layout=None
         if clash.size:
             a, b = int(order[clash[0]]), int(order[clash[0] + 1])
             raise ValueError(f"mix_at_snr_batch: the output ranges of utterances {a} and {b} overlap")
-    return np.concatenate([H._items(length, MIX_CHUNK), s_off, bo + starts, out0, length, extent]).astype(np.int64)
+    return np.concatenate([R.item_prefix(length, MIX_CHUNK), s_off, bo + starts, out0, length, extent]).astype(np.int64)
 
 
 def condition_grid(n_utts, noise_types, snrs):
@@ -129,61 +130,9 @@ def snr_factors(snr_db):
     return np.array([np.power(10, -float(s) / 10) for s in snr_db], np.float64)
 
 
-def _floats(x, name):
-    """A list of 1-D floating-point arrays / tensors (one array or tensor: a list of one)."""
-    x = [x] if torch.is_tensor(x) or isinstance(x, np.ndarray) else list(x)
-    if not x:
-        raise ValueError(f"mix_at_snr_batch: {name}: nothing given")
-    for u, a in enumerate(x):
-        if getattr(a, "ndim", None) != 1:
-            raise ValueError(f"mix_at_snr_batch: {name}: entry {u} is not a 1-D array or tensor")
-        if not (a.dtype.is_floating_point if torch.is_tensor(a) else np.issubdtype(a.dtype, np.floating)):
-            raise TypeError(f"mix_at_snr_batch: {name}: entry {u} is not floating point ({a.dtype})")
-    return x
-
-
-def _view(x):
-    """(offsets, lengths, element count) of the packed buffer _buffer makes of the list x; an array given twice is packed once."""
-    seen, offs, total = {}, [], 0
-    for a in x:
-        if id(a) not in seen:
-            seen[id(a)] = total
-            total += int(a.shape[0])
-        offs.append(seen[id(a)])
-    return np.asarray(offs, np.int64), np.asarray([int(a.shape[0]) for a in x], np.int64), total
-
-
-def _buffer(x, name, dev):
-    """The packed 1-D float32 / float64 CUDA tensor of the list x, in the order of _view: one device tensor is adopted as it is,
-    several are concatenated, host arrays are packed into one pinned buffer and uploaded once."""
-    uniq = list({id(a): a for a in x}.values())
-    on_dev = [torch.is_tensor(a) and a.is_cuda for a in uniq]
-    if all(on_dev):
-        dt = torch.float32 if all(a.dtype == torch.float32 for a in uniq) else torch.float64
-        if len(uniq) == 1 and uniq[0].dtype == dt:
-            return uniq[0].contiguous()
-        return torch.cat([a.to(dt) for a in uniq]).contiguous()
-    if any(on_dev):
-        raise TypeError(f"mix_at_snr_batch: {name} mixes host and device entries")
-    xs = [a.detach().numpy() if torch.is_tensor(a) else np.asarray(a) for a in uniq]
-    # float32 samples convert to double exactly, and the kernels compute in double whatever they read: one buffer type serves all
-    dt = torch.float32 if all(a.dtype == np.float32 for a in xs) else torch.float64
-    host = torch.empty(sum(len(a) for a in xs), dtype=dt, pin_memory=True)
-    h, o = host.numpy(), 0
-    for a in xs:
-        h[o:o + len(a)] = a
-        o += len(a)
-    return host.to(dev, non_blocking=True)
-
-
-def _device(*groups):
-    for g in groups:
-        if isinstance(g, H.WaveBatch):
-            g = [g.y]
-        for a in g:
-            if torch.is_tensor(a) and a.is_cuda:
-                return a.device
-    return H._device()
+def _entries(x, name):
+    """A WaveBatch as it is, anything else as a list of 1-D floating-point arrays / tensors (ragged.as_list in this module's words)."""
+    return R.as_list(x, f"mix_at_snr_batch: {name}", R.ENTRY, "nothing given", floating=True)
 
 
 class MixBatch:
@@ -213,12 +162,7 @@ def mix_packed(speech, noise, tab, factors, normalise_speech=True, out_dtype=tor
     the last output range); outputs: three preallocated 1-D tensors of out_dtype to write into instead.
     -> (out_speech, out_noise, out_mix, stats [U, 6] float64), all on the device."""
     lib = N.load()
-    dev = speech.device
-    for name, b in (("speech", speech), ("noise", noise)):
-        if not (torch.is_tensor(b) and b.is_cuda and b.dim() == 1 and b.dtype in (torch.float32, torch.float64) and b.is_contiguous()):
-            raise TypeError(f"mix_at_snr_batch: {name}: a contiguous 1-D float32 / float64 CUDA tensor is required")
-        if b.device != dev:
-            raise ValueError(f"mix_at_snr_batch: {name} lives on {b.device}, speech on {dev}")
+    dev = R.check_packed("mix_at_snr_batch", [("speech", speech), ("noise", noise)])
     if out_dtype not in (torch.float32, torch.float64):
         raise TypeError(f"mix_at_snr_batch: out_dtype float32 or float64 (got {out_dtype})")
     tab = np.asarray(tab, np.int64)
@@ -240,8 +184,8 @@ def mix_packed(speech, noise, tab, factors, normalise_speech=True, out_dtype=tor
                 raise TypeError(f"mix_at_snr_batch: every output must be a contiguous 1-D {out_dtype} tensor of {n_out} elements on {dev}")
         stats = torch.empty((U, 6), dtype=torch.float64, device=dev)
         ws = torch.empty(lib.dvae_mix_snr_workspace_bytes(n_items, U), dtype=torch.uint8, device=dev)
-        tab_dev, fac_dev = H._upload(tab, dev), H._upload(factors, dev)
-        f64 = lambda b: 1 if b.dtype == torch.float64 else 0
+        tab_dev, fac_dev = R.upload(tab, dev), R.upload(factors, dev)
+        f64 = R.f64_flag
         N.check(lib.dvae_mix_snr_batch(N.ptr(speech), speech.numel(), f64(speech), N.ptr(noise), noise.numel(), f64(noise), U, N.ptr(tab_dev),
                                        n_items, N.ptr(fac_dev), 1 if normalise_speech else 0, N.ptr(outputs[0]), N.ptr(outputs[1]),
                                        N.ptr(outputs[2]), n_out, 1 if out_dtype == torch.float64 else 0, N.ptr(stats), N.ptr(ws), N.stream()),
@@ -260,19 +204,10 @@ def mix_at_snr_batch(speech, noise_banks, noise_index, starts, snr_db, normalise
     (one more rounding of the double result).  stft_layout=True lays the three outputs out as plan_stft_batch lays out padded signals
     (center=False, the end pad of hop zeros written by the kernel), so that MixBatch.spec() transforms the mixtures in place.
     -> MixBatch.  Nothing is synchronised: the call enqueues on the current stream."""
-    if isinstance(speech, H.WaveBatch):
-        y = speech.y
-        if not (torch.is_tensor(y) and y.is_cuda and y.dim() == 1 and y.dtype in (torch.float32, torch.float64)):
-            raise TypeError("mix_at_snr_batch: speech: a WaveBatch over a 1-D float32 / float64 CUDA tensor is required")
-        s_view = (np.asarray(speech.offsets, np.int64), np.asarray(speech.lengths, np.int64), y.numel())
-    else:
-        speech = _floats(speech, "speech")
-        s_view = _view(speech)
-    if isinstance(noise_banks, H.WaveBatch):
-        b_view = (np.asarray(noise_banks.offsets, np.int64), np.asarray(noise_banks.lengths, np.int64), noise_banks.y.numel())
-    else:
-        noise_banks = _floats(noise_banks, "noise_banks")
-        b_view = _view(noise_banks)
+    speech = _entries(speech, "speech")
+    if not isinstance(noise_banks, H.WaveBatch):          # a WaveBatch of banks is taken as it is: mix_packed checks its buffer
+        noise_banks = _entries(noise_banks, "noise_banks")
+    s_view, b_view = R.view(speech, dedupe=True), R.view(noise_banks, dedupe=True)
     U = len(s_view[0])
     # every refusal comes before anything is uploaded or the library is loaded
     snr_db = _per_utterance("snr_db", np.asarray(snr_db, np.float64), U)
@@ -281,10 +216,10 @@ def mix_at_snr_batch(speech, noise_banks, noise_index, starts, snr_db, normalise
     n_out = None if plan is None else int(plan["padded"].sum())
     tab = mix_tables(s_view[:2], (b_view[0], b_view[1], noise_index), starts, None, (s_view[2], b_view[2], n_out), layout)
     factors = snr_factors(snr_db)
-    dev = _device(speech, noise_banks)
+    dev = R.find_device(speech, noise_banks)
     with torch.cuda.device(dev):
-        s_buf = speech.y.contiguous() if isinstance(speech, H.WaveBatch) else _buffer(speech, "speech", dev)
-        b_buf = noise_banks.y.contiguous() if isinstance(noise_banks, H.WaveBatch) else _buffer(noise_banks, "noise_banks", dev)
+        s_buf = R.pack(speech, "mix_at_snr_batch: speech", dev, R.ENTRY, dedupe=True)
+        b_buf = R.pack(noise_banks, "mix_at_snr_batch: noise_banks", dev, R.ENTRY, dedupe=True)
     out_s, out_n, out_x, stats = mix_packed(s_buf, b_buf, tab, factors, normalise_speech, out_dtype, n_out)
     out0, lengths = tab[3 * U + 1:4 * U + 1], tab[4 * U + 1:5 * U + 1]
     return MixBatch(*(H.WaveBatch(o, out0, lengths) for o in (out_s, out_n, out_x)), stats, snr_db, plan)

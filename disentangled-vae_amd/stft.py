@@ -11,6 +11,8 @@ import numpy as np
 import torch
 
 from . import native as N
+from . import ragged as R
+from .ragged import WaveBatch  # noqa: F401  (istft_batch returns it; importable from here as before)
 
 
 def sizes(fs, wlen_sec, hop_percent, what="STFT"):
@@ -48,12 +50,6 @@ def window_f64(win, nfft, device):
         w = torch.from_numpy(np.ascontiguousarray(get_window(win, nfft, fftbins=True), dtype=np.float64)).to(device)
         _window_cache[key] = w
     return w
-
-
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("STFT/ISTFT run on the MI355X HIP path only: no GPU is visible (no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def stft_device(x_dev, window, nfft, hop, T, layout=0):
@@ -168,7 +164,7 @@ def stft_numpy(x, fs, wlen_sec, win, hop_percent, center, pad_mode, pad_at_end, 
     if center:
         x_ = np.pad(x_, int(nfft // 2), mode=pad_mode)
     T = frame_count(len(x_), nfft, hop)
-    dev = _device()
+    dev = R.device()
     xin = np.ascontiguousarray(x_, dtype=np.float64 if x_.dtype != np.float32 else np.float32)
     # the complex result is computed frame-major (whole frames leave the kernel as contiguous rows) and returned as the
     # transpose view: a Fortran-ordered [F, T] array, which is also what librosa.stft hands the reference
@@ -197,7 +193,7 @@ def istft_numpy(Sxx, fs, wlen_sec, win, hop_percent, center, dtype, max_len):
         out_len = ntot - 2 * (nfft // 2) if center else ntot
     else:
         out_len = int(max_len)
-    dev = _device()
+    dev = R.device()
     # frame-major on the device (each frame one contiguous row): free for a Fortran-ordered S (what stft() returns), one host
     # transpose for a C-ordered one
     S_dev = torch.from_numpy(np.ascontiguousarray(S.T, dtype=np.complex64)).to(dev).T
@@ -234,8 +230,7 @@ def plan_stft_batch(lengths, fs=16000, wlen_sec=64e-3, hop_percent=0.25, center=
     end_pad = np.array([1 if pad_at_end and needs_end_pad(n, fs, wlen_sec, hop_percent) else 0 for n in lengths], np.int64)
     padded = np.array(lengths, np.int64) + hop * end_pad + (2 * (nfft // 2) if center else 0)
     frames = np.array([frame_count(int(p), nfft, hop) for p in padded], np.int64)
-    frame_off = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
-    x0 = np.concatenate([[0], np.cumsum(padded)[:-1]]).astype(np.int64)
+    frame_off, x0 = R.prefix(frames), R.prefix(padded)[:-1]
     return dict(nfft=nfft, hop=hop, end_pad=end_pad, padded=padded, frames=frames, frame_off=frame_off, x0=x0)
 
 
@@ -253,17 +248,6 @@ def batch_chunk(frames):
     return best[1]
 
 
-def _items(frames, chunk):
-    items = -(-np.asarray(frames, np.int64) // chunk)
-    return np.concatenate([[0], np.cumsum(items)]).astype(np.int64)
-
-
-def _monotone(name, a):
-    a = np.asarray(a, np.int64)
-    if a.size > 1 and np.any(np.diff(a) < 0):
-        raise ValueError(f"{name} must be non-decreasing: {a.tolist()[:16]}")
-
-
 def stft_tables(frames, x0, padded, n_total, chunk):
     """The int64 table of dvae_stft_batch, [items (U + 1) | frame_off (U + 1) | x0 (U)], after checking that the signals do not
     overlap and lie inside the n_total packed samples, and that every frame lies inside its own signal."""
@@ -273,14 +257,14 @@ def stft_tables(frames, x0, padded, n_total, chunk):
         raise ValueError("stft_batch: frames, x0 and padded lengths need one entry per utterance")
     if np.any(frames < 1):
         raise ValueError(f"stft_batch: every utterance needs at least one frame (frames {frames.tolist()[:16]})")
-    _monotone("stft_batch: signal offsets", x0)
+    R.monotone("stft_batch: signal offsets", x0)
     if x0[0] < 0 or np.any(x0[:-1] + padded[:-1] > x0[1:]) or x0[-1] + padded[-1] > n_total:
         raise ValueError("stft_batch: signals overlap or leave the packed buffer")
     if np.any((frames - 1) * BATCH_HOP + BATCH_NFFT > padded):
         raise ValueError("stft_batch: frames beyond the end of their signal")
     if np.any(padded * 8 >= 2 ** 31) or np.any(frames * 513 * 8 >= 2 ** 31):
         raise ValueError("stft_batch: an utterance of 2 GB or more (use the single-signal stft)")
-    return np.concatenate([_items(frames, chunk), np.concatenate([[0], np.cumsum(frames)]), x0]).astype(np.int64)
+    return np.concatenate([R.item_prefix(frames, chunk), R.prefix(frames), x0]).astype(np.int64)
 
 
 def istft_tables(f0, nfr, y0, out_len, gcol, T_total, y_total, ldg, chunk):
@@ -293,19 +277,15 @@ def istft_tables(f0, nfr, y0, out_len, gcol, T_total, y_total, ldg, chunk):
         raise ValueError("istft_batch: the tables need one entry per utterance")
     if np.any(nfr < 1) or np.any(out_len < 0):
         raise ValueError("istft_batch: every utterance needs at least one frame and a non-negative length")
-    _monotone("istft_batch: frame offsets", f0)
-    _monotone("istft_batch: output offsets", y0)
+    R.monotone("istft_batch: frame offsets", f0)
+    R.monotone("istft_batch: output offsets", y0)
     if f0[0] < 0 or np.any(f0[:-1] + nfr[:-1] > f0[1:]) or f0[-1] + nfr[-1] > T_total:
         raise ValueError("istft_batch: frames overlap or leave the packed spectrogram")
     if y0[0] < 0 or np.any(y0 % 2) or np.any(y0[:-1] + out_len[:-1] > y0[1:]) or y0[-1] + out_len[-1] > y_total:
         raise ValueError("istft_batch: outputs overlap, leave the output buffer or start at an odd sample")
     if ldg is not None and (np.any(gcol < 0) or np.any(gcol + nfr > ldg) or 513 * ldg * 4 >= 2 ** 31):
         raise ValueError("istft_batch: gain columns outside the gain plane (or a plane of 2 GB or more)")
-    return np.concatenate([_items(nfr, chunk), f0, nfr, y0, out_len, gcol]).astype(np.int64)
-
-
-def _upload(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(dev, non_blocking=True)
+    return np.concatenate([R.item_prefix(nfr, chunk), f0, nfr, y0, out_len, gcol]).astype(np.int64)
 
 
 class SpecBatch:
@@ -317,7 +297,7 @@ class SpecBatch:
         self.frames, self.nfft, self.hop, self.center, self.layout = frames, nfft, hop, center, layout
         self.counts = [int(c) for c in counts]
         self.lengths = [int(n) for n in lengths]
-        self.frame_off = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int64)
+        self.frame_off = R.prefix(self.counts)
 
     def __len__(self):
         return len(self.counts)
@@ -330,24 +310,6 @@ class SpecBatch:
         """Every utterance as a host array [513, T_u] (Fortran-ordered views of one host copy)."""
         h = self.frames.cpu().numpy()
         return [h[a:b].T for a, b in zip(self.frame_off[:-1], self.frame_off[1:])]
-
-
-class WaveBatch:
-    """A ragged batch of waveforms on the device: y float32, utterance u is y[offsets[u] : offsets[u] + lengths[u]] (offsets are
-    multiples of 64 samples; what lies between two utterances is unspecified)."""
-
-    def __init__(self, y, offsets, lengths):
-        self.y, self.offsets, self.lengths = y, [int(o) for o in offsets], [int(n) for n in lengths]
-
-    def __len__(self):
-        return len(self.lengths)
-
-    def __getitem__(self, u):
-        return self.y[self.offsets[u]:self.offsets[u] + self.lengths[u]]
-
-    def numpy(self):
-        h = self.y.cpu().numpy()
-        return [h[o:o + n] for o, n in zip(self.offsets, self.lengths)]
 
 
 def stft_packed(x_dev, frames, x0, padded, lengths=None, center=False, layout=2):
@@ -365,8 +327,8 @@ def stft_packed(x_dev, frames, x0, padded, lengths=None, center=False, layout=2)
     tab = stft_tables(frames, x0, padded, x_dev.numel(), chunk)
     U = frames.size
     out = torch.empty((T_total, BATCH_NFFT // 2 + 1), dtype=torch.complex64 if layout == 2 else torch.float32, device=x_dev.device)
-    tab_dev = _upload(tab, x_dev.device)
-    N.check(lib.dvae_stft_batch(N.ptr(x_dev), 1 if x_dev.dtype == torch.float64 else 0, x_dev.numel(), N.ptr(window_f64("hann", BATCH_NFFT, x_dev.device)),
+    tab_dev = R.upload(tab, x_dev.device)
+    N.check(lib.dvae_stft_batch(N.ptr(x_dev), R.f64_flag(x_dev), x_dev.numel(), N.ptr(window_f64("hann", BATCH_NFFT, x_dev.device)),
                                 BATCH_NFFT, BATCH_HOP, U, N.ptr(tab_dev), int(tab[U]), chunk, T_total, N.ptr(out), layout, N.stream()), "dvae_stft_batch")
     return SpecBatch(out, frames, padded if lengths is None else lengths, BATCH_NFFT, BATCH_HOP, center, layout)
 
@@ -393,7 +355,7 @@ def stft_batch(signals, fs=16000, wlen_sec=64e-3, win="hann", hop_percent=0.25, 
         if center:
             x_ = np.pad(x_, int(nfft // 2), mode=pad_mode)
         buf[a:a + p] = x_
-    dev = _device()
+    dev = R.device()
     return stft_packed(torch.from_numpy(buf).to(dev), plan["frames"], plan["x0"], plan["padded"], [len(x) for x in xs], center, layout)
 
 
@@ -435,7 +397,7 @@ def istft_batch(spec, max_len=None, gain=None, gain_cols=None, center=None):
         raise TypeError("istft_batch: frames must be a contiguous complex64 [T, 513] CUDA tensor")
     U = len(spec)
     nfr, lens, start = istft_plan(spec.counts, max_len, spec.nfft, spec.hop, center)
-    y0 = np.concatenate([[0], np.cumsum((np.asarray(lens, np.int64) + 63) // 64 * 64)]).astype(np.int64)
+    y0 = R.prefix((np.asarray(lens, np.int64) + 63) // 64 * 64)
     y_total = max(int(y0[-1]), 2)
     planes = None if gain is None else (list(gain) if isinstance(gain, (list, tuple)) else [gain])
     ldg = None
@@ -451,7 +413,7 @@ def istft_batch(spec, max_len=None, gain=None, gain_cols=None, center=None):
     gcol = np.zeros(U, np.int64) if gain_cols is None else np.asarray(gain_cols, np.int64)
     chunk = batch_chunk(nfr)
     tab = istft_tables(spec.frame_off[:-1], nfr, y0[:-1], lens, gcol, S.shape[0], y_total, ldg, chunk)
-    tab_dev = _upload(tab, S.device)
+    tab_dev = R.upload(tab, S.device)
     ys = [torch.empty(y_total, dtype=torch.float32, device=S.device) for _ in range(1 if planes is None else len(planes))]
     g0 = planes[0] if planes else None
     g1 = planes[1] if planes and len(planes) > 1 else None

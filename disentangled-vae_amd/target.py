@@ -4,6 +4,7 @@ import numpy as np
 import torch
 
 from . import native as N
+from . import ragged as R
 from . import stft as H
 
 
@@ -82,23 +83,10 @@ IBM_CHUNK = 4096           # bins per work item of the mask
 VAD_ITEMS = 8192           # work items the VAD chunk aims at (one wave each: 8 rounds of 1024 four-wave workgroups)
 
 
-def _segments(what, start, extent, n_total):
-    """start / extent: one int64 entry per utterance; refuses empty, overlapping or out-of-buffer segments."""
-    start, extent = np.asarray(start, np.int64).reshape(-1), np.asarray(extent, np.int64).reshape(-1)
-    if start.size == 0 or extent.size != start.size:
-        raise ValueError(f"{what}: the tables need one entry per utterance (got {start.size} offsets, {extent.size} extents)")
-    if np.any(extent < 1):
-        raise ValueError(f"{what}: every utterance needs at least one element (extents {extent.tolist()[:16]})")
-    H._monotone(f"{what}: offsets", start)
-    if start[0] < 0 or np.any(start[:-1] + extent[:-1] > start[1:]) or start[-1] + extent[-1] > n_total:
-        raise ValueError(f"{what}: utterances overlap or leave the packed buffer ({n_total} elements)")
-    return start, extent
-
-
 def peak_tables(x0, lengths, n_total, chunk=PEAK_CHUNK):
     """The int64 table of dvae_peak_normalise_batch, [items (U + 1) | x0 (U) | len (U)]."""
-    x0, lengths = _segments("peak_normalise_batch", x0, lengths, n_total)
-    return np.concatenate([H._items(lengths, chunk), x0, lengths]).astype(np.int64)
+    x0, lengths = R.segments("peak_normalise_batch", x0, lengths, n_total)
+    return np.concatenate([R.item_prefix(lengths, chunk), x0, lengths]).astype(np.int64)
 
 
 def vad_chunk(frames):
@@ -110,20 +98,20 @@ def vad_tables(x0, n, frames, n_total, nfft, hop, chunk):
     """The int64 table of dvae_vad_labels_batch, [items (U + 1) | x0 (U) | n (U) | frame_off (U + 1)]: utterance u's samples are
     x[x0[u] : x0[u] + n[u]] and its frames may reach n[u] + hop (the implied zero end pad of dvae_vad_labels)."""
     frames = np.asarray(frames, np.int64).reshape(-1)
-    x0, n = _segments("vad_labels_batch", x0, n, n_total)
+    x0, n = R.segments("vad_labels_batch", x0, n, n_total)
     if frames.size != x0.size:
         raise ValueError("vad_labels_batch: frames need one entry per utterance")
     if np.any(frames < 1):
         raise ValueError(f"vad_labels_batch: every utterance needs at least one frame (frames {frames.tolist()[:16]})")
     if np.any((frames - 1) * hop + nfft > n + hop):
         raise ValueError("vad_labels_batch: frames beyond the end of their signal and its end pad")
-    return np.concatenate([H._items(frames, chunk), x0, n, np.concatenate([[0], np.cumsum(frames)])]).astype(np.int64)
+    return np.concatenate([R.item_prefix(frames, chunk), x0, n, R.prefix(frames)]).astype(np.int64)
 
 
 def ibm_tables(e0, count, cols, n_total, chunk=IBM_CHUNK, g0=None, n_gate=0):
     """The int64 table of dvae_ibm_labels_batch, [items (U + 1) | e0 (U) | count (U) | cols (U) | g0 (U)]: segment u is a row-major
     (count / cols, cols) matrix at S[e0[u]:]; with a gate (g0 given), its column j is scaled by gate[g0[u] + j] (n_gate entries)."""
-    e0, count = _segments("ibm_labels_batch", e0, count, n_total)
+    e0, count = R.segments("ibm_labels_batch", e0, count, n_total)
     cols = np.asarray(cols, np.int64).reshape(-1)
     if cols.size != e0.size or np.any(cols < 1) or np.any(count % cols):
         raise ValueError("ibm_labels_batch: every segment needs a column count that divides its length")
@@ -133,7 +121,7 @@ def ibm_tables(e0, count, cols, n_total, chunk=IBM_CHUNK, g0=None, n_gate=0):
         g0 = np.asarray(g0, np.int64).reshape(-1)
         if g0.size != e0.size or np.any(g0 < 0) or np.any(g0 + cols > n_gate):
             raise ValueError(f"ibm_labels_batch: gate columns outside the gate ({n_gate} entries)")
-    return np.concatenate([H._items(count, chunk), e0, count, cols, g0]).astype(np.int64)
+    return np.concatenate([R.item_prefix(count, chunk), e0, count, cols, g0]).astype(np.int64)
 
 
 def _vector(t, what, dtypes):
@@ -158,7 +146,7 @@ def peak_normalise_batch(x_dev, x0, lengths):
     n_items = int(tab[U])
     peak = torch.empty(U, dtype=torch.float64, device=x_dev.device)
     ws = torch.empty(lib.dvae_peak_normalise_workspace_bytes(n_items), dtype=torch.uint8, device=x_dev.device)
-    tab_dev = H._upload(tab, x_dev.device)
+    tab_dev = R.upload(tab, x_dev.device)
     N.check(lib.dvae_peak_normalise_batch(N.ptr(x_dev), x_dev.numel(), U, N.ptr(tab_dev), n_items, PEAK_CHUNK, N.ptr(peak), N.ptr(ws), N.stream()),
             "dvae_peak_normalise_batch")
     return peak
@@ -178,8 +166,8 @@ def vad_labels_batch(x_dev, x0, n, frames, nfft, hop, vad_threshold=1.70):
     n_items = int(tab[U])
     vad = torch.empty(T_total, dtype=torch.float32, device=x_dev.device)
     ws = torch.empty(lib.dvae_vad_batch_workspace_bytes(T_total, n_items), dtype=torch.uint8, device=x_dev.device)
-    tab_dev = H._upload(tab, x_dev.device)
-    N.check(lib.dvae_vad_labels_batch(N.ptr(x_dev), 1 if x_dev.dtype == torch.float64 else 0, x_dev.numel(), int(nfft), int(hop), float(vad_threshold),
+    tab_dev = R.upload(tab, x_dev.device)
+    N.check(lib.dvae_vad_labels_batch(N.ptr(x_dev), R.f64_flag(x_dev), x_dev.numel(), int(nfft), int(hop), float(vad_threshold),
                                       U, N.ptr(tab_dev), n_items, chunk, T_total, N.ptr(vad), N.ptr(ws), N.stream()), "dvae_vad_labels_batch")
     return vad
 
@@ -203,7 +191,7 @@ def ibm_labels_batch(S_flat, e0, count, cols, eps=1e-8, ibm_threshold=50, gate=N
     mask = torch.empty(S.shape, dtype=torch.float32, device=S.device)
     ws = torch.empty(lib.dvae_ibm_batch_workspace_bytes(n_items), dtype=torch.uint8, device=S.device)
     gate = None if gate is None else _dev(gate).contiguous()
-    tab_dev = H._upload(tab, S.device)
+    tab_dev = R.upload(tab, S.device)
     N.check(lib.dvae_ibm_labels_batch(N.ptr(torch.view_as_real(S)), S.numel(), float(eps), float(ibm_threshold), U, N.ptr(tab_dev), n_items,
                                       IBM_CHUNK, N.ptr(gate), gate.numel() if gate is not None else 0, N.ptr(mask), N.ptr(ws), N.stream()),
             "dvae_ibm_labels_batch")
@@ -217,7 +205,7 @@ class FrameBatch:
     def __init__(self, X, Y, counts):
         self.X, self.Y = X, Y
         self.counts = [int(c) for c in counts]
-        self.frame_off = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int64)
+        self.frame_off = R.prefix(self.counts)
 
     def __len__(self):
         return len(self.counts)

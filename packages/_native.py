@@ -40,6 +40,10 @@ def stft_host():
     return _mod("stft")
 
 
+def ragged_host():
+    return _mod("ragged")
+
+
 def mcem_dev():
     return _mod("mcem")
 

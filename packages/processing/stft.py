@@ -61,7 +61,7 @@ def stft_pytorch(x,
     if center:
         x_ = torch.nn.functional.pad(x_[None, None], (nfft // 2, nfft // 2), mode=pad_mode)[0, 0]
     T = H.frame_count(x_.numel(), nfft, hop)
-    dev = x_.device if x_.is_cuda else H._device()
+    dev = x_.device if x_.is_cuda else _native.ragged_host().device()
     if win != 'hann':
         raise ValueError("stft_pytorch: only win='hann' is defined (as in the reference)")
     xin = x_.to(dev)
@@ -95,7 +95,7 @@ def istft_pytorch(Sxx,
         S = torch.view_as_complex(Sxx)                     # e.g. the real view stft_pytorch returned: frame-major memory, read in place
     else:
         S = torch.view_as_complex(Sxx.contiguous())
-    dev = S.device if S.is_cuda else H._device()
+    dev = S.device if S.is_cuda else _native.ragged_host().device()
     T = S.shape[1]
     ntot = nfft + hop * (T - 1)
     start = nfft // 2 if center else 0
@@ -158,7 +158,7 @@ def istft_many(Sxx_list,
             raise ValueError("istft: expected a [%d, T] spectrogram" % (1 + nfft // 2))
     # frame-major on the device, one copy: the rows of each S.T (free for a Fortran-ordered S, what stft() returns) end to end
     frames = np.concatenate([S.T for S in Ss]).astype(np.complex64, copy=False)
-    dev = H._device()
+    dev = _native.ragged_host().device()
     spec = H.SpecBatch(torch.from_numpy(np.ascontiguousarray(frames)).to(dev), [S.shape[1] for S in Ss], [0] * len(Ss), nfft, hop, center, 2)
     ys = H.istft_batch(spec, mls).numpy()
     out = []

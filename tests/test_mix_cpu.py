@@ -11,6 +11,7 @@ import mix_ref as XR
 
 X = importlib.import_module("disentangled-vae_amd.mix")
 H = importlib.import_module("disentangled-vae_amd.stft")
+R = importlib.import_module("disentangled-vae_amd.ragged")
 native = importlib.import_module("disentangled-vae_amd.native")
 GOLD = XR.load_golden(os.path.join(os.path.dirname(__file__), "golden", "mix_golden.npz"))
 
@@ -142,7 +143,7 @@ def test_the_batch_call_refuses_before_the_library_is_loaded(monkeypatch):
 
 def test_a_repeated_array_is_packed_once():
     a, b = np.zeros(100, np.float32), np.zeros(50, np.float32)
-    offs, lens, total = X._view([a, b, a, a])
+    offs, lens, total = R.view([a, b, a, a], dedupe=True)
     assert offs.tolist() == [0, 100, 0, 0] and lens.tolist() == [100, 50, 100, 100] and total == 150
 
 

@@ -22,7 +22,7 @@ import numpy as np, torch
 import mix_bounds as XB
 import mix_ref as XR
 X = importlib.import_module("disentangled-vae_amd.mix")
-H = importlib.import_module("disentangled-vae_amd.stft")
+R = importlib.import_module("disentangled-vae_amd.ragged")
 SNRS, INNER, PROCS, PEAK_BYTES_PER_S = [-10.0, -5.0, 0.0, 5.0], 20, 16, 8e12
 DATA = {}
 
@@ -94,11 +94,11 @@ def main():
     U = len(grid)
 
     # device time: inputs resident, the table and the factors made once on the host
-    s_view, b_view = X._view(grid), X._view(banks)
+    s_view, b_view = R.view(grid, dedupe=True), R.view(banks, dedupe=True)
     tab = X.mix_tables(s_view[:2], (b_view[0], b_view[1], index), starts, None, (s_view[2], b_view[2]))
     factors = X.snr_factors(snr)
-    dev = H._device()
-    s_buf, b_buf = X._buffer(grid, "speech", dev), X._buffer(banks, "noise_banks", dev)
+    dev = R.device()
+    s_buf, b_buf = (R.pack(x, f"mix_at_snr_batch: {name}", dev, R.ENTRY, dedupe=True) for x, name in ((grid, "speech"), (banks, "noise_banks")))
     outs = None
 
     def window():
