@@ -1,6 +1,6 @@
 // Optimizer step of the fused train step (scripts/training_M2.py:146-147: torch.optim.Adam.step on every parameter, torch's op order,
 // SURVEY.md 8a-13) and the refresh of the kernel-layout weight copies: the ONE definition behind
-//   * apply_kernel (train_fused.hip): one thread per parameter, its own launch -- the three-launch step, the multi-GPU step, flushes;
+//   * apply_kernel (train_wgrad.hip): one thread per parameter, its own launch -- the three-launch step, the multi-GPU step, flushes;
 //   * the folded tail of wgrad4_kernel (diagnostic builds);
 //   * the DEFERRED step (round 4): the update of step n runs in the opening of step n + 1's rows kernel, on the chain waves that would
 //     otherwise wait for the x tile (train_rows2.hip) -- two launches per step.

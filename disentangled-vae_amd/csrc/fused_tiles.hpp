@@ -1,4 +1,4 @@
-// MFMA tile machinery shared by the fused train step (train_fused.hip) and the MCEM kernels (mcem.hip):
+// MFMA tile machinery shared by the fused train step (train_rows*.hip, train_wgrad.hip) and the MCEM kernels (mcem.hip):
 // operand policies (exact fp32 / bf16), fragment-major weight fetch through buffer loads, the
 // register-ring GEMM block, C-tile epilogue helpers.
 #pragma once

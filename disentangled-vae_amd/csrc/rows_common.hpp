@@ -1,8 +1,10 @@
-// Device helpers shared by the rows kernels of the fused train step (train_fused.hip: 4-wave kernel; train_rows2.hip:
+// Device helpers shared by the rows kernels of the fused train step (train_rows1.hip: 4-wave kernel; train_rows2.hip:
 // 8-wave chain + helper kernel): reparametrisation noise, kernel arguments, tile loaders, LDS -> stash transposition.
+// At the foot: the launchers through which the host (train_fused.hip) reaches each rows kernel file.
 #pragma once
 #include "fused_tiles.hpp"
 #include "apply_types.hpp"
+#include "../../include/dvae_train.h"
 
 namespace dvae {
 namespace fused {
@@ -427,6 +429,21 @@ __device__ __forceinline__ void stash_from_lds(const typename P::T* U, int ldu, 
 }
 
 
+// ---- host side: what the launchers of the kernel files and the entry points (train_fused.hip) share
+static int current_device() { int dev = 0; (void)hipGetDevice(&dev); return dev < 0 || dev >= 64 ? 0 : dev; }      // (index of the per-device tables: 64 entries)
+static inline bool is_bf(int precision) { return precision == DVAE_PREC_BF16 || precision == DVAE_PREC_BF16X3; }
+// f(P{}) for the operand policy P of plan->precision
+template <typename F>
+static auto with_policy(int precision, F&& f) {
+    if (precision == DVAE_PREC_BF16X3) return f(PolX3{});
+    if (precision == DVAE_PREC_BF16) return f(PolBF16{});
+    return f(PolF32{});
+}
+
+// train_rows1.hip: the 4-wave rows kernel (every model but M2_DEC; fp32 operands, bf16 and bf16x3 in the diagnostic build), and the
+// noise_kernel that writes out the reparametrisation noise it draws in the kernel
+int launch_rows1(int precision, int model, int y_dim, const RowsArgs& a, int grid, hipStream_t s);
+int launch_noise(unsigned long long seed, unsigned long long step, int64_t B, float* out, hipStream_t s);
 // train_rows2.hip: the 8-wave chain + helper rows kernel (M1 / M2, bf16 and bf16x3 operand policies)
 int launch_rows2(int precision, int model, int y_dim, const RowsArgs& a, int grid, hipStream_t s);
 bool rows2_supported(int precision, int model);

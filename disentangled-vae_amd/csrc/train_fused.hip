@@ -1,26 +1,8 @@
-// Fused train step for the reference geometry (x 513, h [128,128], z 16, y 0/1/513):
-// see include/dvae_train.h for the three-launch structure.
-//
-// rows kernel (one 256-thread workgroup = 4 waves per 32-frame tile).  Every layer is computed
-// TRANSPOSED: out^T[features x frames] = W[features x K] * in^T[K x frames] on 32x32 MFMA tiles, so
-//   * the A operand is the weight matrix in its natural nn.Linear [out][in] order: each lane reads
-//     16 contiguous bytes of one weight row straight from L2 into VGPRs (a weight element is used
-//     by exactly one wave of the workgroup, so staging it in LDS would buy nothing);
-//   * the B operand is the previous layer's activations, kept in LDS as [frame][feature] rows whose
-//     stride is an odd number of 16-byte slots (conflict-free ds_read_b128);
-//   * in the C tile the lane is the frame and the 16 registers are features, so the tanh / exp /
-//     loss epilogues, the [frame][feature] LDS write for the next layer and the coalesced
-//     [feature][frame] stash store for the weight-gradient kernel all come out without shuffles;
-//   * the four waves split the output features; fp32 copies of the tanh outputs stay in registers
-//     for the backward pass of the same tile.
-// Two operand policies share the code: exact fp32 (v_mfma_f32_32x32x2_f32, parity mode) and bf16
-// operands with fp32 accumulation (v_mfma_f32_32x32x16_bf16, throughput mode).
-//
-// wgrad kernel: dW tile[32 out x 32 in] = sum over frames of dPre^T * In, both operands read from
-// the [feature][frame] stash with 16-byte loads (frame = MFMA k index), 4 tiles per workgroup,
-// the frame axis cut into `ksplit` slabs that the apply kernel sums in a fixed order
-// (deterministic: no atomics anywhere).  Bias gradients ride along as one extra MFMA against a
-// constant-one fragment.
+// Fused train step for the reference geometry (x 513, h [128,128], z 16, y 0/1/513): see include/dvae_train.h for the three-launch
+// structure.  This file is the host side only: plan and workspace layout, the tables the kernels read, the schedule of the
+// weight-gradient launch, the per-workspace state and every extern "C" entry point.  The kernels are reached through launchers:
+//   rows kernels             train_rows1.hip (4 waves), train_rows2.hip (8 waves), train_rows3.hip     -- rows_common.hpp
+//   weight gradients, apply  train_wgrad.hip                                                           -- wgrad_types.hpp
 #include <atomic>
 #include <mutex>
 #include <unordered_map>
@@ -30,1523 +12,13 @@
 #include <tuple>
 #include <math.h>
 #include <stdlib.h>
-#include <type_traits>
 #include "fused_tiles.hpp"
 #include "rows_common.hpp"
-#include "apply_common.hpp"
+#include "wgrad_types.hpp"
 #include "../../include/dvae_train.h"
 
 namespace dvae {
 namespace fused {
-
-
-// x[32 frames][f0 .. f0+127] (fp32) for the loss epilogue: 16 coalesced dwords per thread, addresses clamped
-template <typename RowOf>
-__device__ __forceinline__ void xt_issue(const float* __restrict__ x, int ldx, RowOf rowof, int f0, float (&xr)[16], int tid) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int idx = tid + 256 * i;
-        const int row = idx >> 7, col = idx & 127;
-        int cg = f0 + col; cg = cg < XD ? cg : XD - 1;
-        xr[i] = x[rowof(row) * ldx + cg];          // rowof clamps rows past the batch
-    }
-    __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void xt_commit(const float (&xr)[16], float* Xt, int ldxt, int64_t b0, int64_t B, int f0, int tid) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int idx = tid + 256 * i;
-        const int row = idx >> 7, col = idx & 127;
-        Xt[row * ldxt + col] = (f0 + col < XD && b0 + row < B) ? xr[i] : 0.f;
-    }
-}
-
-// "Classifier" (packages/models/models.py:41-63): 128-128-1 relu / relu / sigmoid MLP on the current tile, its
-// binary_cross_entropy against the frame label (utils.py:55-56) and the unit-scale backward, all on chip.
-// Used twice by M2_info (scripts/training_M2_info_vad.py:159-183): classifier on x, auxiliary net on z.
-// Each wave owns 32 hidden features; the 1-wide output layer is a VALU dot product reduced through LDS.
-struct SideArgs {
-    WRef W1, W2, W2t, W1t;          // W1t only when the gradient wrt the input is needed
-    unsigned s1, s1t;               // k-step strides of W1 / W1t
-    const float *b1, *b2, *w3;      // LDS tables
-    float b3;
-    float y, invB, eps;
-    bool live, need_dx;
-    float scale;                    // factor applied to the stashed pre-activation gradients (loss weight)
-    void *h1T, *h2T, *d1T, *d2T, *d3T;
-    int64_t Bp, b0, spl;
-};
-
-template <typename P, int K1STEPS>
-__device__ __forceinline__ void side_mlp(__amdgpu_buffer_rsrc_t wrs, const SideArgs& a, const typename P::T* in_row,
-                                         typename P::T* Ha, typename P::T* Hb, float* redbuf, int wave, int l31, int h,
-                                         unsigned S4, float& bce_frame, float& p_out, f32x16& dx) {
-    typedef typename P::T T;
-    constexpr int E = P::E, KS = P::KSTEP, LDH = Ld<T>::hh;
-    const int fb = 32 * wave;
-    const T* const Har = Ha + l31 * LDH + h * E;
-    const T* const Hbr = Hb + l31 * LDH + h * E;
-    f32x16 acc;
-    float bv[16], w3v[16], c1r[16], c2r[16], dv[16];
-    // layer 1
-    WPre<P, K1STEPS> w1;
-    wprefetch<P, K1STEPS>(w1, wrs, a.W1, a.s1);
-    zero_acc<P>(acc);
-    gemm_block<P, K1STEPS>(acc, w1, wrs, a.W1, in_row, a.s1);
-    WPre<P, HD / KS, P::PRE128> w2;
-    wprefetch<P, HD / KS>(w2, wrs, a.W2, S4);
-    bias16(a.b1, fb, h, bv);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) c1r[r] = fmaxf(acc[r] + bv[r], 0.f);
-    put_lds<P>(c1r, Ha, LDH, fb, l31, h);
-    __syncthreads();
-    // layer 2 + output dot product
-    zero_acc<P>(acc);
-    gemm_block<P, HD / KS>(acc, w2, wrs, a.W2, Har, S4, [&]() { stash_tile<P>(Ha, LDH, fb, (T*)a.h1T + (int64_t)wave * 32 * a.Bp, a.spl, a.b0, l31, h); });
-    WPre<P, HD / KS, P::PRE128> w2t;
-    wprefetch<P, HD / KS>(w2t, wrs, a.W2t, S4);
-    bias16(a.b2, fb, h, bv);
-    bias16(a.w3, fb, h, w3v);
-    float pd = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { c2r[r] = fmaxf(acc[r] + bv[r], 0.f); pd = fmaf(w3v[r], c2r[r], pd); }
-    put_lds<P>(c2r, Hb, LDH, fb, l31, h);
-    pd += __shfl_xor(pd, 32, 64);
-    if (h == 0) redbuf[wave * 32 + l31] = pd;
-    __syncthreads();
-    const float logit = redbuf[l31] + redbuf[32 + l31] + redbuf[64 + l31] + redbuf[96 + l31] + a.b3;
-    const float p = 1.f / (1.f + P::exp_(-logit));
-    p_out = p;
-    const float lp = P::log_(p + a.eps), lq = P::log_(1.f - p + a.eps);
-    bce_frame = a.live ? -(a.y * lp + (1.f - a.y) * lq) : 0.f;                              // utils.py:55-56, this frame's term
-    const float u = a.live ? -a.invB * (a.y / (p + a.eps) - (1.f - a.y) / (1.f - p + a.eps)) : 0.f;   // d BCE / d p
-    const float dpre3 = u * p * (1.f - p);
-    stash_tile<P>(Hb, LDH, fb, (T*)a.h2T + (int64_t)wave * 32 * a.Bp, a.spl, a.b0, l31, h);
-    if (wave == 0 && h == 0) {       // output pre-activation gradient: feature row 0 of a 32-row stash tile
-        T* d3 = (T*)a.d3T + (a.b0 / KS) * (64 * E) + (l31 / E) * 32 * E + (l31 % E);
-        const T d3h = P::cvt(dpre3 * a.scale);
-        *d3 = d3h;
-        if constexpr (P::NP == 2) d3[a.spl] = P::cvt(dpre3 * a.scale - (float)d3h);
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dv[r] = c2r[r] > 0.f ? w3v[r] * dpre3 : 0.f;            // dpre2 (unit scale)
-    put_lds<P>(dv, Ha, LDH, fb, l31, h);
-    __syncthreads();
-    // backward through layer 2
-    zero_acc<P>(acc);
-    gemm_block<P, HD / KS>(acc, w2t, wrs, a.W2t, Har, S4, [&]() { stash_tile<P>(Ha, LDH, fb, (T*)a.d2T + (int64_t)wave * 32 * a.Bp, a.spl, a.b0, l31, h, a.scale); });
-    WPre<P, HD / KS> w1t;
-    if (a.need_dx && wave == 0) wprefetch<P, HD / KS>(w1t, wrs, a.W1t, a.s1t);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dv[r] = c1r[r] > 0.f ? acc[r] : 0.f;                      // dpre1 (unit scale)
-    put_lds<P>(dv, Hb, LDH, fb, l31, h);
-    __syncthreads();
-    zero_acc<P>(dx);
-    if (a.need_dx && wave == 0) {
-        gemm_block<P, HD / KS>(dx, w1t, wrs, a.W1t, Hbr, a.s1t, [&]() { stash_tile<P>(Hb, LDH, fb, (T*)a.d1T + (int64_t)wave * 32 * a.Bp, a.spl, a.b0, l31, h, a.scale); });
-    } else {
-        stash_tile<P>(Hb, LDH, fb, (T*)a.d1T + (int64_t)wave * 32 * a.Bp, a.spl, a.b0, l31, h, a.scale);
-    }
-    __syncthreads();
-}
-
-template <typename P, int YP, bool YENC, bool INFO>
-__global__ __launch_bounds__(256, 1) void vae_rows_kernel(const RowsArgs g) {
-    typedef typename P::T T;
-    constexpr int E = P::E;
-    constexpr int KS = P::KSTEP;
-    constexpr int LDU = Ld<T>::u, LDH = Ld<T>::hh, LDZ = Ld<T>::z, LDX = Ld<T>::xt;
-    constexpr int LD1 = XP + (YENC ? YP : 0);           // W1 shadow row length
-    constexpr int LD3 = ZD + YP;                        // W3 shadow row length
-    constexpr bool Y513 = (YP == XP);                   // IBM labels: y has the same 513-column shape as x
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    T* U = reinterpret_cast<T*>(smem);
-    T* Ha = U + TB * LDU;
-    T* Hb = Ha + TB * LDH;
-    T* Zb = Hb + TB * LDH;
-    float* Xt = reinterpret_cast<float*>(U + P::NP * Ld<T>::act_elems);     // behind the operand plane(s).  XFULL: dense [32][513] fp32 x tile; else [32][129] slice
-    float* Bias = Xt + (P::XFULL ? Ld<T>::xf_floats : Ld<T>::xt_floats);
-    constexpr int OB1 = 0, OB2 = HD, OBMV = 2 * HD, OB3 = 2 * HD + 32, OB4 = 3 * HD + 32, OB5 = 4 * HD + 32;
-    // M2_info tables behind the VAE biases: bc1 bc2 wc3 ba1 ba2 wa3 (128 each), then bc3, ba3
-    constexpr int OI = Ld<T>::nbias, OBC1 = OI, OBC2 = OI + HD, OWC3 = OI + 2 * HD, OBA1 = OI + 3 * HD, OBA2 = OI + 4 * HD, OWA3 = OI + 5 * HD, OS3 = OI + 6 * HD;
-    __shared__ float red[16];
-    __shared__ float red2[128];
-    __shared__ int64_t rowsrc[TB];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, h = lane >> 5;
-    const int fb = 32 * wave;                           // this wave's feature block in 128-wide layers
-    // fragment-major weight copies: [k-step][row tile][lane][E] (k-step major: the fragments a wave keeps in
-    // flight then sit >= 4 KB apart and spread over the L2 channels); this wave's tile = wave in 128-row layers
-    constexpr int FB = 64 * E;                          // elements per (tile, k-step) block
-    // weight copies through ONE buffer descriptor: per-lane byte offset + wave-uniform (matrix, tile) offset
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(g.wcopy), 0, (int)g.wcopy_bytes, 0x00020000);
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    constexpr unsigned SZ = sizeof(T);
-    auto wbase = [&](const void* Wp, int tile, int ld) -> WRef {
-        const unsigned m = (unsigned)((const char*)Wp - (const char*)g.wcopy);
-        if (WFRAG) return WRef{lane * 16, m + (unsigned)tile * (FB * SZ), g.wpl_bytes};
-        return WRef{(int)((l31 * ld + h * E) * SZ), m + (unsigned)(32 * tile * ld) * SZ, g.wpl_bytes};
-    };
-    // byte strides between k-steps (4-tile, 1-tile and 17-tile matrices), between row tiles of W5s, and the
-    // byte offsets of the y k-blocks inside W1 / W3
-    constexpr unsigned S4 = (WFRAG ? 4 * FB : 2 * E) * SZ, S1 = (WFRAG ? FB : 2 * E) * SZ, S17 = (WFRAG ? NT_OUT * FB : 2 * E) * SZ;
-    constexpr unsigned TSTEP = (WFRAG ? FB : 32 * HD) * SZ;
-    constexpr unsigned KB1 = (WFRAG ? (XP / KS) * 4 * FB : XP) * SZ;
-    constexpr unsigned KB3 = (WFRAG ? (ZD / KS) * 4 * FB : ZD) * SZ;
-    const WRef W1r = wbase(g.W1s, wave_u, LD1);
-    const WRef W2r = wbase(g.W2s, wave_u, HD);
-    const WRef Wmvr = wbase(g.Wmvs, 0, HD);
-    const WRef W3r = wbase(g.W3s, wave_u, LD3);
-    const WRef W4r = wbase(g.W4s, wave_u, HD);
-    const WRef W5s = wbase(g.W5s, 0, HD);
-    const WRef W5tr = wbase(g.W5t, wave_u, NO);
-    const WRef W4tr = wbase(g.W4t, wave_u, HD);
-    const WRef W3ztr = wbase(g.W3zt, 0, HD);
-    const WRef Wmvtr = wbase(g.Wmvt, wave_u, 32);
-    const WRef W2tr = wbase(g.W2t, wave_u, HD);
-    auto woff = [](WRef r, unsigned bytes) { return WRef{r.voff, r.soff + bytes, r.pl}; };
-    const T* const Ur = U + l31 * LDU + h * E;
-    const T* const Har = Ha + l31 * LDH + h * E;
-    const T* const Hbr = Hb + l31 * LDH + h * E;
-    const T* const Zbr = Zb + l31 * LDZ + h * E;
-
-    double tot_rec = 0.0, tot_kl = 0.0, tot_bc = 0.0, tot_ba = 0.0;
-
-    // fp32 bias table -> LDS once (epilogues must not queue global loads behind the weight prefetch).
-    // The loads are issued here (clamped addresses instead of branches); the LDS stores wait until the first
-    // tile's x loads are in flight, so the kernel's first HBM round trip carries both.
-    constexpr int NB = (Ld<T>::nbias + 255) / 256;
-    float bvv[NB];
-#pragma unroll
-    for (int it = 0; it < NB; ++it) {
-        int i = tid + 256 * it;
-        i = i < Ld<T>::nbias ? i : Ld<T>::nbias - 1;
-        const float* src;
-        int k;
-        if (i < OB2) { src = g.b1; k = i; }
-        else if (i < OBMV) { src = g.b2; k = i - OB2; }
-        else if (i < OBMV + ZD) { src = g.bmu; k = i - OBMV; }
-        else if (i < OB3) { src = g.blv; k = i - OBMV - ZD; }
-        else if (i < OB4) { src = g.b3; k = i - OB3; }
-        else if (i < OB5) { src = g.b4; k = i - OB4; }
-        else if (i < OB5 + NO) { src = g.b5; k = i - OB5; k = k < XD ? k : XD - 1; }
-        else { src = g.w5last; k = i - OB5 - NO; }
-        bvv[it] = src[k];
-    }
-    auto store_bias_table = [&]() {
-#pragma unroll
-        for (int it = 0; it < NB; ++it) {
-            const int i = tid + 256 * it;
-            if (i < Ld<T>::nbias) Bias[i] = (i >= OB5 + XD && i < OB5 + NO) ? 0.f : bvv[it];
-        }
-        if (INFO) {
-            for (int i = tid; i < 6 * HD + 2; i += 256) {
-                float v;
-                const int q = i / HD, k = i - q * HD;
-                if (q == 0) v = g.bc1[k]; else if (q == 1) v = g.bc2[k]; else if (q == 2) v = g.wc3[k];
-                else if (q == 3) v = g.ba1[k]; else if (q == 4) v = g.ba2[k]; else if (q == 5) v = g.wa3[k];
-                else v = k == 0 ? g.bc3[0] : g.ba3[0];
-                Bias[OI + i] = v;
-            }
-        }
-    };
-    bool bias_pending = true;
-
-    for (int tile = blockIdx.x; tile < g.ntiles; tile += gridDim.x) {
-        const int64_t b0 = (int64_t)tile * TB;
-        const bool live = (b0 + l31) < g.B;             // this lane's frame exists
-        const bool full = (b0 + TB) <= g.B;
-        float rec_lane = 0.f, kl_lane = 0.f, bce_c = 0.f, bce_a = 0.f;
-        float y_l = 0.f;
-        // source row of the tile's frame r (clamped to the batch): identity, or through the gather table
-        if (g.rows != nullptr) {
-            __syncthreads();                                 // previous tile's readers are done with rowsrc
-            if (tid < TB) {
-                const int64_t bf = b0 + tid;
-                const int64_t br = bf < g.B ? bf : g.B - 1;
-                int64_t rr = g.rows[br];
-                if (rr < 0 || rr >= g.n_rows) { rr = 0; if (g.bad_rows && bf < g.B) atomicAdd(g.bad_rows, 1); }   // never dereference an out-of-range index
-                rowsrc[tid] = rr;
-            }
-            __syncthreads();
-        }
-        auto rowof = [&](int r) -> int64_t {
-            if (g.rows != nullptr) return rowsrc[r];
-            const int64_t br = b0 + r;
-            return br < g.B ? br : g.B - 1;
-        };
-        if (INFO) y_l = g.y[rowof(l31) * g.ldy];
-        f32x16 dzu;                                      // M2_info: d BCE_aux / d z (unit scale), wave 0
-        // per-iteration opaque copy of the thread id: stops the compiler from hoisting the ~70 per-thread
-        // staging addresses out of the tile loop (they would live across the whole loop and spill)
-        int tl = tid;
-        asm volatile("" : "+v"(tl));
-
-        DVAE_STAMP(0);
-        if (g.dbg && tid == 0) g.dbg[(size_t)blockIdx.x * 32 + 30] = clock64();
-        // reparametrisation noise of this lane's frame (wave 0 owns the latent tile): requested first,
-        // long before it is needed
-        float ep_r[8];
-        if (wave == 0) {
-            int64_t br = b0 + l31; br = br < g.B ? br : g.B - 1;
-            if (g.eps != nullptr) {
-                const f32x4 e0 = *reinterpret_cast<const f32x4*>(g.eps + br * ZD + 4 * h);
-                const f32x4 e1 = *reinterpret_cast<const f32x4*>(g.eps + br * ZD + 8 + 4 * h);
-#pragma unroll
-                for (int jq = 0; jq < 4; ++jq) { ep_r[jq] = live ? e0[jq] : 0.f; ep_r[4 + jq] = live ? e1[jq] : 0.f; }
-            } else {                                             // drawn here: no noise tensor, no extra launch
-                frame_noise8(g.rng_seed, (unsigned long long)br, g.rng_step, h, ep_r);
-#pragma unroll
-                for (int jq = 0; jq < 8; ++jq) ep_r[jq] = live ? ep_r[jq] : 0.f;
-            }
-        }
-        // ---------------- encoder layer 1: [x | y] -> h1 ----------------
-        WPre<P, XP / KS> w1x;
-        wprefetch<P, XP / KS>(w1x, wrs, W1r, S4);
-        const bool yfast = Y513 && g.fasty && full;
-        f32x4 yv[NQ513];
-        if (g.fastx && full) {
-            f32x4 xv[NQ513];
-            tile513_issue(g.x, rowof, xv, tl);
-            if constexpr (Y513 && P::EARLY_Y) {
-                if (yfast) tile513_issue(g.y, rowof, yv, tl);      // y tile in flight under the x commit and the x GEMM
-            }
-            if (bias_pending) { store_bias_table(); bias_pending = false; }
-            tile513_commit<P, XP>(xv, U, LDU, tl, P::XFULL ? Xt : nullptr);
-        } else {
-            if (bias_pending) { store_bias_table(); bias_pending = false; }
-            load_rows_to_lds<P>(g.x, g.ldx, XD, XP, b0, g.B, U, LDU, tl, rowof, P::XFULL ? Xt : nullptr);
-            if constexpr (Y513 && P::EARLY_Y) {
-                if (yfast) tile513_issue(g.y, rowof, yv, tl);
-            }
-        }
-        __syncthreads();
-        DVAE_STAMP(1);
-        f32x16 acc;
-        zero_acc<P>(acc);
-        gemm_block<P, XP / KS>(acc, w1x, wrs, W1r, Ur, S4, [&]() {
-            if (!(g.ablate & 2)) stash_from_lds<P>(U, LDU, XP, NO, (T*)g.xT, g.spl, g.Bp, b0, tl);
-        });
-        DVAE_STAMP(2);
-        if (INFO) {
-            const f32x16 acc_keep = acc;
-            SideArgs sa;
-            sa.W1 = wbase(g.Wc1s, wave_u, XP); sa.W2 = wbase(g.Wc2s, wave_u, HD); sa.W2t = wbase(g.Wc2t, wave_u, HD); sa.W1t = sa.W2t;
-            sa.s1 = S4; sa.s1t = S4; sa.b1 = Bias + OBC1; sa.b2 = Bias + OBC2; sa.w3 = Bias + OWC3; sa.b3 = Bias[OS3];
-            sa.y = y_l; sa.invB = g.invB; sa.eps = g.elbo_eps; sa.live = live; sa.need_dx = false; sa.scale = g.alpha;
-            sa.h1T = g.c1T; sa.h2T = g.c2T; sa.d1T = g.dc1T; sa.d2T = g.dc2T; sa.d3T = g.dc3T; sa.Bp = g.Bp; sa.b0 = b0; sa.spl = g.spl;
-            float pc; f32x16 dxc;
-            side_mlp<P, XP / KS>(wrs, sa, Ur, Ha, Hb, red2, wave, l31, h, S4, bce_c, pc, dxc);
-            acc = acc_keep;
-        }
-        WPre<P, HD / KS, P::PRE128> w2;
-        WPre<P, (YENC ? YP : 0) / KS> w1y;
-        if (YENC) wprefetch<P, (YENC ? YP : 0) / KS>(w1y, wrs, woff(W1r, KB1), S4);
-        else wprefetch<P, HD / KS>(w2, wrs, W2r, S4);
-        if (YP > 0) {
-            __syncthreads();
-            if (Y513 && yfast) {
-                if constexpr (!P::EARLY_Y) tile513_issue(g.y, rowof, yv, tl);
-                tile513_commit<P, XP>(yv, U, LDU, tl);
-            } else {
-                load_rows_to_lds<P>(g.y, g.ldy, g.ydim, YP, b0, g.B, U, LDU, tl, rowof);
-            }
-            __syncthreads();
-            if (YENC) {
-                gemm_block<P, (YENC ? YP : 0) / KS>(acc, w1y, wrs, woff(W1r, KB1), Ur, S4, [&]() {
-                    if (!(g.ablate & 2)) stash_from_lds<P>(U, LDU, YP, (YP + 31) / 32 * 32, (T*)g.yT, g.spl, g.Bp, b0, tl);
-                });
-                wprefetch<P, HD / KS>(w2, wrs, W2r, S4);
-            } else {
-                if (!(g.ablate & 2)) stash_from_lds<P>(U, LDU, YP, (YP + 31) / 32 * 32, (T*)g.yT, g.spl, g.Bp, b0, tl);
-            }
-        }
-        float h1r[16], bv[16];
-        DVAE_STAMP(3);
-        bias16(Bias + OB1, fb, h, bv);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) h1r[r] = P::tanh_(acc[r] + bv[r]);
-        put_lds<P>(h1r, Ha, LDH, fb, l31, h);
-        __syncthreads();
-
-        DVAE_STAMP(4);
-        // ---------------- encoder layer 2 ----------------
-        zero_acc<P>(acc);
-        gemm_block<P, HD / KS>(acc, w2, wrs, W2r, Har, S4, [&]() { DVAE_FSTAMP(16); stash_tile<P>(Ha, LDH, fb, (g.ablate & 1) ? nullptr : (T*)g.h1T + (int64_t)(wave) * 32 * g.Bp, g.spl, b0, l31, h); DVAE_FSTAMP(17); });
-        DVAE_FSTAMP(18);
-        WPre<P, HD / KS, P::PRE128> wmv;
-        WPre<P, ZD / KS> w3z;
-        if (wave == 0) wprefetch<P, HD / KS>(wmv, wrs, Wmvr, S1);
-        wprefetch<P, ZD / KS>(w3z, wrs, W3r, S4);
-        float h2r[16];
-        bias16(Bias + OB2, fb, h, bv);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) h2r[r] = P::tanh_(acc[r] + bv[r]);
-        DVAE_FSTAMP(19);
-        put_lds<P>(h2r, Hb, LDH, fb, l31, h);
-        DVAE_FSTAMP(20);
-        __syncthreads();
-
-        DVAE_STAMP(5);
-        // ---------------- heads + reparametrisation (wave 0): rows 0-15 mu, 16-31 log_var ----------------
-        float mu_r[8], lv_r[8], sd_r[8];
-        // the label block of decoder layer 1 (33 k-steps) does not depend on z: its first fragments are requested here,
-        // a whole phase ahead (three of the four waves idle through the heads anyway)
-        WPre<P, (YP > 0 ? YP : KS) / KS, P::PREBIG> w3y;
-        if (YP > 0) wprefetch<P, (YP > 0 ? YP : KS) / KS>(w3y, wrs, woff(W3r, KB3), S4);
-        if (wave == 0) {
-            zero_acc<P>(acc);
-            gemm_block<P, HD / KS>(acc, wmv, wrs, Wmvr, Hbr, S1, [&]() { stash_tile<P>(Hb, LDH, fb, (g.ablate & 1) ? nullptr : (T*)g.h2T + (int64_t)(wave) * 32 * g.Bp, g.spl, b0, l31, h); });
-            float zv[16];
-            bias16(Bias + OBMV, 0, h, bv);                          // rows 0-15 bmu, 16-31 blv
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                mu_r[r] = acc[r] + bv[r];
-                lv_r[r] = acc[r + 8] + bv[r + 8];
-                sd_r[r] = P::exp_(0.5f * lv_r[r]);                 // models.py:17
-                zv[r] = fmaf(sd_r[r], ep_r[r], mu_r[r]);           // models.py:20
-                zv[r + 8] = 0.f;
-                if (live) kl_lane += lv_r[r] - mu_r[r] * mu_r[r] - P::exp_(lv_r[r]);   // utils.py:75
-            }
-            // z block of the decoder input: features 0..15 valid, 16..31 zero
-            put_lds<P>(zv, Zb, LDZ, 0, l31, h);
-        } else {
-            stash_tile<P>(Hb, LDH, fb, (g.ablate & 1) ? nullptr : (T*)g.h2T + (int64_t)(wave) * 32 * g.Bp, g.spl, b0, l31, h);
-        }
-        __syncthreads();
-
-        DVAE_STAMP(6);
-        if (INFO) {
-            SideArgs sa;
-            sa.W1 = wbase(g.Wa1s, wave_u, ZD); sa.W2 = wbase(g.Wa2s, wave_u, HD); sa.W2t = wbase(g.Wa2t, wave_u, HD); sa.W1t = wbase(g.Wa1t, 0, HD);
-            sa.s1 = S4; sa.s1t = S1; sa.b1 = Bias + OBA1; sa.b2 = Bias + OBA2; sa.w3 = Bias + OWA3; sa.b3 = Bias[OS3 + 1];
-            sa.y = y_l; sa.invB = g.invB; sa.eps = g.elbo_eps; sa.live = live; sa.need_dx = true; sa.scale = g.gamma - g.beta;
-            sa.h1T = g.a1T; sa.h2T = g.a2T; sa.d1T = g.da1T; sa.d2T = g.da2T; sa.d3T = g.da3T; sa.Bp = g.Bp; sa.b0 = b0; sa.spl = g.spl;
-            float pa;
-            if (wave == 0) stash_tile<P>(Zb, LDZ, 0, (T*)g.zT, g.spl, b0, l31, h);
-            side_mlp<P, ZD / KS>(wrs, sa, Zbr, Ha, Hb, red2, wave, l31, h, S4, bce_a, pa, dzu);
-        }
-        // ---------------- decoder layer 1: [z | y] -> d1 ----------------
-        zero_acc<P>(acc);
-        gemm_block<P, ZD / KS>(acc, w3z, wrs, W3r, Zbr, S4, [&]() { if (!INFO && wave == 0) stash_tile<P>(Zb, LDZ, 0, (T*)g.zT, g.spl, b0, l31, h); });
-        WPre<P, HD / KS, P::PRE128> w4;
-        if (YP > 0) gemm_block<P, (YP > 0 ? YP : KS) / KS>(acc, w3y, wrs, woff(W3r, KB3), Ur, S4);
-        wprefetch<P, HD / KS>(w4, wrs, W4r, S4);
-        float d1r[16];
-        bias16(Bias + OB3, fb, h, bv);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) d1r[r] = P::tanh_(acc[r] + bv[r]);
-        put_lds<P>(d1r, Ha, LDH, fb, l31, h);
-        __syncthreads();
-
-        DVAE_STAMP(7);
-        // ---------------- decoder layer 2 ----------------
-        zero_acc<P>(acc);
-        gemm_block<P, HD / KS>(acc, w4, wrs, W4r, Har, S4, [&]() { stash_tile<P>(Ha, LDH, fb, (g.ablate & 1) ? nullptr : (T*)g.d1T + (int64_t)(wave) * 32 * g.Bp, g.spl, b0, l31, h); });
-        WPre<P, HD / KS, P::PRE128> w5;
-        wprefetch<P, HD / KS>(w5, wrs, woff(W5s, wave_u * TSTEP), S17);
-        float xr[16];
-        if (!P::XFULL) xt_issue(g.x, g.ldx, rowof, 0, xr, tl);
-        float d2r[16];
-        bias16(Bias + OB4, fb, h, bv);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) d2r[r] = P::tanh_(acc[r] + bv[r]);
-        put_lds<P>(d2r, Hb, LDH, fb, l31, h);
-        __syncthreads();
-
-        DVAE_STAMP(8);
-        // ---------------- output layer a = W5 d2 + b5, Itakura-Saito terms, da -> U ----------------
-        WPre<P, NO / KS> w5t;
-        // one 32-feature tile t of the output layer for this wave: GEMM, loss terms, da
-        auto out_tile = [&](int t, const float* xsrc, int xld, int xcol0, int xcmax) {
-            if (t == 4) DVAE_FSTAMP(21);
-            zero_acc<P>(acc);
-            const WRef wr = woff(W5s, (unsigned)t * TSTEP);
-            gemm_block<P, HD / KS>(acc, w5, wrs, wr, Hbr, S17, [&]() { if (t < 4) stash_tile<P>(Hb, LDH, fb, (g.ablate & 1) ? nullptr : (T*)g.d2T + (int64_t)(wave) * 32 * g.Bp, g.spl, b0, l31, h); });
-            if (t == 4) DVAE_FSTAMP(22);
-            if (t + 4 < (P::XFULL ? NT_OUT - 1 : NT_OUT)) wprefetch<P, HD / KS>(w5, wrs, woff(wr, 4 * TSTEP), S17);
-            else wprefetch<P, NO / KS>(w5t, wrs, W5tr, S4);
-            if (t == 4) DVAE_FSTAMP(23);
-            float da[16], b5v[16], xs[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {                       // all x reads up front: one LDS wait, not sixteen
-                int xc = xcol0 + feat_of(r, h); xc = xc < xcmax ? xc : xcmax;
-                xs[r] = xsrc[l31 * xld + xc];
-            }
-            bias16(Bias + OB5, 32 * t, h, b5v);
-            if (t == 4) DVAE_FSTAMP(24);
-            const float invB_l = live ? g.invB : 0.f;            // frames past B contribute nothing
-            if (t < NT_OUT - 1) {                                // all 32 features of the tile exist
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float a = acc[r] + b5v[r];
-                    const float xe = xs[r] * P::exp_(-a);        // x / r,  r = exp(a)  (models.py:122)
-                    rec_lane += xe - P::log_(xs[r] + g.elbo_eps) + a - 1.f;   // utils.py:74 (log r = a)
-                    da[r] = (1.f - xe) * invB_l;                 // d recon / d a
-                }
-            } else {                                             // last tile: features >= 513 are padding
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const bool ok = 32 * t + feat_of(r, h) < XD;
-                    const float a = acc[r] + b5v[r];
-                    const float xe = xs[r] * P::exp_(-a);
-                    const float term = xe - P::log_(xs[r] + g.elbo_eps) + a - 1.f;
-                    rec_lane += ok ? term : 0.f;
-                    da[r] = ok ? (1.f - xe) * invB_l : 0.f;
-                }
-            }
-            if (t == 4) DVAE_FSTAMP(25);
-            put_lds<P>(da, U, LDU, 32 * t, l31, h);
-            if (t == 4) DVAE_FSTAMP(26);
-        };
-        if (P::XFULL) {
-            // the fp32 x tile is resident in LDS ([frame][513], odd stride: conflict-free): no barriers here.
-            // 16 full tiles = 4 per wave.  The 17th tile holds ONE real feature (bin 512): a whole MFMA tile and
-            // epilogue round for it would be a fifth round for wave 0; wave 3 does it as a 128-term dot product instead.
-#pragma unroll 1
-            for (int t = wave_u; t < NT_OUT - 1; t += 4) out_tile(t, Xt, XD, 32 * t, XD - 1);
-            if (wave_u == 3) {
-                const float* wl = Bias + OB5 + NO + 64 * h;                 // this half's 64 weights (LDS broadcast reads)
-                const T* drow = Hb + l31 * LDH + 64 * h;
-                float s = 0.f;
-#pragma unroll
-                for (int c = 0; c < 64 / E; ++c) {
-                    const typename P::Frag dv = *reinterpret_cast<const typename P::Frag*>(drow + c * E);
-#pragma unroll
-                    for (int j = 0; j < E; j += 4) {
-                        const f32x4 wv = *reinterpret_cast<const f32x4*>(wl + c * E + j);
-                        s = fmaf((float)dv[j], wv[0], s); s = fmaf((float)dv[j + 1], wv[1], s);
-                        s = fmaf((float)dv[j + 2], wv[2], s); s = fmaf((float)dv[j + 3], wv[3], s);
-                    }
-                }
-                s += __shfl_xor(s, 32, 64);
-                const float a = s + Bias[OB5 + XD - 1];
-                const float xv512 = Xt[l31 * XD + XD - 1];
-                const float xe = xv512 * P::exp_(-a);
-                if (h == 0) rec_lane += xe - P::log_(xv512 + g.elbo_eps) + a - 1.f;
-                const float da512 = live ? (1.f - xe) * g.invB : 0.f;
-                // columns 512 .. 543 of this frame's da row: the value, then 31 zeros (16 bf16 = 2 fragments per half)
-                typename P::Frag z0, z1;
-#pragma unroll
-                for (int j = 0; j < E; ++j) { z0[j] = P::cvt(0.f); z1[j] = P::cvt(0.f); }
-                if (h == 0) z0[0] = P::cvt(da512);
-                T* urow = U + l31 * LDU + (XD - 1) + 16 * h;
-                *reinterpret_cast<typename P::Frag*>(urow) = z0;
-                *reinterpret_cast<typename P::Frag*>(urow + E) = z1;
-            }
-            __syncthreads();
-        } else {
-#pragma unroll 1
-            for (int it = 0; it < (NT_OUT + 3) / 4; ++it) {
-                xt_commit(xr, Xt, LDX, b0, g.B, 128 * it, tl);
-                __syncthreads();
-                if (it + 1 < (NT_OUT + 3) / 4) xt_issue(g.x, g.ldx, rowof, 128 * (it + 1), xr, tl);
-                const int t = 4 * it + wave_u;
-                if (t < NT_OUT) out_tile(t, Xt, LDX, 32 * wave, 127);
-                __syncthreads();
-            }
-        }
-
-        DVAE_STAMP(9);
-        // ---------------- backward: d2 <- da ----------------
-        zero_acc<P>(acc);
-        gemm_block<P, NO / KS>(acc, w5t, wrs, W5tr, Ur, S4, [&]() {
-            for (int t = wave; t < NT_OUT; t += 4) stash_tile<P>(U, LDU, 32 * t, (g.ablate & 1) ? nullptr : (T*)g.daT + (int64_t)(t) * 32 * g.Bp, g.spl, b0, l31, h);
-        });
-        WPre<P, HD / KS, P::PRE128> w4t;
-        wprefetch<P, HD / KS>(w4t, wrs, W4tr, S4);
-        float dv[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dv[r] = acc[r] * (1.f - d2r[r] * d2r[r]);
-        put_lds<P>(dv, Ha, LDH, fb, l31, h);
-        __syncthreads();
-
-        DVAE_STAMP(10);
-        // ---------------- backward: d1 <- dpre_d2 ----------------
-        zero_acc<P>(acc);
-        gemm_block<P, HD / KS>(acc, w4t, wrs, W4tr, Har, S4, [&]() { stash_tile<P>(Ha, LDH, fb, (g.ablate & 1) ? nullptr : (T*)g.dd2T + (int64_t)(wave) * 32 * g.Bp, g.spl, b0, l31, h); });
-        WPre<P, HD / KS, P::PRE128> w3zt;
-        WPre<P, 32 / KS> wmvt;
-        if (wave == 0) wprefetch<P, HD / KS>(w3zt, wrs, W3ztr, S1);
-        wprefetch<P, 32 / KS>(wmvt, wrs, Wmvtr, S4);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dv[r] = acc[r] * (1.f - d1r[r] * d1r[r]);
-        put_lds<P>(dv, Hb, LDH, fb, l31, h);
-        __syncthreads();
-
-        DVAE_STAMP(11);
-        // ---------------- backward: z <- dpre_d1 (wave 0), then dmu / dlogvar ----------------
-        if (wave == 0) {
-            zero_acc<P>(acc);
-            gemm_block<P, HD / KS>(acc, w3zt, wrs, W3ztr, Hbr, S1, [&]() { stash_tile<P>(Hb, LDH, fb, (g.ablate & 1) ? nullptr : (T*)g.dd1T + (int64_t)(wave) * 32 * g.Bp, g.spl, b0, l31, h); });
-            float dml[16];
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const float dz = INFO ? acc[r] - g.beta * dzu[r] : acc[r];     // enc_loss = ELBO + alpha*clf - beta*BCE(aux(z), y)
-                dml[r] = live ? dz + mu_r[r] * g.invB : 0.f;                                                   // dmu
-                dml[r + 8] = live ? dz * ep_r[r] * (0.5f * sd_r[r]) - 0.5f * g.invB * (1.f - P::exp_(lv_r[r])) : 0.f;   // dlogvar
-            }
-            put_lds<P>(dml, Zb, LDZ, 0, l31, h);
-        } else {
-            stash_tile<P>(Hb, LDH, fb, (g.ablate & 1) ? nullptr : (T*)g.dd1T + (int64_t)(wave) * 32 * g.Bp, g.spl, b0, l31, h);
-        }
-        __syncthreads();
-
-        DVAE_STAMP(12);
-        // ---------------- backward: h2 <- [dmu | dlogvar] ----------------
-        zero_acc<P>(acc);
-        gemm_block<P, 32 / KS>(acc, wmvt, wrs, Wmvtr, Zbr, S4, [&]() { if (wave == 0) stash_tile<P>(Zb, LDZ, 0, (T*)g.dmlvT, g.spl, b0, l31, h); });
-        WPre<P, HD / KS, P::PRE128> w2t;
-        wprefetch<P, HD / KS>(w2t, wrs, W2tr, S4);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dv[r] = acc[r] * (1.f - h2r[r] * h2r[r]);
-        put_lds<P>(dv, Ha, LDH, fb, l31, h);
-        __syncthreads();
-
-        DVAE_STAMP(13);
-        // ---------------- backward: h1 <- dpre_h2 (inputs are data: stop here) ----------------
-        zero_acc<P>(acc);
-        gemm_block<P, HD / KS>(acc, w2t, wrs, W2tr, Har, S4, [&]() { stash_tile<P>(Ha, LDH, fb, (g.ablate & 1) ? nullptr : (T*)g.dh2T + (int64_t)(wave) * 32 * g.Bp, g.spl, b0, l31, h); });
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dv[r] = acc[r] * (1.f - h1r[r] * h1r[r]);
-        put_lds<P>(dv, Hb, LDH, fb, l31, h);
-        stash_tile<P>(Hb, LDH, fb, (g.ablate & 1) ? nullptr : (T*)g.dh1T + (int64_t)(wave) * 32 * g.Bp, g.spl, b0, l31, h);
-
-        DVAE_STAMP(14);
-        // ---------------- per-tile loss sums ----------------
-        if (!live) rec_lane = 0.f;
-        const float rs = wave_sum(rec_lane), ks = wave_sum(kl_lane);
-        if (lane == 0) { red[wave] = rs; red[4 + wave] = ks; }
-        if (INFO && wave == 0) {
-            const float bcs = wave_sum(h == 0 ? bce_c : 0.f), bas = wave_sum(h == 0 ? bce_a : 0.f);
-            if (lane == 0) { red[8] = bcs; red[9] = bas; }
-        }
-        __syncthreads();
-        if (tid == 0) {
-            tot_rec += (double)red[0] + (double)red[1] + (double)red[2] + (double)red[3];
-            tot_kl += -0.5 * (double)red[4];
-            if (INFO) { tot_bc += (double)red[8]; tot_ba += (double)red[9]; }
-        }
-        __syncthreads();
-    }
-    DVAE_STAMP(15);
-    if (g.dbg && tid == 0) g.dbg[(size_t)blockIdx.x * 32 + 31] = clock64();
-    if (tid == 0) {
-        g.partials[4 * blockIdx.x] = tot_rec;
-        g.partials[4 * blockIdx.x + 1] = tot_kl;
-        g.partials[4 * blockIdx.x + 2] = tot_bc;
-        g.partials[4 * blockIdx.x + 3] = tot_ba;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// One wave = one 2x2 group of 32x32 MFMA tiles (64 output features x 64 input features of one
-// layer): per k-step it loads 2 + 2 operand fragments and issues 4 MFMAs, halving the bytes per
-// FLOP of a single-tile wave.  Missing halves (odd tile counts, 16-row heads) are null.
-struct GroupDesc {
-    const void* A[2];        // stash rows of dPre^T (32 output features each); A[1] may be null
-    const void* Bm[2];       // stash rows of In^T (32 input features each); Bm[1] may be null
-    int64_t out_off[2][2];   // float offset of tile (i, j) element (0, 0) in a gradient slab
-    int64_t bias_off[2];     // float offset of the bias gradient rows of A block i, -1 = none
-    int32_t ldo[2];          // row stride of the destination tensor of A block i
-    int32_t mvalid[2];
-    int32_t nvalid[2];
-    int32_t split16;         // A block 0 holds two 16-row tensors (mu | log_var heads): rows >= 16 go to the *_hi targets
-    int32_t ldo_hi;
-    int64_t out_off_hi[2];
-    int64_t bias_off_hi;
-};
-
-template <typename P, bool A1, bool B1>
-__device__ __forceinline__ void wgrad_body(const GroupDesc& d, int64_t kbeg, int64_t kend, int64_t Bp, int64_t spl, float* __restrict__ slab,
-                                           int l31, int h) {
-    typedef typename P::T T;
-    typedef typename P::Frag Frag;
-    constexpr int E = P::E, KS = P::KSTEP, NP = P::NP;
-    const int lane = h * 32 + l31;
-    constexpr int FB = 64 * E;                              // elements per (feature tile, k-step) block
-    const T* a0p = (const T*)d.A[0] + lane * E;
-    const T* a1p = A1 ? (const T*)d.A[1] + lane * E : a0p;
-    const T* b0p = (const T*)d.Bm[0] + lane * E;
-    const T* b1p = B1 ? (const T*)d.Bm[1] + lane * E : b0p;
-    const bool bias0 = d.bias_off[0] >= 0, bias1 = A1 && d.bias_off[1] >= 0;
-    f32x16 c00, c01, c10, c11, cb0, cb1;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { c00[i] = 0.f; c01[i] = 0.f; c10[i] = 0.f; c11[i] = 0.f; cb0[i] = 0.f; cb1[i] = 0.f; }
-    const Frag one = P::ones();
-    const int64_t sbeg = kbeg / KS, send = kend / KS;       // k-steps of this frame slice
-    // The stash was written once by the previous kernel: these are cold HBM/MALL reads (~2 us round trip).
-    // A ring of RD k-steps per operand keeps 4 * RD (x planes) 1-KB loads in flight per wave; the slot an MFMA group has
-    // consumed is re-requested RD steps ahead (clamped on the last lap: a harmless reload, no branch).
-    constexpr int RD = P::WRING;
-    Frag a0[RD][NP], a1[RD][NP], b0[RD][NP], b1[RD][NP];
-    auto ldp = [&](Frag (&f)[NP], const T* p, int64_t sk) {
-        f[0] = *reinterpret_cast<const Frag*>(p + sk * FB);
-        if constexpr (NP == 2) f[1] = *reinterpret_cast<const Frag*>(p + spl + sk * FB);
-    };
-#pragma unroll
-    for (int i = 0; i < RD; ++i) {
-        int64_t sk = sbeg + i; sk = sk < send ? sk : send - 1;
-        ldp(a0[i], a0p, sk);
-        ldp(b0[i], b0p, sk);
-        if (A1) ldp(a1[i], a1p, sk);
-        if (B1) ldp(b1[i], b1p, sk);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll 1
-    for (int64_t sk = sbeg; sk < send; sk += RD) {
-#pragma unroll
-        for (int i = 0; i < RD; ++i) {
-            if (sk + i < send) {                            // wave-uniform: slices are multiples of RD steps except the tail
-                mmap<P>(c00, a0[i], b0[i]);
-                if (B1) mmap<P>(c01, a0[i], b1[i]);
-                if (A1) mmap<P>(c10, a1[i], b0[i]);
-                if (A1 && B1) mmap<P>(c11, a1[i], b1[i]);
-                if (bias0) { P::mma(cb0, a0[i][0], one); if constexpr (NP == 2) P::mma(cb0, a0[i][1], one); }
-                if (A1) { if (bias1) { P::mma(cb1, a1[i][0], one); if constexpr (NP == 2) P::mma(cb1, a1[i][1], one); } }
-            }
-            int64_t sn = sk + RD + i; sn = sn < send ? sn : send - 1;
-            ldp(a0[i], a0p, sn);
-            ldp(b0[i], b0p, sn);
-            if (A1) ldp(a1[i], a1p, sn);
-            if (B1) ldp(b1[i], b1p, sn);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = feat_of(r, h);
-        if (row < d.mvalid[0]) {
-            const bool hi = d.split16 && row >= 16;
-            const int rr = hi ? row - 16 : row;
-            const int ldo = hi ? d.ldo_hi : d.ldo[0];
-            if (l31 < d.nvalid[0]) slab[(hi ? d.out_off_hi[0] : d.out_off[0][0]) + (int64_t)rr * ldo + l31] = c00[r];
-            if (B1) { if (l31 < d.nvalid[1]) slab[(hi ? d.out_off_hi[1] : d.out_off[0][1]) + (int64_t)rr * ldo + l31] = c01[r]; }
-            if (bias0 && l31 == 0) slab[(hi ? d.bias_off_hi : d.bias_off[0]) + rr] = cb0[r];
-        }
-        if (A1) {
-            if (row < d.mvalid[1]) {
-                if (l31 < d.nvalid[0]) slab[d.out_off[1][0] + (int64_t)row * d.ldo[1] + l31] = c10[r];
-                if (B1) { if (l31 < d.nvalid[1]) slab[d.out_off[1][1] + (int64_t)row * d.ldo[1] + l31] = c11[r]; }
-                if (bias1 && l31 == 0) slab[d.bias_off[1] + row] = cb1[r];
-            }
-        }
-    }
-}
-
-// grid.x = workgroups * ksplit with the k-slice as the FAST index: consecutive workgroups (dealt
-// round-robin to the 8 XCDs) work on different frame slices, so each XCD's L2 mostly holds one
-// slice of the stash.  blockDim.x / 64 groups per workgroup.
-#ifndef DVAE_WGRAD_OCC
-#define DVAE_WGRAD_OCC 1
-#endif
-template <typename P>
-__global__ __launch_bounds__(256, DVAE_WGRAD_OCC) void wgrad_kernel(const GroupDesc* __restrict__ groups, int ngroups, int ksplit, int64_t Bp,
-                                                    int64_t spl, int64_t kper, float* __restrict__ slabs, int64_t slab_stride) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int l31 = lane & 31, h = lane >> 5;
-    const int slice = blockIdx.x % ksplit, wg = blockIdx.x / ksplit;
-    const int gi = wg * (blockDim.x >> 6) + wave;
-    if (gi >= ngroups) return;
-    const GroupDesc d = groups[gi];
-    const int64_t kbeg = (int64_t)slice * kper;
-    int64_t kend = kbeg + kper;
-    if (kend > Bp) kend = Bp;
-    float* slab = slabs + (int64_t)slice * slab_stride;
-    const bool a1 = d.A[1] != nullptr, b1 = d.Bm[1] != nullptr;
-    if (a1 && b1) wgrad_body<P, true, true>(d, kbeg, kend, Bp, spl, slab, l31, h);
-    else if (a1) wgrad_body<P, true, false>(d, kbeg, kend, Bp, spl, slab, l31, h);
-    else if (b1) wgrad_body<P, false, true>(d, kbeg, kend, Bp, spl, slab, l31, h);
-    else wgrad_body<P, false, false>(d, kbeg, kend, Bp, spl, slab, l31, h);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Weight gradients, workgroup-blocked: one 256-thread workgroup owns a 4 x 4 block of 32 x 32 tiles (128 output x 128 input
-// features of one layer), wave (wr, wc) the 2 x 2 group {2wr, 2wr+1} x {2wc, 2wc+1} of it.  The block's 4 + 4 operand tiles
-// are staged ONCE per k-step in LDS and shared by the four waves: the fragment-major stash tile of one k-step is 1 KB in
-// exactly the lane-linear order a direct-to-LDS load writes (LDS address = wave-uniform base + lane * 16), so a fragment
-// costs one `global_load_lds_dwordx4` and no registers.  A ring of NSTG stages x 2 k-steps keeps (NSTG - 1) stages in flight
-// across one raw workgroup barrier per stage (counted vmcnt, never 0: cdna_hip_programming.md "Pipelining across barriers").
-// Against the register-ring kernel above (every wave loads its own 2 + 2 fragments: each stash line crosses L2 -> CU 3.7
-// times) the operand traffic halves and the in-flight bytes no longer cost registers.
-struct BlockDesc {
-    const void* At[4];       // the block's A tiles (null = absent)
-    const void* Bt[4];
-    GroupDesc g[4];          // per wave (wr * 2 + wc): destinations of its 2 x 2 group; A[0] == null: nothing to do
-};
-
-#ifdef DVAE_DIAG
-template <typename P> struct WgLds {
-    static constexpr int KPS = 2;                                   // k-steps per stage
-    static constexpr int NSTG = 4;
-    static constexpr int FRAG = 1024;                               // bytes of one (tile, plane, k-step) fragment block
-    static constexpr int STAGE = 8 * P::NP * KPS * FRAG;
-    static constexpr int BYTES = NSTG * STAGE;
-    static constexpr int LOADS = 2 * P::NP * KPS;                   // direct-to-LDS loads per wave and stage (one A slot + one B slot)
-};
-
-template <typename P>
-__global__ __launch_bounds__(256, 1) void wgrad_lds_kernel(const BlockDesc* __restrict__ blocks, int nblocks, int ksplit, int64_t Bp,
-                                                           int64_t spl, int64_t kper, float* __restrict__ slabs, int64_t slab_stride) {
-    typedef typename P::T T;
-    typedef typename P::Frag Frag;
-    typedef WgLds<P> W;
-    constexpr int E = P::E, KS = P::KSTEP, NP = P::NP, KPS = W::KPS, NSTG = W::NSTG;
-    constexpr int FB = 64 * E;
-    extern __shared__ __attribute__((aligned(16))) char wsm[];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int l31 = lane & 31, h = lane >> 5;
-    const int slice = blockIdx.x % ksplit, bi = blockIdx.x / ksplit;
-    if (bi >= nblocks) return;
-    const BlockDesc& bd = blocks[bi];
-    const GroupDesc d = bd.g[wave];
-    const int64_t kbeg = (int64_t)slice * kper;
-    int64_t kend = kbeg + kper;
-    if (kend > Bp) kend = Bp;
-    const int64_t sbeg = kbeg / KS, send = kend / KS;                 // k-steps of this frame slice
-    const int nst = (int)((send - sbeg + KPS - 1) / KPS);             // stages
-    float* slab = slabs + (int64_t)slice * slab_stride;
-    // this wave stages tile slots `wave` (an A tile) and 4 + `wave` (a B tile); absent tiles reload the block's first A tile so
-    // that every wave issues the same number of loads per stage (the vmcnt counts below are immediates)
-    const T* src[2];
-    src[0] = (const T*)(bd.At[wave] ? bd.At[wave] : bd.At[0]);
-    src[1] = (const T*)(bd.Bt[wave] ? bd.Bt[wave] : bd.At[0]);
-    auto issue = [&](int st) {                                        // stage st -> ring slot st % NSTG
-        char* base = wsm + (st % NSTG) * W::STAGE;
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl)
-#pragma unroll
-                for (int kk = 0; kk < KPS; ++kk) {
-                    int64_t sk = sbeg + (int64_t)st * KPS + kk; sk = sk < send ? sk : send - 1;   // past the slice: a harmless reload into a free slot
-                    const T* gp = src[q] + pl * spl + sk * FB + lane * E;
-                    char* lp = base + (((q * 4 + wave) * NP + pl) * KPS + kk) * W::FRAG;
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp, (__attribute__((address_space(3))) void*)lp, 16, 0, 0);
-                }
-    };
-    f32x16 c00, c01, c10, c11, cb0, cb1;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { c00[i] = 0.f; c01[i] = 0.f; c10[i] = 0.f; c11[i] = 0.f; cb0[i] = 0.f; cb1[i] = 0.f; }
-    const bool have = d.A[0] != nullptr;
-    const bool A1 = d.A[1] != nullptr, B1 = d.Bm[1] != nullptr;
-    const bool bias0 = have && d.bias_off[0] >= 0, bias1 = A1 && d.bias_off[1] >= 0;
-    const Frag one = P::ones();
-    const int wr = wave >> 1, wc = wave & 1;
-#pragma unroll
-    for (int st = 0; st < NSTG - 1; ++st) issue(st);
-    for (int st = 0; st < nst; ++st) {
-        // stage st has landed for this wave's loads once at most (NSTG - 2) later stages are outstanding; the barrier extends that
-        // to every wave's loads and says that everybody has finished reading stage st - 1, whose slot the next issue overwrites
-        if constexpr (W::LOADS * (NSTG - 2) == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if constexpr (W::LOADS * (NSTG - 2) == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_barrier" ::: "memory");
-        issue(st + NSTG - 1);
-        const char* base = wsm + (st % NSTG) * W::STAGE;
-#pragma unroll
-        for (int kk = 0; kk < KPS; ++kk) {
-            if (sbeg + (int64_t)st * KPS + kk >= send) break;         // wave-uniform tail
-            auto frag = [&](int slot, int pl) -> Frag {
-                return *reinterpret_cast<const Frag*>(base + ((slot * NP + pl) * KPS + kk) * W::FRAG + lane * 16);
-            };
-            Frag a0[NP], a1[NP], b0[NP], b1[NP];
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl) { a0[pl] = frag(2 * wr, pl); a1[pl] = frag(2 * wr + 1, pl); b0[pl] = frag(4 + 2 * wc, pl); b1[pl] = frag(5 + 2 * wc, pl); }
-            if (have) {
-                mmap<P>(c00, a0, b0);
-                if (B1) mmap<P>(c01, a0, b1);
-                if (A1) mmap<P>(c10, a1, b0);
-                if (A1 && B1) mmap<P>(c11, a1, b1);
-                if (bias0) { P::mma(cb0, a0[0], one); if constexpr (NP == 2) P::mma(cb0, a0[1], one); }
-                if (bias1) { P::mma(cb1, a1[0], one); if constexpr (NP == 2) P::mma(cb1, a1[1], one); }
-            }
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // the clamped tail loads must land before the LDS is released
-    if (!have) return;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = feat_of(r, h);
-        if (row < d.mvalid[0]) {
-            const bool hi = d.split16 && row >= 16;
-            const int rr = hi ? row - 16 : row;
-            const int ldo = hi ? d.ldo_hi : d.ldo[0];
-            if (l31 < d.nvalid[0]) slab[(hi ? d.out_off_hi[0] : d.out_off[0][0]) + (int64_t)rr * ldo + l31] = c00[r];
-            if (B1) { if (l31 < d.nvalid[1]) slab[(hi ? d.out_off_hi[1] : d.out_off[0][1]) + (int64_t)rr * ldo + l31] = c01[r]; }
-            if (bias0 && l31 == 0) slab[(hi ? d.bias_off_hi : d.bias_off[0]) + rr] = cb0[r];
-        }
-        if (A1) {
-            if (row < d.mvalid[1]) {
-                if (l31 < d.nvalid[0]) slab[d.out_off[1][0] + (int64_t)row * d.ldo[1] + l31] = c10[r];
-                if (B1) { if (l31 < d.nvalid[1]) slab[d.out_off[1][1] + (int64_t)row * d.ldo[1] + l31] = c11[r]; }
-                if (bias1 && l31 == 0) slab[d.bias_off[1] + row] = cb1[r];
-            }
-        }
-    }
-}
-#endif  // DVAE_DIAG
-
-// ---------------------------------------------------------------------------------------------
-// Weight gradients, third form (default): one 256-thread workgroup = one 4 x 4 block of 32 x 32 tiles (128 output x 128 input
-// features of a layer) x one frame slice, ONE workgroup per CU.  EVERY wave owns the whole 4 x 4 block (256 accumulator
-// registers: the kernel runs at one wave per SIMD and has 512) on a QUARTER of the slice's frames: per k-step a wave loads 4 + 4
-// operand fragments and issues 16 tile products, so a byte pulled into the CU feeds twice the MFMAs of the 2 x 2 register-ring
-// kernel above (the measured bound there: ~55 GB/s of operand fragments per CU, 335 MB per launch, at 2.6 x the MFMA time).
-// The four partial blocks meet in LDS as a reduce-scatter in a fixed order (deterministic): wave w finishes and stores A row w.  Bias gradients are in-lane sums of the A fragments (a frame
-// sum needs no MFMA: one fp32 register per A tile instead of a 16-register accumulator against a constant-one operand).
-struct Block4 {
-    const void* At[4];       // stash rows of dPre^T, 32 output features each (null = absent; tiles are contiguous from 0)
-    const void* Bt[4];       // stash rows of In^T, 32 input features each
-    int64_t a_off[4];        // float offset, in a gradient slab, of (row 0 of A tile i, column 0) of its tensor
-    int64_t bias_off[4];     // float offset of the bias-gradient rows of A tile i, -1 = none (only a layer's first B column carries them)
-    int32_t ldo[4];          // row stride of A tile i's tensor
-    int32_t mvalid[4];
-    int32_t bcol[4];         // column of B tile j in the tensor
-    int32_t nvalid[4];
-    int32_t split16;         // A tile 0 holds two 16-row tensors (mu | log_var heads): rows >= 16 go to the *_hi targets
-    int32_t ldo_hi;
-    int64_t a_off_hi;
-    int64_t bias_off_hi;
-    // B tiles that are columns of the step's INPUTS (x: raw = 1, labels: raw = 2): the kernel can take them straight from the fp32
-    // input matrix (the rows kernel then writes no stash for them); blocks never mix input tiles with stash tiles
-    int32_t raw, rncols;     // rncols: columns of the input matrix (513 / y_dim)
-    int32_t rcol[4];         // first column of B tile j in the input matrix
-    int32_t wt[4], bt[4], wt_hi, bt_hi;   // tensor numbers of A tile i's weight / bias rows (and of the rows >= 16 of a split tile): fold_tail
-    int32_t layer, pad_;                   // host side (w4_schedule): blocks of one emit() call share their A or their B tiles
-};
-
-// One workgroup of wgrad4_kernel = one item: block `block` over frames [kbeg, kend) into gradient slab `slice`.  The table is built on the
-// host (w4_build_items): which slices a block is cut into, and which XCD a workgroup index lands on, are scheduling decisions the kernel
-// only reads.  block < 0: an empty slot of the grid.
-struct W4Item { int32_t block, slice; int64_t kbeg, kend; };
-constexpr int W4_MAX_ITEMS = 4096;
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for_w(F&& f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for_w<I + 1, N>(f); }
-}
-
-// gradient-slab stores of the workgroup k-split kernel as buffer stores with cache-policy bits (W4_SLAB_AUX: gfx950 buffer aux, 0 = plain,
-// 16 = sc1 = write-through -- the slabs are read by the apply kernel: 73.1 -> 72.9 us per step, same box, alternating; non-temporal
-// loads of the once-read B fragments, also tried: 26.8 -> 31.6 us for the kernel)
-#ifndef W4_SLAB_AUX
-#define W4_SLAB_AUX 16
-#endif
-// the ragged-tile and bias stores of the slabs: write-through like the full-tile buffer stores (the folded optimizer tail reads the
-// slabs of other workgroups of the same launch and relies on every slab store being one)
-__device__ __forceinline__ void slab_store(float* p, float v) {
-#if W4_SLAB_AUX
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-    *p = v;
-#endif
-}
-template <typename P> struct Wg4 {
-#ifndef DVAE_W4RING_X3
-#define DVAE_W4RING_X3 2      // round 5, same box, alternating, three rounds: 25.6 us (2) against 27.2 (3) by hipEvent -- 32 instead of 48 KB per wave in flight
-#endif
-#ifndef DVAE_W4RING
-#define DVAE_W4RING 4
-#endif
-    static constexpr int RD = P::NP == 2 ? DVAE_W4RING_X3 : DVAE_W4RING;      // k-steps of operand fragments in flight per wave
-    static constexpr size_t BYTES = (size_t)(8 * 16) * 64 * 16 + 12 * 64 * 4;           // 8 exchange slots of one A row (4 tiles x 16 registers x 64 lanes x 4 B) + the bias sums
-};
-
-// NA x NB = tiles of the block this instantiation computes (absent tiles alias tile 0 and are masked at the store: their
-// descriptors carry mvalid / nvalid 0).  Compile-time shapes keep every operand load unconditional: a load under a run-time
-// branch makes hipcc's wait-count pass fall back to vmcnt(0) in front of the first MFMA of every k-step (the ring then holds one).
-struct RawIn { const float* x; const float* y; int ldx, ldy; int64_t B; };
-
-// BLO = false: the B tiles (labels) have no lo plane in this launch -- it is neither read nor multiplied
-// BIAS = false: no A tile of the block carries bias rows (only a layer's first B column does): no frame sums of the A fragments
-template <typename P, int NA, int NB, int RAW, bool BLO = true, bool BIAS = true>
-__device__ __forceinline__ void wgrad4_body(const Block4& bd, const Block4* __restrict__ bdg, char* wsm, int slice, int64_t Bp, int64_t spl, int64_t kbeg, int64_t kend_,
-                                            float* __restrict__ slabs, int64_t slab_stride, int lane, int wave, const RawIn& ri) {
-    typedef typename P::T T;
-    typedef typename P::Frag Frag;
-    typedef Wg4<P> W;
-    typedef const __attribute__((address_space(1))) char* gptr;
-    typedef const __attribute__((address_space(1))) Frag* gfrag;
-    // RAW: 0 = B tiles from the stash; 1 = from the fp32 input matrix by dword loads (any shape); 2 = from the input matrix through
-    // this wave's LDS staging rows (four full tiles): 16 frames x 128 columns per k-step arrive as eight 1 KB row loads, are split
-    // into (hi, lo) bf16, written as [frame][column] rows and read back transposed (ds_read_b64_tr_b16) into MFMA fragments.
-    // Mode 1 needs 32 loads per k-step and overruns the 6-bit vmcnt (at most 63 loads in flight: 1.5 k-steps); mode 2 needs 16.
-    constexpr int E = P::E, KS = P::KSTEP, NP = P::NP, RD = RAW == 2 ? 2 : W::RD;
-    constexpr int64_t FBB = 64 * 16;                                     // bytes of one (feature tile, k-step) fragment block
-    constexpr int SLD = 128 + 8, SPL = 16 * SLD;                         // staging rows: elements per frame row (odd number of 16-byte slots), per plane
-    const int l31 = lane & 31, h = lane >> 5;
-    // this wave's quarter of the slice's k-steps
-    int64_t kend = kend_;
-    if (kend > Bp) kend = Bp;
-    const int64_t s0 = kbeg / KS, s1 = kend / KS;
-    const int64_t nq = (s1 - s0 + 3) / 4;
-    int64_t sbeg = s0 + (int64_t)wave * nq, send = sbeg + nq;
-    if (send > s1) send = s1;
-    if (sbeg > send) sbeg = send;
-    gptr ap[NA], bp[NB];
-    // NA == 4: wave w holds the A tiles rotated by w (local row i = A tile (i + w) % 4), so that "the row this wave finishes and
-    // stores" is local row 0 for every wave and the reduce-scatter below is ONE instruction stream with compile-time register indices
-    const int rot = NA == 4 ? wave : 0;
-#pragma unroll
-    for (int k = 0; k < NA; ++k) { const void* q = NA == 4 ? bdg->At[(k + rot) & 3] : bd.At[k]; ap[k] = (gptr)(uintptr_t)(q ? q : bd.At[0]); }   // dynamic index: from the global copy (a scalar load), not a private-memory copy of bd
-#pragma unroll
-    for (int k = 0; k < NB; ++k) bp[k] = (gptr)(uintptr_t)(bd.Bt[k] ? bd.Bt[k] : bd.Bt[0]);
-    const int64_t plb = spl * (int64_t)sizeof(T);                          // bytes between the hi and lo planes
-    const unsigned loff = (unsigned)lane * 16u;
-    f32x16 c[NA][NB];
-#pragma unroll
-    for (int i = 0; i < NA; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) c[i][j][r] = 0.f;
-    float bs[4] = {0.f, 0.f, 0.f, 0.f};
-    Frag a[RD][NA][NP], b[RAW == 1 ? 1 : (RAW == 2 ? 1 : RD)][RAW == 1 ? 1 : NB][NP];   // RAW == 2: b[0] = the fragments of the k-step being multiplied
-    // RAW: the B fragments come from the fp32 input matrix itself -- lane (feature l31, frame half h) of tile j needs E consecutive
-    // frames of ONE column: E dword loads, each wave-instruction two 128-byte row segments; split into (hi, lo) when consumed.
-    // Frames past the batch repeat its last row (their dPre operand is zero), pad columns repeat the last column (never stored).
-    float braw[RAW == 1 ? RD : 1][RAW == 1 ? NB : 1][E];
-    f32x4 rawq[RAW == 2 ? RD : 1][RAW == 2 ? 8 : 1];                        // RAW == 2: row 2u + (lane >> 5), columns 4 (lane & 31) .. + 3 of the k-step's block
-    typedef const __attribute__((address_space(1))) float* gflt;
-    const gflt rsrc = (gflt)(uintptr_t)(RAW ? (bd.raw == 1 ? ri.x : ri.y) : nullptr);
-    const int rld = RAW ? (bd.raw == 1 ? ri.ldx : ri.ldy) : 0;
-    int rcolv[RAW == 1 ? NB : 1];
-    if constexpr (RAW == 1) {
-#pragma unroll
-        for (int k = 0; k < NB; ++k) { const int cc = bd.rcol[k] + l31; rcolv[k] = cc < bd.rncols ? cc : bd.rncols - 1; }
-    }
-    T* const stg = reinterpret_cast<T*>(wsm) + wave * (SPL * NP);          // RAW == 2: this wave's staging rows
-    const int rcol4 = RAW == 2 ? bd.rcol[0] + 4 * l31 : 0;
-    auto load = [&](auto sc, int64_t sk) __attribute__((always_inline)) {
-        constexpr int s = decltype(sc)::value;
-        const int64_t o = sk * FBB;
-#pragma unroll
-        for (int k = 0; k < NA; ++k) {
-            a[s][k][0] = *(gfrag)(ap[k] + o + loff);
-            if constexpr (NP == 2) a[s][k][1] = *(gfrag)(ap[k] + plb + o + loff);
-        }
-        if constexpr (RAW == 1) {
-            const int64_t f0 = sk * KS + h * E;
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                int64_t fr = f0 + e; fr = fr < ri.B ? fr : ri.B - 1;
-                const gflt rowp = rsrc + fr * rld;
-#pragma unroll
-                for (int k = 0; k < NB; ++k) braw[s][k][e] = rowp[rcolv[k]];
-            }
-        } else if constexpr (RAW == 2) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                int64_t fr = sk * KS + 2 * u + h; fr = fr < ri.B ? fr : ri.B - 1;
-                rawq[s][u] = reinterpret_cast<const __attribute__((address_space(1))) F4U*>(rsrc + fr * rld + rcol4)->v;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < NB; ++k) {
-                b[s][k][0] = *(gfrag)(bp[k] + o + loff);
-                if constexpr (NP == 2 && BLO) b[s][k][1] = *(gfrag)(bp[k] + plb + o + loff);
-            }
-        }
-    };
-    auto fsum = [&](const Frag& f) __attribute__((always_inline)) {
-        float t = 0.f;
-#pragma unroll
-        for (int q = 0; q < E; ++q) t += (float)f[q];
-        return t;
-    };
-    // RAW == 2: stage s of the raw ring -> (hi, lo) rows in LDS -> transposed fragments b[0][j]
-    auto prepare = [&](auto sc) __attribute__((always_inline)) {
-        constexpr int s = decltype(sc)::value;
-        if constexpr (RAW == 2) {
-            typedef typename P::Pack4 Pack4;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                Pack4 ph, pl;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { ph[e] = P::cvt(rawq[s][u][e]); pl[e] = P::cvt(rawq[s][u][e] - (float)ph[e]); }
-                T* const rowp = stg + (2 * u + h) * SLD + 4 * l31;
-                *reinterpret_cast<Pack4*>(rowp) = ph;
-                if constexpr (NP == 2) *reinterpret_cast<Pack4*>(rowp + SPL) = pl;
-            }
-            const int i16 = l31 & 15, q = i16 >> 2, pp = i16 & 3, cg = l31 >> 4;
-            typedef short s16x8 __attribute__((ext_vector_type(8)));
-#pragma unroll
-            for (int j = 0; j < NB; ++j)
-#pragma unroll
-                for (int pln = 0; pln < NP; ++pln) {
-                    const T* bpj = stg + pln * SPL + q * SLD + 32 * j + 16 * cg + 4 * pp;
-                    const s16x4 r0 = lds_tr16(bpj + (8 * h) * SLD), r1 = lds_tr16(bpj + (8 * h + 4) * SLD);
-                    const s16x8 raw8 = {r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]};
-                    b[0][j][pln] = __builtin_bit_cast(Frag, raw8);
-                }
-        }
-    };
-    // timing ablations of the main loop (tools/r05/ab_libs.sh on variants built by tools/r05/mkvariant.sh; results are wrong under any of them): W4_NOMFMA = loads + bias sums only,
-    // W4_NOFSUM = no bias sums, W4_NOLOAD = the ring is never refilled (MFMAs on the prologue's fragments), W4_NOEPI = no reduce-scatter / stores
-    auto compute = [&](auto sc) __attribute__((always_inline)) {
-        constexpr int s = decltype(sc)::value;
-#ifdef W4_NOMFMA
-        if constexpr (RAW == 0) {
-#pragma unroll
-            for (int i = 0; i < NA; ++i) {
-                bs[i] += fsum(a[s][i][0]);
-                if constexpr (NP == 2) bs[i] += fsum(a[s][i][1]);
-#pragma unroll
-                for (int j = 0; j < NB; ++j) { c[i][j][0] += (float)b[s][j][0][0]; if constexpr (NP == 2 && BLO) c[i][j][1] += (float)b[s][j][1][0]; }
-            }
-            return;
-        }
-#endif
-        if constexpr (RAW == 2) {
-#pragma unroll
-            for (int i = 0; i < NA; ++i) {
-#pragma unroll
-                for (int j = 0; j < NB; ++j) mmap<P>(c[i][j], a[s][i], b[0][j]);
-                if constexpr (BIAS) {
-                    bs[i] += fsum(a[s][i][0]);
-                    if constexpr (NP == 2) bs[i] += fsum(a[s][i][1]);
-                }
-            }
-        } else if constexpr (RAW == 1) {
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                Frag bj[NP];
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    bj[0][e] = P::cvt(braw[s][j][e]);
-                    if constexpr (NP == 2) bj[1][e] = P::cvt(braw[s][j][e] - (float)bj[0][e]);
-                }
-#pragma unroll
-                for (int i = 0; i < NA; ++i) mmap<P>(c[i][j], a[s][i], bj);
-            }
-            if constexpr (BIAS) {
-#pragma unroll
-                for (int i = 0; i < NA; ++i) {
-                    bs[i] += fsum(a[s][i][0]);
-                    if constexpr (NP == 2) bs[i] += fsum(a[s][i][1]);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NA; ++i) {
-#pragma unroll
-                for (int j = 0; j < NB; ++j) mmap<P>(c[i][j], a[s][i], b[s][j], BLO);
-#ifndef W4_NOFSUM
-                if constexpr (BIAS) {
-                    bs[i] += fsum(a[s][i][0]);                           // bias gradient: frame sum of the A fragment (VALU in the MFMAs' shadow)
-                    if constexpr (NP == 2) bs[i] += fsum(a[s][i][1]);
-                }
-#endif
-            }
-        }
-    };
-    // No branch around the loop (an empty range runs zero laps; its clamped prologue loads re-read the slice's last k-step): a
-    // conditional region here makes every accumulator a phi of (zero, loop result) and costs a 256-register copy.
-    {
-        const int64_t slast = (send > s0 ? send : s0 + 1) - 1;
-        static_for_w<0, RD>([&](auto sc) {
-            int64_t sk = sbeg + decltype(sc)::value; sk = sk < slast ? sk : slast;
-            load(sc, sk);
-        });
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (RAW == 2) prepare(std::integral_constant<int, 0>{});
-#pragma unroll 1
-        for (int64_t sk = sbeg; sk < send; sk += RD) {
-            static_for_w<0, RD>([&](auto sc) {
-                constexpr int s = decltype(sc)::value;
-                if (sk + s < send) compute(sc);                         // wave-uniform
-                int64_t sn = sk + RD + s; sn = sn < slast ? sn : slast;     // last lap: a harmless reload, no branch around a load
-                if constexpr (RAW == 2) {
-                    // the MFMAs of this k-step are in the pipe (their operands are read): stage the NEXT k-step's B tiles in their shadow
-                    // -- its raw values are consumed before this slot's reload below overwrites the ring
-                    prepare(std::integral_constant<int, (s + 1) % RD>{});
-                }
-#ifndef W4_NOLOAD
-                load(sc, sn);
-#else
-                (void)sn;
-#endif
-                __builtin_amdgcn_sched_barrier(0);
-            });
-        }
-        if constexpr (RAW == 2) __syncthreads();                        // every wave is done with its staging rows: the reduce-scatter below reuses the LDS
-    }
-    // ---- the four partial blocks meet in LDS: a reduce-scatter in a fixed order (deterministic).  Wave w ends up with A tile row
-    // w of the block (its local row 0) and stores it: a single wave storing 8 tiles with per-element address arithmetic took
-    // 17 us (issue-bound), more than the main loop.
-#ifdef W4_NOEPI
-    {
-        float t = bs[0] + bs[1] + bs[2] + bs[3];
-#pragma unroll
-        for (int i = 0; i < NA; ++i)
-#pragma unroll
-            for (int j = 0; j < NB; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) t += c[i][j][r];
-        if (t == 123.456f) slabs[0] = t;
-        return;
-    }
-#endif
-    constexpr int ROWQ = 4 * 4 * 64;                                      // f32x4 quads of one A row (4 tiles x 16 registers x 64 lanes)
-    f32x4* const lds = reinterpret_cast<f32x4*>(wsm);
-    float* const lbias = reinterpret_cast<float*>(lds + 8 * ROWQ);        // [dest wave][source order][lane]
-    auto put_row = [&](auto ic, int slot) __attribute__((always_inline)) {
-        constexpr int i = decltype(ic)::value;
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                lds[slot * ROWQ + (j * 4 + q) * 64 + lane] = f32x4{c[i][j][4 * q], c[i][j][4 * q + 1], c[i][j][4 * q + 2], c[i][j][4 * q + 3]};
-    };
-    auto add_row0 = [&](int slot) __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const f32x4 v = lds[slot * ROWQ + (j * 4 + q) * 64 + lane];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) c[0][j][4 * q + e] += v[e];
-            }
-    };
-    typedef std::integral_constant<int, 0> I0; typedef std::integral_constant<int, 1> I1;
-    typedef std::integral_constant<int, 2> I2; typedef std::integral_constant<int, 3> I3;
-    if constexpr (NA == 1) {
-        // one A row: waves 1-3 hand it to wave 0
-        if (wave != 0) { put_row(I0{}, wave); lbias[wave * 64 + lane] = bs[0]; }
-        __syncthreads();
-        if (wave != 0) return;
-        add_row0(1); add_row0(2); add_row0(3);
-        bs[0] += lbias[64 + lane]; bs[0] += lbias[128 + lane]; bs[0] += lbias[192 + lane];
-    } else {
-        // round A: local rows 1, 2 go to waves (w + 1) % 4, (w + 2) % 4 (slot = 2 * destination + source order); round B: local row 3
-        const int d1 = (wave + 1) & 3, d2 = (wave + 2) & 3, d3 = (wave + 3) & 3;
-        put_row(I1{}, 2 * d1); put_row(I2{}, 2 * d2 + 1);
-        lbias[(3 * d1 + 0) * 64 + lane] = bs[1]; lbias[(3 * d2 + 1) * 64 + lane] = bs[2]; lbias[(3 * d3 + 2) * 64 + lane] = bs[3];
-        __syncthreads();
-        add_row0(2 * wave); add_row0(2 * wave + 1);                         // from wave (w - 1) % 4, then from wave (w - 2) % 4
-        __syncthreads();
-        put_row(I3{}, d3);
-        __syncthreads();
-        add_row0(wave);                                                   // from wave (w - 3) % 4
-        bs[0] += lbias[(3 * wave + 0) * 64 + lane]; bs[0] += lbias[(3 * wave + 1) * 64 + lane]; bs[0] += lbias[(3 * wave + 2) * 64 + lane];
-    }
-    // ---- store local row 0 = A tile `rot` of the block (descriptor fields of that tile: wave-uniform scalar loads)
-    float* const slab = slabs + (int64_t)slice * slab_stride;
-    const int mv = bdg->mvalid[rot], ldo = bdg->ldo[rot];
-    const int64_t a_off = bdg->a_off[rot], bias_off = bdg->bias_off[rot];
-    const bool split = rot == 0 && bd.split16;
-    if (mv == 32 && !split) {
-        // full tile rows: one exec region per tile, scalar row address + a per-lane 32-bit offset.  (Round 3 tried 16-byte stores -- the
-        // tile turned through this wave's LDS slot so that a lane holds four consecutive columns, 4 stores of 1 KB per tile instead of
-        // 16 of 256 B: 28.1 us against 27.2 us for the kernel, same box, alternating.  The dword form stays.)
-        const unsigned lo = (unsigned)(4 * h * ldo + l31);
-#if W4_SLAB_AUX
-        const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(slab + a_off, 0, 0x7fffffff, 0x00020000);   // this A row's 32 tensor rows
-#endif
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            if (l31 < bd.nvalid[j]) {
-                float* const t0 = slab + a_off + bd.bcol[j];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-#if W4_SLAB_AUX
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(c[0][j][r]), srs, (int)(4u * lo), (int)(4u * (unsigned)(bd.bcol[j] + ((r & 3) + 8 * (r >> 2)) * ldo)), W4_SLAB_AUX);
-#else
-                    float* const rowp = t0 + (int64_t)((r & 3) + 8 * (r >> 2)) * ldo;     // wave-uniform
-                    rowp[lo] = c[0][j][r];
-#endif
-                }
-                (void)t0;
-            }
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = feat_of(r, h);
-                if (row < mv && l31 < bd.nvalid[j]) {
-                    const bool hi = split && row >= 16;
-                    const int rr = hi ? row - 16 : row;
-                    const int ld = hi ? bd.ldo_hi : ldo;
-                    slab_store(&slab[(hi ? bd.a_off_hi : a_off) + (int64_t)rr * ld + bd.bcol[j] + l31], c[0][j][r]);
-                }
-            }
-        }
-    }
-    const float tot = bs[0] + __shfl_xor(bs[0], 32, 64);                  // the two frame halves of feature row l31
-    if (h == 0 && l31 < mv && bias_off >= 0) {
-        const bool hi = split && l31 >= 16;
-        slab_store(&slab[hi ? bd.bias_off_hi + (l31 - 16) : bias_off + l31], tot);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// ---- the optimizer step folded into the tail of the weight-gradient kernel (a train step = two launches).
-// Every (slice, block) workgroup, once its partial block is in its slab, arrives at the block's counter and waits until all `ksplit`
-// slices of the block have arrived (the grid is one round of workgroups, all resident: the host folds only when the grid fits the CUs;
-// the wait is bounded and raises the error word instead of hanging).  Then the ksplit * 4 waves share the block's parameters: a wave
-// takes whole tensor rows (row u of the block's 128, u = wave id, + ksplit * 4, ...; units 128-131: the bias rows), a lane two elements
-// of a row; each element = the slab sum in slab order (the very additions of apply_kernel), Adam, the weight-copy refresh.  Workgroup 0
-// also turns the rows kernel's partial sums into the loss scalars.
-// Counters (unsigned words of the flag header): [2] error (sticky), [16 + b] arrivals of block b -- never reset: launch number n of a
-// workspace (counted by the host, fold_seq) waits for ksplit * n.  One fire-and-forget atomic and the polling loads are all the
-// synchronisation a workgroup pays (returning atomics cost a device-scope round trip each: 2 us on the critical path).
-constexpr int FOLD_MAXB = 120;
-struct FoldArgs { unsigned* cnt; unsigned target; unsigned max_polls; };
-
-#ifdef DVAE_DIAG
-template <typename T, int NP>
-__device__ __forceinline__ void fold_tail(const ApplyArgs& g, const FoldArgs& fa, const Block4& bd, const Block4* __restrict__ bdg, int bi, int slice,
-                                          int ks, int lane, int wave, char* wsm) {
-    int* const flag = reinterpret_cast<int*>(wsm);                     // the reduce-scatter is over: the exchange slots are free
-    // This wave's slab stores are complete, i.e. visible device-wide: they are write-through (sc1) stores, so waiting for them is
-    // enough.  (A release fence writes back the XCD's whole L2 and the matching acquire invalidates it -- 960 times per launch: the
-    // kernel took 75 us instead of 28.)
-#if W4_SLAB_AUX
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-#endif
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __hip_atomic_fetch_add(fa.cnt + 16 + bi, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        unsigned polls = 0;
-        int ok = 1;
-        while ((int)(__hip_atomic_load(fa.cnt + 16 + bi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - fa.target) < 0) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++polls > fa.max_polls) { ok = 0; break; }
-        }
-        if (!ok) __hip_atomic_store(fa.cnt + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        flag[0] = ok;
-    }
-    __syncthreads();
-    const int ok = flag[0];
-#if !W4_SLAB_AUX
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
-#ifndef FOLD_DIAG
-#define FOLD_DIAG 0      // timing diagnostics (wrong results): 1 = wait only, 2 = wait + loads + stores of p only, 3 = no loss scalars
-#endif
-    if (ok && FOLD_DIAG != 1) {
-        int nb = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) if (bd.Bt[k] != nullptr) nb = k + 1;
-        const int gw = slice * 4 + wave, nw = ks * 4;
-        constexpr int UB = 4;                                          // units per batch: their loads are all in flight together
-        for (int u0 = gw; u0 < 132; u0 += UB * nw) {
-            int64_t idx[UB][2];
-            float pi[UB][2], mo[UB][2], vo[UB][2], gi[UB][2];
-            int tq[UB][2];                                             // wave-uniform: a unit is a row of ONE tensor (two for the heads' bias unit: one per q)
-#pragma unroll
-            for (int b = 0; b < UB; ++b) {
-                const int u = u0 + b * nw;                             // wave-uniform
-                idx[b][0] = idx[b][1] = -1;
-                tq[b][0] = tq[b][1] = 0;
-                if (u < 128) {
-                    const int rot = u >> 5, rr = u & 31;
-                    if (rr < bdg->mvalid[rot]) {
-                        const bool hi = rot == 0 && bd.split16 && rr >= 16;
-                        const int64_t base = hi ? bd.a_off_hi + (int64_t)(rr - 16) * bd.ldo_hi : bdg->a_off[rot] + (int64_t)rr * bdg->ldo[rot];
-                        tq[b][0] = tq[b][1] = hi ? bd.wt_hi : bdg->wt[rot];
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) {
-                            const int j = (lane >> 5) + 2 * q, l = lane & 31;     // columns lane and lane + 64 of the block's 128
-                            if (j < nb && l < bdg->nvalid[j]) idx[b][q] = base + bdg->bcol[j] + l;
-                        }
-                    }
-                } else if (u < 132) {
-                    const int rot = u - 128;
-                    const int64_t bo = bdg->bias_off[rot];
-                    const int mv = bdg->mvalid[rot];
-                    if (bo >= 0) {
-                        const bool split = rot == 0 && bd.split16;
-                        tq[b][0] = bdg->bt[rot]; tq[b][1] = bd.bt_hi;
-                        if (lane < (split ? 16 : 32) && lane < mv) idx[b][0] = bo + lane;
-                        if (split && lane >= 16 && lane < 32 && lane < mv) idx[b][1] = bd.bias_off_hi + (lane - 16);
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const int64_t i = idx[b][q] >= 0 ? idx[b][q] : 0;  // masked lanes read element 0 (no branch around the loads)
-                    pi[b][q] = g.p[i]; mo[b][q] = g.m[i]; vo[b][q] = g.v[i];
-                    gi[b][q] = slab_sum_at<W4_SLAB_AUX != 0>(g, i);               // the other slices' slabs, not this XCD's stale L2 lines
-                }
-            }
-#pragma unroll
-            for (int b = 0; b < UB; ++b)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const TensorDesc& d = g.tensors[tq[b][q]];                     // uniform address: scalar loads
-                    if (FOLD_DIAG == 2) { if (idx[b][q] >= 0) g.p[idx[b][q]] = pi[b][q] + mo[b][q] + vo[b][q] + gi[b][q]; continue; }
-                    if (idx[b][q] >= 0) apply_element<T, true, NP>(g, idx[b][q], d, pi[b][q], mo[b][q], vo[b][q], gi[b][q]);
-                }
-        }
-    }
-    if (blockIdx.x == 0 && g.losses3 != nullptr && FOLD_DIAG == 0) {   // workgroup 0 (always a participant): loss scalars
-        __syncthreads();
-        finalize_losses(g, reinterpret_cast<double (*)[4]>(wsm + 64));
-        // a wait that ran out (error word set, sticky): parameters were not all updated -- the loss says so
-        if (threadIdx.x == 0 && __hip_atomic_load(fa.cnt + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) g.losses3[0] = __builtin_nanf("");
-    }
-    if (!ok && threadIdx.x == 0 && g.losses3 != nullptr) g.losses3[0] = __builtin_nanf("");
-}
-#endif  // DVAE_DIAG
-
-template <typename P>
-__global__ __launch_bounds__(256, 1) void wgrad4_kernel(const Block4* __restrict__ blocks, const W4Item* __restrict__ items, int ksplit, int64_t Bp,
-                                                        int64_t spl, float* __restrict__ slabs, int64_t slab_stride,
-                                                        const RawIn ri, int use_raw, const unsigned* __restrict__ ylo_epoch, unsigned launch_id,
-                                                        const ApplyArgs fold_apply, const FoldArgs fold, int fin_block, const unsigned* fin_err) {
-    extern __shared__ __attribute__((aligned(16))) char wsm[];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // deferred optimizer step (apply_common.hpp): the step's loss scalars no longer come from an optimizer launch -- ONE extra workgroup of
-    // this launch (it follows the rows kernel, whose partial sums are complete) reduces them, on a CU the weight-gradient blocks leave free
-    if (fin_block >= 0 && (int)blockIdx.x == fin_block) {
-        finalize_losses(fold_apply, reinterpret_cast<double (*)[4]>(wsm));
-        if (threadIdx.x == 0 && fin_err != nullptr && __hip_atomic_load(fin_err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)
-            fold_apply.losses3[0] = __builtin_nanf("");              // a bounded wait of the rows kernel ran out: the update was not complete
-        return;
-    }
-    // Workgroup -> (block, slice, frames): the host's item table (w4_build_items).  Workgroup i runs on XCD i % 8 (speed only): the table
-    // keeps the items that read the same stash lines -- the blocks of a layer over the same frames -- on one XCD, and cuts every block into
-    // as many slices as its cost per k-step asks for, so that all workgroups of the one round finish together.
-    const W4Item it = items[blockIdx.x];
-    if (it.block < 0) return;
-    const int slice = it.slice, bi = it.block;
-    const Block4 bd = blocks[bi];                                       // by value: wave-uniform, lives in SGPRs (a reference would be re-read after every slab store)
-    int na = 0, nb = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { if (bd.At[k] != nullptr) na = k + 1; if (bd.Bt[k] != nullptr) nb = k + 1; }
-    // (BIAS = false bodies -- no frame sums of the A fragments in blocks that carry no bias rows -- exist as a template parameter and are NOT
-    // instantiated: built in round 5, the kernel with them took 34.3 us against 25.3 without, same box, alternating (their loops are
-    // tighter, 158 against 394 instructions per two k-steps, but hipcc spills 250 - 650 registers around them; tools/r05/w4_ab2.sh))
-#define W4_GO_(NA_, NB_, RAW_, BLO_) wgrad4_body<P, NA_, NB_, RAW_, BLO_, true>(bd, blocks + bi, wsm, slice, Bp, spl, it.kbeg, it.kend, slabs, slab_stride, lane, wave, ri)
-#define W4_GO(NA_, NB_, RAW_) W4_GO_(NA_, NB_, RAW_, true)
-    bool raw = false;
-    if constexpr (sizeof(typename P::T) == 2) raw = (use_raw & bd.raw) != 0;      // input-matrix B tiles (16-bit operand policies only); use_raw bit 0: x, bit 1: labels
-    if (raw) {
-        if constexpr (sizeof(typename P::T) == 2) {
-            if (nb == 4 && bd.rcol[0] + 128 <= bd.rncols) W4_GO(4, 4, 2);      // four full tiles: through the LDS staging rows
-            else if (nb == 1) W4_GO(4, 1, 1);
-            else if (nb == 2) W4_GO(4, 2, 1);
-            else W4_GO(4, 4, 1);
-        }
-    } else if (sizeof(typename P::T) == 2 && P::NP == 2 && bd.raw == 2 && ylo_epoch != nullptr && *ylo_epoch != launch_id) {
-        // label-fed blocks of a launch whose label tiles all fit one bf16 plane (binary labels): hi plane only
-        if (nb == 1) W4_GO_(4, 1, 0, false);
-        else if (nb == 2) W4_GO_(4, 2, 0, false);
-        else W4_GO_(4, 4, 0, false);
-    } else if (na == 1) {
-        if (nb == 1) W4_GO(1, 1, 0);
-        else if (nb == 2) W4_GO(1, 2, 0);
-        else W4_GO(1, 4, 0);
-    } else {
-        if (nb == 1) W4_GO(4, 1, 0);
-        else if (nb == 2) W4_GO(4, 2, 0);
-        else W4_GO(4, 4, 0);
-    }
-#undef W4_GO
-#undef W4_GO_
-#ifndef W4_FOLD
-#ifdef DVAE_DIAG
-#define W4_FOLD 1      // 0: the folded optimizer tail compiled out (A/B of what its presence costs the main loop)
-#else
-#define W4_FOLD 0      // product build: no folded tail
-#endif
-#endif
-#if W4_FOLD
-    if (fold.cnt != nullptr) fold_tail<typename P::T, P::NP>(fold_apply, fold, bd, blocks + bi, bi, slice, ksplit, lane, wave, wsm);
-#endif
-}
-
-// sum of up to NS slabs at element i: every load issued before the first addition (a run-time loop makes each addition wait for
-// its own load: ten dependent round trips), additions in slab order (deterministic)
-template <int NS>
-__device__ __forceinline__ float slab_total(const float* __restrict__ slabs, int64_t i, int nslabs, int64_t stride) {
-    float part[NS];
-#pragma unroll
-    for (int k = 0; k < NS; ++k) part[k] = slabs[(int64_t)(k < nslabs ? k : 0) * stride + i];
-    float t = part[0];
-#pragma unroll
-    for (int k = 1; k < NS; ++k) if (k < nslabs) t += part[k];
-    return t;
-}
-__device__ __forceinline__ float slab_total_any(const float* __restrict__ slabs, int64_t i, int nslabs, int64_t stride) {
-    if (nslabs <= 8) return slab_total<8>(slabs, i, nslabs, stride);
-    if (nslabs <= 16) return slab_total<16>(slabs, i, nslabs, stride);
-    float s = slabs[i];
-    for (int k = 1; k < nslabs; ++k) s += slabs[k * stride + i];
-    return s;
-}
-
-// dst = (accumulate ? dst : 0) + sum of the slabs (fixed order: deterministic)
-__global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__ slabs, int64_t n, int nslabs, int64_t stride, float* __restrict__ dst, int accumulate) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float s = slab_total_any(slabs, i, nslabs, stride);
-        dst[i] = accumulate ? dst[i] + s : s;
-    }
-}
-
-__global__ __launch_bounds__(256) void slab_reduce_kernel(float* __restrict__ slabs, int64_t n, int nslabs, int64_t stride) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        slabs[i] = slab_total_any(slabs, i, nslabs, stride);
-}
-
-// One thread per parameter over the flat buffer (every load independent); chunk_tensor maps each
-// 64-float chunk to its tensor (tensors start on 64-float boundaries), 255 = alignment padding.
-// The block after the last parameter block finalises the loss scalars.
-template <typename T, bool ADAM, int NP = 1>
-__global__ __launch_bounds__(256) void apply_kernel(const ApplyArgs g) {
-    if (blockIdx.x == gridDim.x - 1) {                    // loss finalisation block
-        if (!ADAM || g.losses3 == nullptr) return;
-        __shared__ double red[4][4];
-        finalize_losses(g, red);
-        return;
-    }
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= g.n_params) return;
-    // Everything this thread reads sits at flat index idx (alignment padding between tensors included, the buffers
-    // are allocated whole): request it all FIRST, so the two dependent table lookups below (chunk -> tensor ->
-    // descriptor) overlap the one HBM round trip instead of preceding it.
-    const float pi = g.p[idx];
-    float m_old = 0.f, v_old = 0.f, gi = 0.f;
-    if (ADAM) {
-        m_old = g.m[idx]; v_old = g.v[idx];
-        gi = slab_sum_at(g, idx);
-    }
-    // a wave covers one 64-float chunk: its tensor and the descriptor are wave-uniform, fetched by scalar loads
-    const int t = g.chunk_tensor[__builtin_amdgcn_readfirstlane((int)(idx >> 6))];
-    if (t == 255) return;
-    const TensorDesc d = g.tensors[t];
-    apply_element<T, ADAM, NP>(g, idx, d, pi, m_old, v_old, gi);
-}
-
-#ifdef DVAE_DIAG
-// The optimizer step by UNITS (apply_common.hpp: defer_unit -- 8 rows x 32 columns of one weight matrix per wave, whole-line loads of
-// parameters / moments / slabs, the kernel-layout copies as whole 8- and 16-byte pieces through the transposing LDS read): the same
-// element arithmetic as apply_kernel on the same slab sums (bit-identical, tested), a quarter of its instructions, no lone 2-byte stores.
-// One unit per wave; the block after the last unit block finalises the loss scalars.  bf16 / bf16x3 copies.
-template <typename T, int NP>
-__global__ __launch_bounds__(256) void apply_units_kernel(const ApplyArgs g, const DeferTask* __restrict__ tasks, int nunits) {
-    __shared__ __attribute__((aligned(16))) char sm[4 * DeferLds<T, NP>::wave_elems * sizeof(T) > 128 ? 4 * DeferLds<T, NP>::wave_elems * sizeof(T) : 128];
-    if (blockIdx.x == gridDim.x - 1) {
-        if (g.losses3 == nullptr) return;
-        finalize_losses(g, reinterpret_cast<double (*)[4]>(sm));
-        return;
-    }
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    // unit un of the launch: consecutive units of a tile on different workgroups (a tile's four units share lines at odd row lengths)
-    const int un = wave * ((int)gridDim.x - 1) + (int)blockIdx.x;
-    if (un >= nunits) return;
-    T* const tile = reinterpret_cast<T*>(sm) + wave * DeferLds<T, NP>::wave_elems;
-    defer_unit<T, NP, false>(g, tasks[un >> 2], un & 3, tile, lane);
-}
-#endif  // DVAE_DIAG
 
 // ---------------------------------------------------------------------------------------------
 // host-side planning
@@ -1572,7 +44,6 @@ constexpr int64_t DEFER_BYTES = DEFER_O_DONE + 128;
 
 static inline int64_t al(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
-static inline bool is_bf(int precision) { return precision == DVAE_PREC_BF16 || precision == DVAE_PREC_BF16X3; }
 static inline int planes_of(int precision) { return precision == DVAE_PREC_BF16X3 ? 2 : 1; }
 
 static int make_layout(const dvae_train_plan_t& p, Layout& L) {
@@ -2021,31 +492,12 @@ static int launch_apply(const dvae_train_plan_t* plan, const Layout& L, float* p
     const int ntasks = defer_state_get(ws).ntasks;
     const char* ak = getenv("DVAE_APPLY");
 #ifdef DVAE_DIAG
-    if (adam && is_bf(plan->precision) && n_slabs <= 12 && ntasks > 0 && ntasks <= DEFER_MAX_TASKS && ak && strcmp(ak, "units") == 0) {
-        const int nunits = 4 * ntasks;
-        const dim3 gu((unsigned)((nunits + 3) / 4 + 1));
-        const DeferTask* tasks = (const DeferTask*)(ws + L.o_defer);
-        if (plan->precision == DVAE_PREC_BF16X3) hipLaunchKernelGGL((apply_units_kernel<__bf16, 2>), gu, dim3(256), 0, s, a, tasks, nunits);
-        else hipLaunchKernelGGL((apply_units_kernel<__bf16, 1>), gu, dim3(256), 0, s, a, tasks, nunits);
-        DVAE_LAUNCH_OK("apply_units_kernel");
-        return 0;
-    }
+    if (adam && is_bf(plan->precision) && n_slabs <= 12 && ntasks > 0 && ntasks <= DEFER_MAX_TASKS && ak && strcmp(ak, "units") == 0)
+        return launch_apply_units(plan->precision, a, (const DeferTask*)(ws + L.o_defer), 4 * ntasks, s);
 #else
     (void)ntasks; (void)ak;
 #endif
-    const dim3 grid((unsigned)((plan->n_params + 255) / 256 + 1));   // + 1: loss finalisation block
-    if (plan->precision == DVAE_PREC_BF16X3) {
-        if (adam) hipLaunchKernelGGL((apply_kernel<__bf16, true, 2>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((apply_kernel<__bf16, false, 2>), grid, dim3(256), 0, s, a);
-    } else if (plan->precision == DVAE_PREC_BF16) {
-        if (adam) hipLaunchKernelGGL((apply_kernel<__bf16, true>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((apply_kernel<__bf16, false>), grid, dim3(256), 0, s, a);
-    } else {
-        if (adam) hipLaunchKernelGGL((apply_kernel<float, true>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((apply_kernel<float, false>), grid, dim3(256), 0, s, a);
-    }
-    DVAE_LAUNCH_OK("apply_kernel");
-    return 0;
+    return launch_apply_kernel(plan->precision, adam, a, s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2317,22 +769,6 @@ extern "C" int dvae_train_init(const dvae_train_plan_t* plan, const float* param
     return dvae_train_repack(plan, params, ws, stream);
 }
 
-static int current_device() { int dev = 0; (void)hipGetDevice(&dev); return dev < 0 || dev >= 64 ? 0 : dev; }      // (index of the per-device tables: 64 entries)
-template <typename P, int YP, bool YENC, bool INFO = false>
-static int launch_rows(const RowsArgs& a, int grid, hipStream_t s) {
-    const size_t lds = Pl<P>::bytes;
-    static bool attr_done[64] = {};                      // per device: the attribute belongs to the device's copy of the code object
-    const int dev = current_device();
-    if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)vae_rows_kernel<P, YP, YENC, INFO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute(rows kernel, %zu B LDS): %s", lds, hipGetErrorString(e)); return (int)e; }
-        attr_done[dev] = true;
-    }
-    hipLaunchKernelGGL((vae_rows_kernel<P, YP, YENC, INFO>), dim3(grid), dim3(256), lds, s, a);
-    DVAE_LAUNCH_OK("vae_rows_kernel");
-    return 0;
-}
-
 // dvae_train_step -> run_grads: "run the optimizer step in the weight-gradient launch if you can" (done: the answer, it did)
 struct FoldRequest { bool want = false, done = false; PendingUpdate u{}; float* losses3 = nullptr; };
 
@@ -2437,14 +873,6 @@ struct StepEnv {
 // launch id, or its label blocks would misread the epoch word.  The one state that crosses calls, per thread.
 static thread_local struct GroupPairing { unsigned last_id = 0; const void* last_ws = nullptr; } g_pairing;
 
-// f(P{}) for the operand policy P of plan->precision
-template <typename F>
-static auto with_policy(int precision, F&& f) {
-    if (precision == DVAE_PREC_BF16X3) return f(PolX3{});
-    if (precision == DVAE_PREC_BF16) return f(PolBF16{});
-    return f(PolF32{});
-}
-
 // the rows kernel's arguments from plan, layout and options (all but ylo_skip, which run_grads decides); host arithmetic only
 static int fill_rows_args(const dvae_train_plan_t* plan, const Layout& L, const GradsOptions& o, const StepEnv& env, const float* params, char* w,
                           const float* x, int ldx, const float* y, int ldy, const float* eps_noise, float elbo_eps, RowsArgs& a) {
@@ -2523,22 +951,7 @@ static int launch_rows_kernel(const dvae_train_plan_t* plan, const RowsArgs& a, 
     const int grid = (int)plan->rows_grid;
     if (plan->rows_kernel == 3 && rows3_supported(plan->precision, plan->model)) return launch_rows3(plan->model, plan->y_dim, a, grid, s);
     if (plan->rows_kernel == 2 && rows2_supported(plan->precision, plan->model)) return launch_rows2(plan->precision, plan->model, plan->y_dim, a, grid, s);
-    auto rows4 = [&](auto pol) {      // the 4-wave kernel of one operand policy, in the plan's model variant
-        using P = decltype(pol);
-        if (plan->model == DVAE_MODEL_M2_INFO) return launch_rows<P, 16, false, true>(a, grid, s);
-        if (plan->model != DVAE_MODEL_M2) return launch_rows<P, 0, false>(a, grid, s);
-        if (plan->y_dim == 1) return launch_rows<P, 16, true>(a, grid, s);
-        return launch_rows<P, 528, true>(a, grid, s);
-    };
-#ifdef DVAE_DIAG
-    return with_policy(plan->precision, rows4);
-#else
-    if (is_bf(plan->precision)) {
-        set_error("train_grads: the 4-wave rows kernel under the bf16 policies exists in the diagnostic build only (build.py --diag)");
-        return DVAE_E_UNSUPPORTED;
-    }
-    return rows4(PolF32{});
-#endif
+    return launch_rows1(plan->precision, plan->model, plan->y_dim, a, grid, s);
 }
 
 // the weight-gradient launch(es) over the stash the rows kernel left, then the optional slab reduction; wg4: the workgroup k-split kernel
@@ -2551,7 +964,7 @@ static int launch_wgrad_pass(const dvae_train_plan_t* plan, const Layout& L, Gra
     DVAE_CHECK_ARG(!w4_classed(*plan) || env.wgrad_form == 4,
                    "train_grads: the plan was made for the workgroup k-split weight-gradient kernel (class-sliced schedule); DVAE_WGRAD changed since");
     float* slabs = (float*)(w + L.o_grads);
-    const int dev = current_device();
+    const WgradArgs wa{ks, plan->Bp, a.spl, kper, slabs, plan->n_params};      // (the two uniform-slice kernels)
     for (int rep = 0; rep < env.wgrad_repeat; ++rep) {
         if (wg4) {
             // one launch (table 0), or the launches of a grouped plan: tables 1 and 2, both (group < 0) or the one asked for
@@ -2571,7 +984,7 @@ static int launch_wgrad_pass(const dvae_train_plan_t* plan, const Layout& L, Gra
                 memset(&fa_apply, 0, sizeof(fa_apply));
                 FoldArgs fold{nullptr, 0u, 0u};
                 const PendingUpdate& u = o.fold.u;
-                if (o.fold.want && !w4_classed(*plan) && env.wgrad_repeat == 1 && a.mode == 0 && ks > 1 && ks <= 16 && L.nblocks4 <= FOLD_MAXB && (int)g3.x <= device_cu_count(dev)) {
+                if (o.fold.want && !w4_classed(*plan) && env.wgrad_repeat == 1 && a.mode == 0 && ks > 1 && ks <= 16 && L.nblocks4 <= FOLD_MAXB && (int)g3.x <= device_cu_count(current_device())) {
                     fa_apply = make_apply_args(plan, L, u.params, u.m, u.v, w, ks, true, u.step, u.lr, u.beta1, u.beta2, u.adam_eps, 1.0, o.fold.losses3);
                     fold.cnt = (unsigned*)(w + L.o_flags);
                     fold.target = (unsigned)ks * fold_seq_next(w);
@@ -2586,50 +999,26 @@ static int launch_wgrad_pass(const dvae_train_plan_t* plan, const Layout& L, Gra
                     fin_block = (int)g3.x; fin_err = a.defer.err;
                     g3l = dim3(g3.x + 1);
                 }
-                const int rc = with_policy(plan->precision, [&](auto pol) -> int {
-                    using P = decltype(pol);
-                    static bool attr_done[64] = {};      // per device: the attribute belongs to the device's copy of the code object
-                    if (!attr_done[dev]) { DVAE_HIP(hipFuncSetAttribute((const void*)wgrad4_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Wg4<P>::BYTES)); attr_done[dev] = true; }
-                    hipLaunchKernelGGL((wgrad4_kernel<P>), g3l, dim3(256), Wg4<P>::BYTES, s, bl, w4items, ks, plan->Bp, a.spl, slabs, plan->n_params, ri, use_raw,
-                                       a.ylo_skip ? a.ylo_epoch : nullptr, x3 ? a.launch_id : 0u /* the split-bf16 kernel alone reads them */, fa_apply, fold, fin_block, fin_err);
-                    return 0;
-                });
+                const Wgrad4Args w4a{bl, w4items, ks, plan->Bp, a.spl, slabs, plan->n_params, ri, use_raw,
+                                     a.ylo_skip ? a.ylo_epoch : nullptr, x3 ? a.launch_id : 0u /* the split-bf16 kernel alone reads them */, fa_apply, fold, fin_block, fin_err};
+                const int rc = launch_wgrad4(plan->precision, w4a, (int)g3l.x, s);
                 if (rc) return rc;
-                DVAE_LAUNCH_OK("wgrad4_kernel");
             }
         } else if (is_bf(plan->precision) && env.wgrad_form == 1) {
-#ifdef DVAE_DIAG
             ProfScope ps(s, rep == 0 ? 1 : 2);
-            const dim3 g3((unsigned)(L.nblocks * ks));
-            auto lds = [&](auto pol) -> int {      // (two policies: there is no fp32 form of this kernel)
-                using P = decltype(pol);
-                static bool attr_done[64] = {};
-                if (!attr_done[dev]) { DVAE_HIP(hipFuncSetAttribute((const void*)wgrad_lds_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, WgLds<P>::BYTES)); attr_done[dev] = true; }
-                hipLaunchKernelGGL((wgrad_lds_kernel<P>), g3, dim3(256), WgLds<P>::BYTES, s, (const BlockDesc*)(w + L.o_blocks), L.nblocks, ks, plan->Bp, a.spl, kper, slabs, plan->n_params);
-                return 0;
-            };
-            const int rc = x3 ? lds(PolX3{}) : lds(PolBF16{});
+            const int rc = launch_wgrad_lds(plan->precision, (const BlockDesc*)(w + L.o_blocks), L.nblocks, wa, s);
             if (rc) return rc;
-            DVAE_LAUNCH_OK("wgrad_lds_kernel");
-#else
-            set_error("train_grads: DVAE_WGRAD=lds exists in the diagnostic build only (build.py --diag)");
-            return DVAE_E_UNSUPPORTED;
-#endif
         } else {
             ProfScope ps(s, rep == 0 ? 1 : 2);
-            const dim3 g2((unsigned)(((L.ntiles + env.gpw - 1) / env.gpw) * ks));
-            with_policy(plan->precision, [&](auto pol) {
-                hipLaunchKernelGGL((wgrad_kernel<decltype(pol)>), g2, dim3(64 * env.gpw), 0, s, (const GroupDesc*)(w + L.o_tiles), L.ntiles, ks, plan->Bp, a.spl, kper, slabs, plan->n_params);
-            });
-            DVAE_LAUNCH_OK("wgrad_kernel");
+            const int rc = launch_wgrad_ring(plan->precision, (const GroupDesc*)(w + L.o_tiles), L.ntiles, wa, env.gpw, s);
+            if (rc) return rc;
         }
     }
     if (reduce_slabs && ks > 1) {
         ProfScope ps(s, 2);
         int64_t lo, hi;                                                   // a group's launch reduces its own part of the flat gradient
         dvae_train_group_range(plan, o.group, &lo, &hi, nullptr);
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(512), dim3(256), 0, s, slabs + lo, hi - lo, ks, plan->n_params);
-        DVAE_LAUNCH_OK("slab_reduce_kernel");
+        return launch_slab_reduce(slabs + lo, hi - lo, ks, plan->n_params, s);
     }
     return 0;
 }
@@ -2774,10 +1163,7 @@ extern "C" int dvae_module_backward(const dvae_train_plan_t* plan, const float* 
     Layout L;
     make_layout(*plan, L);
     const float* slabs = (const float*)((const char*)ws + L.o_grads);
-    hipLaunchKernelGGL(slab_sum_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, slabs, plan->n_params, used_slabs(plan), plan->n_params,
-                       grad_flat, accumulate);
-    DVAE_LAUNCH_OK("slab_sum_kernel");
-    return 0;
+    return launch_slab_sum(slabs, plan->n_params, used_slabs(plan), plan->n_params, grad_flat, accumulate, (hipStream_t)stream);
 }
 
 extern "C" int dvae_train_debug_stamps(void* buf) {
@@ -2800,29 +1186,12 @@ extern "C" int dvae_train_eval(const dvae_train_plan_t* plan, const float* param
     char* w = (char*)ws;
     a.partials = (const double*)(w + L.o_partials); a.npartials = (int)plan->rows_grid; a.B = plan->B; a.losses3 = losses3; a.accum = (double*)(uintptr_t)plan->loss_accum;
     a.info = plan->model == DVAE_MODEL_M2_INFO; a.alpha = (float)plan->info_alpha; a.beta = (float)plan->info_beta; a.gamma = (float)plan->info_gamma;
-    hipLaunchKernelGGL((apply_kernel<float, true>), dim3(1), dim3(256), 0, (hipStream_t)stream, a);   // grid of 1 = the loss block only
-    DVAE_LAUNCH_OK("apply_kernel(loss only)");
-    return 0;
+    return launch_apply_losses(a, (hipStream_t)stream);
 }
-
-namespace dvae { namespace fused {
-__global__ __launch_bounds__(256) void noise_kernel(unsigned long long seed, unsigned long long step, int64_t B, float* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;      // one (frame, half) pair per thread
-    if (i >= 2 * B) return;
-    const int64_t frame = i >> 1; const int h = (int)(i & 1);
-    float e[8];
-    frame_noise8(seed, (unsigned long long)frame, step, h, e);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { out[frame * ZD + 4 * h + j] = e[j]; out[frame * ZD + 8 + 4 * h + j] = e[4 + j]; }
-}
-} }
 
 extern "C" int dvae_train_noise(const dvae_train_plan_t* plan, uint64_t step, float* eps_out, void* stream) {
     DVAE_CHECK_ARG(plan && eps_out, "train_noise: null argument");
-    hipLaunchKernelGGL(dvae::fused::noise_kernel, dim3((unsigned)((2 * plan->B + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (unsigned long long)plan->rng_seed, (unsigned long long)step, plan->B, eps_out);
-    DVAE_LAUNCH_OK("noise_kernel");
-    return 0;
+    return launch_noise((unsigned long long)plan->rng_seed, (unsigned long long)step, plan->B, eps_out, (hipStream_t)stream);
 }
 
 extern "C" int dvae_train_profile(int enable) {

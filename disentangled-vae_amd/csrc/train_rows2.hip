@@ -11,7 +11,7 @@
 //                      backward phases and committed once the output-gradient tile has been consumed.
 // Both roles run the same sequence of workgroup barriers (the phase list below); a helper always transposes the
 // buffer the chain is reading in that phase (both only read it), while the chain's epilogue fills the other one.
-// Compared with the 4-wave kernel of train_fused.hip (one wave per SIMD, 512 registers, 136 of them staging
+// Compared with the 4-wave kernel of train_rows1.hip (one wave per SIMD, 512 registers, 136 of them staging
 // registers, stash stores and tile loads on the chain's critical path): <= 256 registers per wave, a second
 // instruction stream per SIMD, the loss epilogue reads x straight from global memory into registers (no LDS slices,
 // no barriers inside the output layer), and the label part of decoder layer 1 is computed while the label tile is

@@ -85,7 +85,7 @@ typedef struct {
     int64_t  row_count;
     uint64_t bad_row_counter;
     /* rows kernel generation chosen by dvae_train_plan: 2 = 8-wave chain + helper kernel (csrc/train_rows2.hip; M1 / M2 with
-       bf16 or bf16x3 operands), 1 = 4-wave kernel (csrc/train_fused.hip; every model and policy).  Environment override
+       bf16 or bf16x3 operands), 1 = 4-wave kernel (csrc/train_rows1.hip; every model and policy).  Environment override
        DVAE_ROWS=1 at plan time. */
     int32_t  rows_kernel;
     int32_t  reserved1;

@@ -1,5 +1,5 @@
 """The optimizer launch of the fused train step (csrc/apply_common.hpp: slab_sum_at, adam_element, apply_element; apply_kernel in
-csrc/train_fused.hip; make_apply_args) and the layer-level dvae_adam_step (csrc/losses.hip) against float64, PER ELEMENT, from the
+csrc/train_wgrad.hip; make_apply_args in csrc/train_fused.hip) and the layer-level dvae_adam_step (csrc/losses.hip) against float64, PER ELEMENT, from the
 kernel's own inputs: the slabs it summed and the p, m, v it read.  The bound is derived in tests/adam_bounds.py (a few float32
 roundings per element; tests/test_adam_bounds_cpu.py shows it sound and sharp); no element is exempted and no share may be off.
 
