@@ -76,6 +76,8 @@ SIGNATURES = {
                                c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dvae_mix_snr_workspace_bytes": (c_sz, [c_i64, c_i]),
     "dvae_mix_snr_batch": (c_i, [c_vp, c_i64, c_i, c_vp, c_i64, c_i, c_i, c_vp, c_i64, c_vp, c_i, c_vp, c_vp, c_vp, c_i64, c_i, c_vp, c_vp, c_vp]),
+    "dvae_resample_run": (c_i, [c_i, c_i, c_i]),
+    "dvae_resample_batch": (c_i, [c_vp, c_i64, c_i, c_i64, c_vp, c_i64, c_i, c_i, c_vp, c_i64, c_vp, c_i, c_i, c_i, c_vp]),
     # include/dvae_train.h (plan pointers are passed with ctypes.byref)
     "dvae_train_plan": (c_i, [c_i, c_i, c_i, c_i64, c_i, c_vp]),
     "dvae_train_init": (c_i, [c_vp, c_vp, c_vp, c_vp]),

@@ -4,11 +4,14 @@ launches whatever the number of conditions), then written as <name>_s.wav, <name
 
     python examples/build_test_set.py --speech a.wav b.wav --noise cafe.wav car.wav --snr -5 0 5 --out test_set/
     python examples/build_test_set.py --synthetic 8 --snr -5 0 5        # no data at hand: speech-like signals and noise banks from a seed
+    python examples/build_test_set.py --speech a.wav --noise CAFE-CAFE-1.wav --noise-fs 48000      # raw recordings, resampled on the device
 
 Every utterance meets every noise recording at every SNR (NTCD-TIMIT's layout: each utterance under 6 noises x 6 SNRs).  The segment
 starts come from a seeded numpy Generator; the reference draws them from the global np.random inside a thread pool, so its choice
-is not reproducible and no parity with it is claimed.  The noise recordings must already be at 16 kHz: the reference's resampling of
-the raw QUT recordings (preprocess_noise) is not part of this path.  <out>/stats.npy holds p, Ps, Pn, k, norm and the achieved SNR
+is not reproducible and no parity with it is claimed.  The noise recordings are at 16 kHz, or with --noise-fs N at N Hz (the raw
+48 kHz QUT recordings, any channel count): those are brought to 16 kHz on the device by packages/dataset/qut_database.py:
+preprocess_noise_many (first channel, one launch for all of them; a file named like the car recording gets the reference's cut) and
+stay there for the mixer.  <out>/stats.npy holds p, Ps, Pn, k, norm and the achieved SNR
 of every mixture (mix.STATS), <out>/conditions.txt their names.
 """
 import argparse
@@ -23,14 +26,17 @@ from scipy.io import wavfile
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 mixer = importlib.import_module("disentangled-vae_amd.mix")
+from packages.dataset import qut_database
 FS = 16000
 
 
-def read_wav(path):
+def read_wav(path, fs_want=FS, channels=False):
     fs, w = wavfile.read(path)
-    if fs != FS:
-        raise ValueError(f"{path}: {FS} Hz expected, got {fs}")       # create_test_set.py:98: 'Unexpected sampling rate'
-    if w.ndim != 1:
+    if fs != fs_want:
+        raise ValueError(f"{path}: {fs_want} Hz expected, got {fs}")  # create_test_set.py:98: 'Unexpected sampling rate'
+    if channels:
+        w = w.reshape(len(w), -1)                                     # [n, C], as soundfile hands the reference its recordings
+    elif w.ndim != 1:
         raise ValueError(f"{path}: one channel expected")
     return w.astype(np.float64) / 32768.0 if w.dtype == np.int16 else w.astype(np.float32 if w.dtype == np.float32 else np.float64)
 
@@ -42,9 +48,9 @@ def synthetic_speech(seconds, seed):
     return env * rng.standard_normal(n) * np.sin(2 * np.pi * 220 * np.arange(n) / FS + rng.random())
 
 
-def synthetic_noise(seconds, seed, tilt):
+def synthetic_noise(seconds, seed, tilt, fs=FS):
     rng = np.random.default_rng(seed)
-    w = rng.standard_normal(int(FS * seconds) + 1)
+    w = rng.standard_normal(int(fs * seconds) + 1)
     return 0.1 * (w[1:] + tilt * w[:-1])
 
 
@@ -53,6 +59,8 @@ def main():
     ap.add_argument("--speech", nargs="*", default=[], help="clean utterances (16 kHz wav)")
     ap.add_argument("--noise", nargs="*", default=[], help="long noise recordings (16 kHz wav), each longer than every utterance")
     ap.add_argument("--synthetic", type=int, default=0, help="number of synthetic 3-4 s utterances (and two 10 s noise banks) instead of files")
+    ap.add_argument("--noise-fs", type=int, default=FS, metavar="N", help="sampling rate of the noise recordings (or of the synthetic banks): "
+                    "anything but 16000 is resampled to 16 kHz on the device, first channel, before mixing")
     ap.add_argument("--snr", type=float, nargs="+", default=[-15.0, -10.0, -5.0, 0.0, 5.0], help="target SNRs in dB (create_test_set.py:142)")
     ap.add_argument("--seed", type=int, default=0, help="seed of the segment starts")
     ap.add_argument("--float32", action="store_true", help="keep the outputs in float32 on the device (one more rounding)")
@@ -61,14 +69,20 @@ def main():
     if a.synthetic:
         speech = [synthetic_speech(3.0 + 0.25 * (i % 5), i) for i in range(a.synthetic)]
         names = [f"synthetic_{i:02d}" for i in range(a.synthetic)]
-        banks, noise_names = [synthetic_noise(10.0, 1000 + b, 0.9 * b) for b in range(2)], ["white", "pink"]
+        banks, noise_names = [synthetic_noise(10.0, 1000 + b, 0.9 * b, a.noise_fs) for b in range(2)], ["white", "pink"]
+        if a.noise_fs != FS:
+            banks = [np.stack([b, -b], axis=1) for b in banks]        # two channels, like a raw recording
     else:
         if not a.speech or not a.noise:
             ap.error("give --speech and --noise files, or --synthetic N")
         speech, names = [read_wav(p) for p in a.speech], [os.path.splitext(os.path.basename(p))[0] for p in a.speech]
-        banks, noise_names = [read_wav(p) for p in a.noise], [os.path.splitext(os.path.basename(p))[0] for p in a.noise]
+        banks, noise_names = [read_wav(p, a.noise_fs, a.noise_fs != FS) for p in a.noise], [os.path.splitext(os.path.basename(p))[0] for p in a.noise]
 
     t0 = time.perf_counter()
+    if a.noise_fs != FS:
+        car = qut_database._TEST_FILES["car"][:-4]
+        raw = {("car" if name == car else f"{i}:{name}"): b for i, (name, b) in enumerate(zip(noise_names, banks))}
+        banks = list(qut_database.preprocess_noise_many(raw, a.noise_fs, FS).values())          # on the device, in the order given
     speech_index, noise_index, snr_db = mixer.condition_grid(len(speech), noise_names, a.snr)
     grid = [speech[u] for u in speech_index]                       # the same array many times: packed and uploaded once
     starts = mixer.draw_noise_starts(np.random.default_rng(a.seed), [len(b) for b in banks], noise_index, [len(s) for s in grid])

@@ -373,6 +373,38 @@ int dvae_estoi_batch(const void* x, int64_t n_x, int x_f64, const void* y, int64
                      const double* taps, int p, int q, int L, const double* window, const int64_t* bands, int extended, double* d,
                      int64_t* info, double* tob, void* workspace, void* stream);
 
+/* ---- resampling (packages/dataset/qut_database.py:63-83: preprocess_noise) ----
+ * dvae_resample_batch: U signals resampled by the rational factor p / q in one launch on `stream`, no host synchronisation, no
+ *   atomics, double arithmetic.  The contract is the algorithm below -- the one of step 1 of dvae_estoi_batch, for any target rate --
+ *   restated in numpy by tests/estoi_ref.py::resample; the reference's librosa.resample (resampy's kaiser_best table) is not
+ *   available to this repository, so parity with it is unpinned.
+ *   Given odd-length taps h[0 .. 2 L] (float64), integers p, q >= 1 with p != q, and a signal x[0 .. n - 1]:
+ *   - the output has ceil(n p / q) samples;
+ *   - out[k] = p sum_t h[j0 + t p] x[src0 + t] with j0 = (L - k q) mod p, src0 = (k q + j0 - L) / p (the division is exact),
+ *     t = 0 .. nt - 1, nt = (2 L - j0) / p + 1 (no term when j0 > 2 L), x zero outside [0, n);
+ *   - the sum is accumulated in double from 0.0 with t ascending, one fma per tap, and then multiplied by (double)p; a float32 input
+ *     converts to double exactly; a float32 output is the double result rounded once.
+ *   The order is fixed, so a signal's output does not depend on the tiling, on its place in the batch or on the batch, and repeats
+ *   bit for bit.  This is scipy.signal.resample_poly(x, p, q, window=h) up to the order of the sum.
+ *   x is a device buffer of n_x elements, float64 when x_f64, else float32; sample i of signal u is x[x0[u] + i stride] (stride >= 1
+ *   elements: channel c of an interleaved [n, C] recording is x0 = c, stride = C, read in place).  y is a device buffer of n_y
+ *   elements, float64 when y_f64, else float32; signal u writes y[y0[u] ... y0[u] + ceil(len[u] p / q)), nothing else is touched;
+ *   output ranges may not overlap and y may not alias x.
+ *   taps (device, float64) are PHASE-MAJOR, [p][nt_max] with nt_max = 2 L / p + 1: taps[j0 nt_max + t] = h[j0 + t p], 0 past the
+ *   row's own nt (never read).  p, q <= 2^15, L <= 2^24 as in dvae_estoi_batch.
+ *   tables (device int64) = [items (U + 1) | x0 (U) | len (U) | y0 (U)], 1 <= len <= 2^31.  A work item is one signal and a run of
+ *   dvae_resample_run(p, q, L) of its outputs, items[u + 1] - items[u] = ceil(ceil(len[u] p / q) / run), items[U] = n_items.  The
+ *   run is the largest multiple of 64 p (p <= 16; else of 64), at most DVAE_RESAMPLE_MAX_RUN, whose input span ceil((run - 1) q / p) +
+ *   1 + nt_max fits the DVAE_RESAMPLE_SPAN samples that a wave stages in LDS; a ratio and filter whose smallest run does not fit
+ *   (dvae_resample_run = 0: roughly q / p > 16, or more than a thousand taps per output) is refused with DVAE_E_BADARG.  The kernel
+ *   checks every table entry against n_x, n_y and the item counts before touching memory: a bad entry drops that signal's work (its
+ *   outputs stay as they were). */
+#define DVAE_RESAMPLE_SPAN 1240
+#define DVAE_RESAMPLE_MAX_RUN 4096
+int dvae_resample_run(int p, int q, int L);
+int dvae_resample_batch(const void* x, int64_t n_x, int x_f64, int64_t stride, void* y, int64_t n_y, int y_f64, int U,
+                        const int64_t* tables, int64_t n_items, const double* taps, int p, int q, int L, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
