@@ -24,6 +24,7 @@
 // Every table entry is rechecked against the scalar extents before memory is touched (es_utterance, by every kernel): a bad entry
 // drops that utterance's work and the finish writes NaN (info -1).
 #include <math.h>
+#include "fft_wave.hpp"
 #include "ragged.hpp"
 
 namespace dvae {
@@ -203,19 +204,15 @@ __global__ __launch_bounds__(256) void es_mask_kernel(EsIn in, const double* __r
 }
 
 // ---- 4: overlap-add of the kept frames, 256-in-512 real FFT, third-octave bands ----------------------------------------------------
-struct ec { double x, y; };
-__device__ __forceinline__ ec ec_add(ec a, ec b) { return ec{a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ ec ec_sub(ec a, ec b) { return ec{a.x - b.x, a.y - b.y}; }
-__device__ __forceinline__ ec ec_mul(ec a, double wr, double wi) { return ec{a.x * wr - a.y * wi, a.x * wi + a.y * wr}; }
 __device__ __forceinline__ int es_pad(int i) { return i + (i >> 2); }
 
-__device__ __forceinline__ void es_dft4(ec (&a)[4]) {             // forward, natural order
-    const ec t0 = ec_add(a[0], a[2]), t1 = ec_sub(a[0], a[2]), t2 = ec_add(a[1], a[3]), d = ec_sub(a[1], a[3]);
-    const ec t3 = ec{d.y, -d.x};                                  // * -i
-    a[0] = ec_add(t0, t2);
-    a[2] = ec_sub(t0, t2);
-    a[1] = ec_add(t1, t3);
-    a[3] = ec_sub(t1, t3);
+__device__ __forceinline__ void es_dft4(cd (&a)[4]) {             // forward, natural order
+    const cd t0 = cadd(a[0], a[2]), t1 = csub(a[0], a[2]), t2 = cadd(a[1], a[3]), d = csub(a[1], a[3]);
+    const cd t3 = cd{d.y, -d.x};                                  // * -i
+    a[0] = cadd(t0, t2);
+    a[2] = csub(t0, t2);
+    a[1] = cadd(t1, t3);
+    a[3] = csub(t1, t3);
 }
 
 // 256-point complex forward FFT of one wave whose points 128 ... 255 are zero: z0 = point lane, z1 = point lane + 64 in,
@@ -230,12 +227,12 @@ struct EsFft256 {
             for (int r = 1; r < 4; ++r) sincospi(-2.0 * (double)(r * (lane & (Ns - 1))) / (double)(4 * Ns), &ti[p][r - 1], &tr[p][r - 1]);
         }
     }
-    __device__ __forceinline__ void run(ec z0, ec z1, ec (&v)[4], double* re, double* im, int lane) const {
+    __device__ __forceinline__ void run(cd z0, cd z1, cd (&v)[4], double* re, double* im, int lane) const {
         // pass Ns = 1 with points 2 and 3 zero: X_r = z0 + (-i)^r z1; outputs to lane * 4 + r
-        v[0] = ec_add(z0, z1);
-        v[1] = ec{z0.x + z1.y, z0.y - z1.x};
-        v[2] = ec_sub(z0, z1);
-        v[3] = ec{z0.x - z1.y, z0.y + z1.x};
+        v[0] = cadd(z0, z1);
+        v[1] = cd{z0.x + z1.y, z0.y - z1.x};
+        v[2] = csub(z0, z1);
+        v[3] = cd{z0.x - z1.y, z0.y + z1.x};
 #pragma unroll
         for (int r = 0; r < 4; ++r) { const int i = es_pad(lane * 4 + r); re[i] = v[r].x; im[i] = v[r].y; }
         __builtin_amdgcn_wave_barrier();
@@ -243,9 +240,9 @@ struct EsFft256 {
         for (int p = 0; p < 3; ++p) {
             const int Ns = 4 << (2 * p);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { const int i = es_pad(lane + 64 * r); v[r] = ec{re[i], im[i]}; }
+            for (int r = 0; r < 4; ++r) { const int i = es_pad(lane + 64 * r); v[r] = cd{re[i], im[i]}; }
 #pragma unroll
-            for (int r = 1; r < 4; ++r) v[r] = ec_mul(v[r], tr[p][r - 1], ti[p][r - 1]);
+            for (int r = 1; r < 4; ++r) v[r] = cmulc(v[r], tr[p][r - 1], ti[p][r - 1]);
             es_dft4(v);
             __builtin_amdgcn_wave_barrier();
             if (p < 2) {
@@ -302,8 +299,8 @@ __global__ __launch_bounds__(256) void es_tob_kernel(EsIn in, const double* __re
                     v1[c] = w1[c] * (d + e);
                 }
             }
-            ec v[4];
-            fft.run(ec{v0[0], v0[1]}, ec{v1[0], v1[1]}, v, re, im, lane);
+            cd v[4];
+            fft.run(cd{v0[0], v0[1]}, cd{v1[0], v1[1]}, v, re, im, lane);
             // real-FFT split: X[k] = (Z[k] + conj Z[256 - k]) / 2 + exp(-2 pi i k / 512) (Z[k] - conj Z[256 - k]) / (2 i)
 #pragma unroll
             for (int q = 0; q < 4; ++q) { const int i = es_pad(lane + 64 * q); re[i] = v[q].x; im[i] = v[q].y; }
@@ -312,11 +309,11 @@ __global__ __launch_bounds__(256) void es_tob_kernel(EsIn in, const double* __re
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int i = es_pad((256 - (lane + 64 * q)) & 255);
-                const ec zc = ec{re[i], -im[i]};
-                const ec ev = ec{0.5 * (v[q].x + zc.x), 0.5 * (v[q].y + zc.y)};
-                const ec dd = ec_sub(v[q], zc);
-                const ec od = ec_mul(ec{0.5 * dd.y, -0.5 * dd.x}, sr[q], si[q]);
-                const ec X = ec_add(ev, od);
+                const cd zc = cd{re[i], -im[i]};
+                const cd ev = cd{0.5 * (v[q].x + zc.x), 0.5 * (v[q].y + zc.y)};
+                const cd dd = csub(v[q], zc);
+                const cd od = cmulc(cd{0.5 * dd.y, -0.5 * dd.x}, sr[q], si[q]);
+                const cd X = cadd(ev, od);
                 pw[q] = X.x * X.x + X.y * X.y;
             }
             __builtin_amdgcn_wave_barrier();

@@ -1,8 +1,9 @@
 """Host side of STFT / ISTFT: integer / indexing decisions in Python doubles exactly
 as the reference makes them (packages/processing/stft.py:34-50: window length, hop,
-the floating-point end-pad rule, quirk Q6), then the device kernels of
-csrc/stft.hip through the C ABI.  No CPU transform exists here: without the
-library or a GPU these functions raise.
+the floating-point end-pad rule, quirk Q6), then the C ABI of csrc/stft.hip
+(host entries and dispatch; the kernels are in csrc/stft_fwd.hip and
+csrc/istft.hip).  No CPU transform exists here: without the library or a GPU
+these functions raise.
 """
 import math
 import os
