@@ -181,10 +181,13 @@ class McemBatch:
         i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
         return starts, pos, i32(starts), i32(counts), i32(tile_seg)
 
-    def init_parameters(self, X_list, y_list=None, device="cuda"):
+    def init_parameters(self, X_list, y_list=None, device="cuda", use="hard"):
         """X_list: complex mixture STFTs (F, N_u) (numpy), or a SpecBatch of complex frames (stft.stft_batch) that stays on the
         device: |X|^2 is then formed there (dvae_mcem_spec_init, the same bits) and run() keeps the Wiener gains there for enhance().
-        y_list: labels (y_dim, N_u) tensors/arrays or None."""
+        y_list: labels (y_dim, N_u) tensors/arrays, a LabelBatch (classify.classify_batch) whose `use` labels ("hard" as the
+        reference's evaluation hands them over, or "soft") are taken device to device, or None."""
+        from .classify import LabelBatch
+        labels = y_list if isinstance(y_list, LabelBatch) else None
         spec = X_list if isinstance(X_list, STFT.SpecBatch) else None
         counts = list(spec.counts) if spec is not None else [x.shape[1] for x in X_list]
         for u, c in enumerate(counts):
@@ -201,6 +204,10 @@ class McemBatch:
         self.X_list = None if spec is not None else X_list
         self._S_hat = self._N_hat = None
         self._bufs = None                    # the M-step workspace depends on the utterance count, not only on the padded frame total
+        if labels is not None and list(labels.counts) != counts:
+            bad = next((u for u, (a, b) in enumerate(zip(labels.counts, counts)) if a != b), min(len(labels.counts), len(counts)))
+            raise ValueError(f"McemBatch.init_parameters: utterance {bad}: the LabelBatch's frame counts differ from the spectrograms' "
+                             f"({len(labels.counts)} and {len(counts)} utterances)")
         self.counts = counts
         self.starts, self.ntot, self.seg_start, self.seg_count, self.tile_seg = self._layout(self.counts, dev)
         U, K = len(self.counts), self.K
@@ -217,7 +224,7 @@ class McemBatch:
         self.W = torch.empty((U, F_BINS, K), dtype=torch.float32, device=dev)
         self.y = None
         if self.label_in_decoder:
-            y_dim = y_list[0].shape[0]
+            y_dim = labels.y_dim if labels is not None else y_list[0].shape[0]
             self.y = torch.zeros((y_dim, self.ntot), dtype=torch.float32, device=dev)
         for u in range(U):
             s, c = self.starts[u], self.counts[u]
@@ -227,7 +234,7 @@ class McemBatch:
             self.H[:, s:s + c] = torch.clamp_min(torch.rand(K, c, device=dev), self.eps)           # mcem.py:43
             self.Vb[:, s:s + c] = self.W[u] @ self.H[:, s:s + c]                                    # mcem.py:52
             if self.y is not None:
-                self.y[:, s:s + c] = torch.as_tensor(y_list[u], dtype=torch.float32).to(dev)
+                self.y[:, s:s + c] = labels.view(u, use).to(dev) if labels is not None else torch.as_tensor(y_list[u], dtype=torch.float32).to(dev)
         enc_in = torch.cat([self.X2, self.y], dim=0) if self.label_in_encoder else self.X2
         with torch.no_grad():
             _, mu, _ = self.vae.encoder(torch.t(enc_in))                                            # mcem.py:200, 364

@@ -78,6 +78,9 @@ SIGNATURES = {
     "dvae_mix_snr_batch": (c_i, [c_vp, c_i64, c_i, c_vp, c_i64, c_i, c_i, c_vp, c_i64, c_vp, c_i, c_vp, c_vp, c_vp, c_i64, c_i, c_vp, c_vp, c_vp]),
     "dvae_resample_run": (c_i, [c_i, c_i, c_i]),
     "dvae_resample_batch": (c_i, [c_vp, c_i64, c_i, c_i64, c_vp, c_i64, c_i, c_i, c_vp, c_i64, c_vp, c_i, c_i, c_i, c_vp]),
+    "dvae_classify_weights_floats": (c_sz, [c_i]),
+    "dvae_classify_batch": (c_i, [c_vp, c_i, c_i64, c_i64, c_i, c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp]),
+    "dvae_label_counts_batch": (c_i, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i, c_i, c_vp, c_vp, c_vp, c_vp]),
     # include/dvae_train.h (plan pointers are passed with ctypes.byref)
     "dvae_train_plan": (c_i, [c_i, c_i, c_i, c_i64, c_i, c_vp]),
     "dvae_train_init": (c_i, [c_vp, c_vp, c_vp, c_vp]),

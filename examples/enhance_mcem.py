@@ -9,9 +9,14 @@ device between the batch STFT and the waveforms.
     python examples/enhance_mcem.py --synthetic 8 --snr -5 0 5 --score  # every utterance mixed on the device at each SNR (create_test_set.py's
                                                                         # mixing: disentangled-vae_amd/mix.py); --score adds SI-SIR and SI-SAR
 
-The labels y fed to the M2 decoder are the time-domain VAD of the mixture (packages/processing/target.py); the
-reference's evaluate script takes them from a video classifier or from the clean signal (oracle), neither of which
-ships with it.  Writes <name>_s_est.wav and <name>_n_est.wav like the reference (evaluate_ntcd_M2.py:232-245).
+    python examples/enhance_mcem.py --synthetic 8 --labels classifier --score   # the M2_info flow: labels from the model's own classifier
+
+--labels vad (the default): the labels y fed to the M2 decoder are the time-domain VAD of the mixture
+(packages/processing/target.py); the reference's evaluate_ntcd_M2.py takes them from a video classifier or from the clean signal
+(oracle), neither of which ships with it.  --labels classifier: the flow of scripts/evaluate_ntcd_M2_info_vad.py:175-219 -- a
+DeepGenerativeModel_v5 (M2_info) whose classifier labels every frame of the mixtures' SpecBatch in one launch
+(disentangled-vae_amd/classify.py: classify_batch), the hard labels going to the M2v3 variant of MCEM device to device; --score
+then adds the F1 of those labels against the clean speech's VAD (f1_batch).  Writes <name>_s_est.wav and <name>_n_est.wav like the reference (evaluate_ntcd_M2.py:232-245).
 """
 import argparse
 import importlib
@@ -24,7 +29,7 @@ import torch
 from scipy.io import wavfile
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from packages.models.models import DeepGenerativeModel
+from packages.models.models import DeepGenerativeModel, DeepGenerativeModel_v5
 from packages.processing.target import clean_speech_VAD
 
 McemBatch = importlib.import_module("disentangled-vae_amd.mcem").McemBatch
@@ -32,6 +37,8 @@ stft_batch = importlib.import_module("disentangled-vae_amd.stft").stft_batch
 si_sdr_batch = importlib.import_module("disentangled-vae_amd.metrics").si_sdr_batch
 estoi_batch = importlib.import_module("disentangled-vae_amd.metrics").estoi_batch
 mix_at_snr_batch = importlib.import_module("disentangled-vae_amd.mix").mix_at_snr_batch
+classify = importlib.import_module("disentangled-vae_amd.classify")
+utterances_to_frames = importlib.import_module("disentangled-vae_amd.target").utterances_to_frames
 STFT = dict(fs=16000, wlen_sec=64e-3, win="hann", hop_percent=0.25, center=False)      # evaluate_ntcd_M2.py:37-45
 
 
@@ -62,7 +69,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--wav", nargs="*", default=[])
     ap.add_argument("--synthetic", type=int, default=0, help="number of synthetic 3-4 s mixtures instead of --wav")
-    ap.add_argument("--checkpoint", default=None, help="M2 (y_dim 1) state_dict; random weights when absent")
+    ap.add_argument("--checkpoint", default=None, help="M2 (y_dim 1) state_dict, or M2_info with --labels classifier; random weights when absent")
+    ap.add_argument("--labels", choices=["vad", "classifier"], default="vad", help="where the decoder's labels come from: the mixture's "
+                    "time-domain VAD, or the classifier of an M2_info model on the device")
     ap.add_argument("--niter", type=int, default=100)
     ap.add_argument("--precision", choices=["fp32", "bf16"], default="fp32")
     ap.add_argument("--out", default="enhanced")
@@ -86,7 +95,7 @@ def main():
     if not waves:
         ap.error("give --wav files or --synthetic N")
     torch.manual_seed(0)
-    vae = DeepGenerativeModel([513, 1, 16, [128, 128]], None)
+    vae = DeepGenerativeModel_v5([513, 1, 16, [128, 128]]) if a.labels == "classifier" else DeepGenerativeModel([513, 1, 16, [128, 128]], None)
     if a.checkpoint:
         vae.load_state_dict(torch.load(a.checkpoint, map_location="cpu", weights_only=True))
     vae = vae.cuda().eval()
@@ -112,10 +121,17 @@ def main():
     else:
         # every mixture's STFT in one launch, kept on the device: (513, N_u) complex64 per utterance, frame-major and packed
         X = stft_batch(waves, pad_mode="reflect", pad_at_end=True, **STFT)
-    Y = [clean_speech_VAD(w, fs=16000, wlen_sec=64e-3, hop_percent=0.25, center=False, pad_mode="reflect", pad_at_end=True,
-                          vad_threshold=1.70) for w in waves]                                              # (1, N_u)
-    mb = McemBatch(vae, niter=a.niter, nsamples_E_step=10, burnin_E_step=30, nsamples_WF=25, burnin_WF=75, var_RW=0.01,
-                   nmf_rank=10, precision=a.precision)                                                      # evaluate_ntcd_M2.py:92-99
+    if a.labels == "classifier":
+        # y_hat_soft = model.classifier(|X|^2), y_hat_hard = y_hat_soft > 0.5 for every frame of the batch in one launch; the LabelBatch
+        # stays on the device and MCEM_M2v3 (labels in the decoder only) takes its hard labels from there
+        Y = classify.classify_batch(vae.enc_dec_clf.classifier, X)
+        mb = McemBatch(vae.enc_dec_clf, niter=a.niter, nsamples_E_step=10, burnin_E_step=30, nsamples_WF=25, burnin_WF=75, var_RW=0.01,
+                       nmf_rank=10, precision=a.precision, label_in_encoder=False, label_in_decoder=True)
+    else:
+        Y = [clean_speech_VAD(w, fs=16000, wlen_sec=64e-3, hop_percent=0.25, center=False, pad_mode="reflect", pad_at_end=True,
+                              vad_threshold=1.70) for w in waves]                                              # (1, N_u)
+        mb = McemBatch(vae, niter=a.niter, nsamples_E_step=10, burnin_E_step=30, nsamples_WF=25, burnin_WF=75, var_RW=0.01,
+                       nmf_rank=10, precision=a.precision)                                                      # evaluate_ntcd_M2.py:92-99
     mb.init_parameters(X, Y)
     cost = mb.run()
     # Wiener filtering and ISTFT of both estimates in one launch: istft(S_hat, max_len=len(w)) / istft(N_hat, ...) per utterance
@@ -139,6 +155,14 @@ def main():
         for name, m, e, im, ie in zip(names, sdr_mix, sdr_est, ei_mix, ei_est):
             print(f"{name:<16}{m:>16.2f}{e:>17.2f}{'':>7}{im:>16.3f}{ie:>16.3f}")
         print(f"{'mean':<16}{sdr_mix.mean():>16.2f}{sdr_est.mean():>17.2f}{'':>7}{ei_mix.mean():>16.3f}{ei_est.mean():>16.3f}")
+        if a.labels == "classifier":
+            # the labels' score against the clean speech's VAD (run_metrics_classif.py:136), counted on the device; the truth's frames
+            # are those of the mixtures' STFT (the same lengths and the same end pad)
+            truth = utterances_to_frames(clean.numpy() if mix is not None else clean, "vad_labels", device="cuda")
+            f1 = classify.f1_batch(Y, truth).cpu().numpy()
+            print(f"{'utterance':<24}{'accuracy':>10}{'precision':>11}{'recall':>10}{'F1':>10}")
+            for name, r in zip(names, f1):
+                print(f"{name:<24}{r[0]:>10.3f}{r[1]:>11.3f}{r[2]:>10.3f}{r[3]:>10.3f}")
         if mix is not None:
             # the mixer's noise is at the mixture's scale, which is what SI-SIR and SI-SAR need (energy_ratios, packages/metrics.py:39-60)
             ratios = mb.score(mix.speech, mix.noise, max_len=[len(w) for w in waves], trim=a.trim).cpu().numpy()

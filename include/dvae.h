@@ -405,6 +405,37 @@ int dvae_resample_run(int p, int q, int L);
 int dvae_resample_batch(const void* x, int64_t n_x, int x_f64, int64_t stride, void* y, int64_t n_y, int y_f64, int U,
                         const int64_t* tables, int64_t n_items, const double* taps, int p, int q, int L, void* stream);
 
+/* ---- classifier labels and their scores (scripts/evaluate_ntcd_M2_info_vad.py:175-219, packages/models/utils.py:120-159) ----
+ * dvae_classify_batch: the reference's Classifier without batch norm (packages/models/models.py:41-63), 513 -> 128 (relu) -> 128
+ *   (relu) -> y_dim (sigmoid), y_dim 1 or 513, over the frames of a ragged batch in one launch on `stream`, no host synchronisation,
+ *   no atomics, float32 throughout.
+ *   Input, N rows: src_complex = 1: complex64 frames [N][513] (what dvae_stft_batch writes in layout 2, ld = 513); the power of a bin
+ *   is formed in the kernel as a = numpy's complex64 magnitude (larger * sqrt(fma(r, r, 1)), r = smaller / larger, correctly rounded
+ *   float32 operations), p = a * a rounded once -- the bits of dvae_mcem_spec_init and of `(np.abs(X) ** 2).astype(np.float32)`.
+ *   src_complex = 0: float32 power rows, row r at src + r ld, ld >= 513.
+ *   weights (device, float32, dvae_classify_weights_floats(y_dim) of them; 0 for a y_dim not covered): the state_dict tensors in
+ *   their own [out][in] layout, one after the other: W1 [128][513] | b1 [128] | W2 [128][128] | b2 [128] | W3 [y_dim][128] | b3 [y_dim].
+ *   Per frame with power p:  h1[j] = max(0, (sum_k p[k] W1[j][k]) + b1[j]);  h2[j] = max(0, (sum_k h1[k] W2[j][k]) + b2[j]);
+ *   logit[c] = (sum_k h2[k] W3[c][k]) + b3[c];  soft = 1 / (1 + expf(-logit));  hard = soft > 0.5 ? 1 : 0, decided from the float32
+ *   soft that is stored.  Every sum is ONE float32 chain from 0 with k ascending (on the matrix unit two products per step, as
+ *   v_mfma_f32_32x32x2_f32 adds them; layer 1 is padded with zero products to k = 544), the bias added after it: the order does not
+ *   depend on the frame's place in a tile, on the tile's place in the grid or on the batch, so a frame gives the same bits alone, in
+ *   any batch and from run to run.
+ *   frame_off_host (HOST int64 [U + 1]): utterance u is rows frame_off[u] .. frame_off[u + 1] - 1.  It is checked here, before
+ *   anything is launched: 0 <= frame_off[0], non-decreasing, frame_off[U] <= N, else DVAE_E_BADARG naming the utterance.  Rows
+ *   outside [frame_off[0], frame_off[U]) are neither read nor written.
+ *   soft, hard [N][y_dim] float32 (the training layout of Y); logits [N][y_dim] or NULL.
+ * dvae_label_counts_batch: the confusion counts of f1_loss per utterance.  pred, truth: float32 rows [N][y_dim] with leading dimensions
+ *   ldp, ldt >= y_dim; an element counts as 1 when it is not zero.  counts [U][4] int64 = tp, tn, fp, fn over all y_dim (frame_off[u + 1]
+ *   - frame_off[u]) elements of utterance u; zeroed and then added to with integer vector atomics on `stream` (integer sums: any
+ *   order gives the same result).  frame_off_host is checked as above; frame_off_dev is the same table on the device (the kernel
+ *   clamps what it reads from it to [frame_off[0], frame_off[U]], so a copy that differs miscounts but reads nothing outside the rows). */
+size_t dvae_classify_weights_floats(int y_dim);
+int dvae_classify_batch(const void* src, int src_complex, int64_t ld, int64_t N, int U, const int64_t* frame_off_host,
+                        const float* weights, int y_dim, float* soft, float* hard, float* logits, void* stream);
+int dvae_label_counts_batch(const float* pred, int64_t ldp, const float* truth, int64_t ldt, int64_t N, int y_dim, int U,
+                            const int64_t* frame_off_host, const int64_t* frame_off_dev, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,3 +54,7 @@ def target_dev():
 
 def metrics_dev():
     return _mod("metrics")
+
+
+def classify():
+    return _mod("classify")

@@ -4,7 +4,8 @@ Every loss -- `elbo` (reference utils.py:73-76), the `binary_cross_entropy` fami
 `ikatura_saito_divergence` (:68-105) and the squared-error mask / signal / magnitude-spectrum losses (:107-118) -- runs as HIP
 reduction kernels with hand-written backward when its inputs are CUDA tensors (disentangled-vae_amd/ops.py: Elbo, Bce, Bce2,
 IsRows, SqErr; csrc/losses.hip); host tensors take the reference's own ATen expression (its CPU mode).  The label helpers
-(`enumerate_discrete`, `onehot`, `log_sum_exp`, `f1_loss`) are bookkeeping, not losses, and stay plain tensor code.
+(`enumerate_discrete`, `onehot`, `log_sum_exp`, `f1_loss`) are bookkeeping, not losses, and stay plain tensor code; `f1_loss_many` scores a
+list of utterances at once (CUDA tensors: one launch, disentangled-vae_amd/classify.py f1_batch).
 """
 import torch
 from torch.autograd import Variable
@@ -169,3 +170,27 @@ def f1_loss(y_hat_hard: torch.Tensor, y: torch.Tensor, epsilon=1e-8) -> torch.Te
     recall = tp / (tp + fn + epsilon)
     f1 = 2 * (precision * recall) / (precision + recall + epsilon)
     return accuracy, precision, recall, f1
+
+
+def f1_loss_many(y_hat_hard_list, y_list, epsilon=1e-8):
+    """[f1_loss(y_hat_hard, y, epsilon) for each pair] -> list of (accuracy, precision, recall, f1) tuples of 0-dim tensors, bit for
+    bit.  CUDA tensors: the confusion counts of all utterances come from one launch (classify.f1_batch); host tensors: the loop."""
+    preds, truths = list(y_hat_hard_list), list(y_list)
+    if len(preds) != len(truths):
+        raise ValueError(f"f1_loss_many: {len(preds)} predictions, {len(truths)} truths")
+    if not preds or not all(_on_gpu(p, t) for p, t in zip(preds, truths)):
+        return [f1_loss(p, t, epsilon) for p, t in zip(preds, truths)]
+    rows = [[], []]
+    for u, (p, t) in enumerate(zip(preds, truths)):
+        p, t = p.detach(), t.detach()
+        if t.ndim != 1 or p.ndim not in (1, 2):
+            raise AssertionError("f1_loss: y must be 1-D and y_hat_hard 1-D or 2-D")
+        if p.ndim == 2:
+            p = p.argmax(dim=1)
+        if p.numel() != t.numel() or p.numel() == 0:
+            raise ValueError(f"f1_loss_many: utterance {u}: {p.numel()} predictions, {t.numel()} truths")
+        rows[0].append(p.to(torch.float32))
+        rows[1].append(t.to(torch.float32))
+    C = _native.classify()
+    out = C.f1_batch(torch.cat(rows[0])[:, None], torch.cat(rows[1])[:, None], epsilon, counts=[p.numel() for p in rows[0]])
+    return [tuple(row.unbind()) for row in out]
