@@ -168,7 +168,9 @@ __global__ __launch_bounds__(256) void stft1024_kernel(const TIN* __restrict__ x
             if (t + 1 < te) { if (hop == 256) advance(t + 1, cur, nxt); else fetch(t + 1, nxt); }   // in flight under this frame's transform
             one_frame(t, cur, [&](int f, cd X) {
                 // np.abs(complex64) ** 2: float32 magnitude, then its square.  The magnitudes here are far from
-                // overflow, so the correctly rounded square root of re^2 + im^2 stands in for hypotf (30 instructions)
+                // overflow, so the square root of re^2 + im^2 stands in for hypotf (30 instructions).  __fsqrt_rn is the
+                // 1-ulp v_sqrt_f32 here (HIP's headers round it correctly only under OCML_BASIC_ROUNDED_OPERATIONS), on a sum
+                // with two roundings: the magnitude is within 1.5 ulp, not hypotf's 1 (tests/stft_bounds.py, POWER)
                 const float re32 = (float)X.x, im32 = (float)X.y;
                 const float a = __fsqrt_rn(fmaf(re32, re32, im32 * im32));
                 o[t * F + f] = a * a;
