@@ -16,8 +16,33 @@ import numpy as np
 # layers
 # ----------------------------------------------------------------------------
 
-def linear(x, W, b):
+# Optional operand hook (tests/grad_columns.py: the CPU restatements of the 16-bit operand policies).  None, the default, leaves every
+# product below exactly as written.  A hook object restates the four GEMM roles of a layer `name` with its own operand rounding:
+#   fwd(name, x, W) = x @ W.T     wgrad(name, dpre, inp) = dpre.T @ inp     bias(name, dpre) = dpre.sum(axis=0)     bwd(name, dpre, W) = dpre @ W
+_GEMM_HOOK = None
+
+
+class gemm_hook:
+    """`with gemm_hook(h): ...` routes the products of linear() / linear_bwd() through h inside the block."""
+
+    def __init__(self, hook):
+        self.hook = hook
+
+    def __enter__(self):
+        global _GEMM_HOOK
+        self.prev, _GEMM_HOOK = _GEMM_HOOK, self.hook
+        return self.hook
+
+    def __exit__(self, *exc):
+        global _GEMM_HOOK
+        _GEMM_HOOK = self.prev
+        return False
+
+
+def linear(x, W, b, name=None):
     """torch.nn.Linear: y = x @ W.T + b."""
+    if _GEMM_HOOK is not None:
+        return _GEMM_HOOK.fwd(name, x, W) + b
     return x @ W.T + b
 
 
@@ -36,7 +61,7 @@ def mlp_hidden_fwd(params, prefix, x, act):
     :59-60 relu classifier).  Returns the list of layer outputs."""
     outs = []
     for name in _hidden_names(params, prefix):
-        pre = linear(x, params[name + ".weight"], params[name + ".bias"])
+        pre = linear(x, params[name + ".weight"], params[name + ".bias"], name)
         x = np.tanh(pre) if act == "tanh" else np.maximum(pre, 0)
         outs.append(x)
     return outs
@@ -48,8 +73,8 @@ def encoder_fwd(params, prefix, inp, eps_noise):
     z = mu + exp(0.5*log_var) * epsilon."""
     hs = mlp_hidden_fwd(params, prefix, inp, "tanh")
     h = hs[-1]
-    mu = linear(h, params[prefix + "sample.mu.weight"], params[prefix + "sample.mu.bias"])
-    lv = linear(h, params[prefix + "sample.log_var.weight"], params[prefix + "sample.log_var.bias"])
+    mu = linear(h, params[prefix + "sample.mu.weight"], params[prefix + "sample.mu.bias"], prefix + "sample.mu")
+    lv = linear(h, params[prefix + "sample.log_var.weight"], params[prefix + "sample.log_var.bias"], prefix + "sample.log_var")
     std = np.exp(lv * inp.dtype.type(0.5))
     z = mu + std * eps_noise
     return dict(inp=inp, hs=hs, mu=mu, lv=lv, std=std, z=z, eps_noise=eps_noise)
@@ -58,7 +83,7 @@ def encoder_fwd(params, prefix, inp, eps_noise):
 def decoder_fwd(params, prefix, inp):
     """Decoder.forward (packages/models/models.py:119-122): exp(reconstruction(tanh stack))."""
     ds = mlp_hidden_fwd(params, prefix, inp, "tanh")
-    a = linear(ds[-1], params[prefix + "reconstruction.weight"], params[prefix + "reconstruction.bias"])
+    a = linear(ds[-1], params[prefix + "reconstruction.weight"], params[prefix + "reconstruction.bias"], prefix + "reconstruction")
     r = np.exp(a)
     return dict(inp=inp, ds=ds, a=a, r=r)
 
@@ -66,7 +91,7 @@ def decoder_fwd(params, prefix, inp):
 def classifier_fwd(params, prefix, inp):
     """Classifier.forward (packages/models/models.py:57-63): relu stack, sigmoid output."""
     hs = mlp_hidden_fwd(params, prefix, inp, "relu")
-    pre = linear(hs[-1], params[prefix + "output_layer.weight"], params[prefix + "output_layer.bias"])
+    pre = linear(hs[-1], params[prefix + "output_layer.weight"], params[prefix + "output_layer.bias"], prefix + "output_layer")
     p = 1.0 / (1.0 + np.exp(-pre))
     return dict(inp=inp, hs=hs, p=p.astype(inp.dtype))
 
@@ -114,6 +139,11 @@ def _acc(grads, key, val):
 
 
 def linear_bwd(params, grads, name, inp, dpre, need_dx=True):
+    if _GEMM_HOOK is not None:
+        h = _GEMM_HOOK
+        _acc(grads, name + ".weight", h.wgrad(name, dpre, inp))
+        _acc(grads, name + ".bias", h.bias(name, dpre))
+        return h.bwd(name, dpre, params[name + ".weight"]) if need_dx else None
     _acc(grads, name + ".weight", dpre.T @ inp)
     _acc(grads, name + ".bias", dpre.sum(axis=0))
     return dpre @ params[name + ".weight"] if need_dx else None

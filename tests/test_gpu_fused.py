@@ -117,7 +117,8 @@ def test_fused_step_vs_oracle(model, y_dim, B, precision):
     fp32 values (relative precision per element: Adam normalises each element by its own history).
     bf16 (one bf16 per operand, opt-in fast mode): the synthetic power spectra span 1e-12 .. 1e4, so bf16
     rounding of x and W1 moves encoder pre-activations by O(1) on the loudest frames; measured deviation bound
-    stated here: losses 2e-3 relative, every gradient tensor cosine >= 0.99 with the fp64 oracle and within 0.3 of its max."""
+    stated here: losses 2e-3 relative, every gradient tensor cosine >= 0.99 with the fp64 oracle and within 0.3 of its max.
+    Every figure here is relative to a tensor's LARGEST element; per input column, each at its own scale: tests/test_gpu_fused_columns.py."""
     dims = dict(x_dim=513, y_dim=y_dim, z_dim=16, h_dim=(128, 128))
     params = gu.make_params(model, dims, 11)
     x, y, e = gu.make_batch(dims, B, 12)
