@@ -617,9 +617,11 @@ static int run_mh(const dvae_mcem_plan_t* plan, const void* wcopy, MhArgs& a, hi
     a.bias = (const float*)((const char*)wcopy + L.bias_off_bytes);
     const bool bf = plan->precision == DVAE_PREC_BF16;
     a.wpl = plan->precision == DVAE_PREC_BF16X3 ? (unsigned)(L.elems * 2) : 0u;
-    // label rows 0 / 1..16: the weight-stationary chain (mcem_resident.hip); DVAE_MCEM_CHAIN=stream, the 513-row labels and
-    // (F, N) matrices of 2 GB and more: the streaming kernels below
-    static const bool stream_only = [] { const char* e = getenv("DVAE_MCEM_CHAIN"); return e && !strcmp(e, "stream"); }();
+    // every label variant (rows 0 / 1..16 / 513): the weight-stationary chain (mcem_resident*.hip).  The streaming kernels below serve what
+    // that chain refuses -- an (F, N) matrix or a noise array of 2 GB and more -- and DVAE_MCEM_CHAIN=stream, read on every call (as
+    // launch_resident_chain reads DVAE_MCEM_TILE), so one process can run both chains on the same inputs
+    const char* const chain_env = getenv("DVAE_MCEM_CHAIN");
+    const bool stream_only = chain_env && !strcmp(chain_env, "stream");
     if (!stream_only && resident_chain_supported(plan->precision, L.yp) && (int64_t)XD * a.N * 4 < ((int64_t)1 << 31) &&
         (int64_t)a.nit * ZD * a.N * 4 < ((int64_t)1 << 31))
         return launch_resident_chain(plan->precision, L.yp, a, s);

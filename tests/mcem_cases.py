@@ -39,6 +39,34 @@ def make_utterance(case):
     return X, S, (y if ydim else None)
 
 
+def chain_inputs(model, y_dim, N, seed, wscale=1.0, soft=False):
+    """Inputs of one Metropolis-Hastings chain launch over N frames, shared by the chain tests on the device (test_gpu_mcem.py)
+    and the float32-against-float64 check of the oracle on the same inputs (test_mcem_oracle_chain.py).  Labels are binary, or
+    with soft=True uniform in [0, 1) (what McemBatch.init_parameters(..., use="soft") hands over); both take the same number of
+    draws, so everything after them is the same either way.
+    -> params, decoder prefix, X2 (513, N), y (y_dim, N) or None, Z (16, N), g (N), W (513, 10), H (10, N), the generator."""
+    import golden_util as gu
+    dims = dict(x_dim=513, y_dim=y_dim, z_dim=16, h_dim=(128, 128))
+    params = gu.make_params(model, dims, seed, wscale)
+    prefix = "enc_dec_clf.decoder." if model == "M2_info" else "decoder."
+    rng = np.random.default_rng(seed + 77)
+    X2 = (rng.standard_normal((513, N)) ** 2 * np.exp(rng.standard_normal((513, 1)) - 1)).astype(np.float32) + 1e-4
+    y = None
+    if y_dim:
+        u = rng.random((y_dim, N))
+        y = u.astype(np.float32) if soft else (u > 0.5).astype(np.float32)
+    Z = rng.standard_normal((16, N)).astype(np.float32)
+    g = np.exp(0.2 * rng.standard_normal(N)).astype(np.float32)
+    W = np.maximum(rng.random((513, 10)), 1e-6).astype(np.float32)
+    H = np.maximum(rng.random((10, N)), 1e-6).astype(np.float32)
+    return params, prefix, X2, y, Z, g, W, H, rng
+
+
+# label widths between the tested 1 and 513 (zero-padded to 16 rows on the device), and fractional labels: (model, y_dim, N, soft)
+LABEL_CASES = [("M2", 2, 70, False), ("M2", 7, 45, False), ("M2", 15, 70, False), ("M2", 16, 45, False),
+               ("M2", 1, 70, True), ("M2", 7, 45, True), ("M2", 513, 45, True)]
+
+
 def checksum(X, S, y):
     tot = float(np.abs(X).astype(np.float64).sum() + np.abs(S).astype(np.float64).sum())
     return tot + (float(y.sum()) if y is not None else 0.0)

@@ -51,8 +51,17 @@ def test_stft_istft_outputs(n, layout):
     g.check()
 
 
-@pytest.mark.parametrize("model,y_dim,n,precision", [("M2", 1, 45, "fp32"), ("M2", 513, 33, "bf16"), ("M1", 0, 1, "fp32"), ("M2", 1, 300, "bf16")])
-def test_mcem_outputs(model, y_dim, n, precision):
+# chain None: the weight-stationary chain as selected; "stream": the streaming chain of csrc/mcem.hip (DVAE_MCEM_CHAIN=stream), ragged last tiles
+MCEM_CASES = [("M2", 1, 45, "fp32", None), ("M2", 513, 33, "bf16", None), ("M1", 0, 1, "fp32", None), ("M2", 1, 300, "bf16", None),
+              ("M2", 1, 45, "fp32", "stream"), ("M2", 513, 33, "bf16", "stream"), ("M1", 0, 1, "bf16x3", "stream"), ("M2", 7, 300, "bf16x3", "stream")]
+
+
+@pytest.mark.parametrize("model,y_dim,n,precision,chain", MCEM_CASES, ids=["-".join(str(v) for v in c if v is not None) for c in MCEM_CASES])
+def test_mcem_outputs(model, y_dim, n, precision, chain, monkeypatch):
+    if chain is None:
+        monkeypatch.delenv("DVAE_MCEM_CHAIN", raising=False)
+    else:
+        monkeypatch.setenv("DVAE_MCEM_CHAIN", chain)
     lib = N.load()
     dims = dict(x_dim=513, y_dim=y_dim, z_dim=16, h_dim=(128, 128))
     m = build_model(model, dims)

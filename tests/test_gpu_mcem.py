@@ -26,32 +26,45 @@ def t(a):
     return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def setup(model, y_dim, N, seed, wscale=1.0, precision="fp32"):
+def setup(model, y_dim, N, seed, wscale=1.0, precision="fp32", soft=False):
+    params, prefix, X2, y, Z, g, W, H, rng = mc.chain_inputs(model, y_dim, N, seed, wscale, soft)
     dims = dict(x_dim=513, y_dim=y_dim, z_dim=16, h_dim=(128, 128))
-    params = gu.make_params(model, dims, seed, wscale)
     m = build_model(model, dims)
     m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in params.items()})
     m.cuda()
     vae = m.enc_dec_clf if model == "M2_info" else m
     pack = mcem_dev.DecoderPack(vae.decoder, y_dim, precision)
-    prefix = "enc_dec_clf.decoder." if model == "M2_info" else "decoder."
-    rng = np.random.default_rng(seed + 77)
-    X2 = (rng.standard_normal((513, N)) ** 2 * np.exp(rng.standard_normal((513, 1)) - 1)).astype(np.float32) + 1e-4
-    y = (rng.random((y_dim, N)) > 0.5).astype(np.float32) if y_dim else None
-    Z = rng.standard_normal((16, N)).astype(np.float32)
-    g = np.exp(0.2 * rng.standard_normal(N)).astype(np.float32)
-    W = np.maximum(rng.random((513, 10)), 1e-6).astype(np.float32)
-    H = np.maximum(rng.random((10, N)), 1e-6).astype(np.float32)
     return params, prefix, pack, X2, y, Z, g, W, H, rng
 
 
+CHAINS = ["4", "16", "32", "stream"]
+
+
 def pick_tile(monkeypatch, tile, precision):
-    """Frames per workgroup of the weight-stationary chain: 4 (csrc/mcem_resident4.hip: exact fp32 only, what short fp32 chains take by
-    default), 16 (csrc/mcem_resident16.hip, what chains take by default while their 16-frame tiles fit the chip in one round) or 32
-    (csrc/mcem_resident.hip)."""
+    """The chain kernel of the call.  "4" / "16" / "32": frames per workgroup of the weight-stationary chain (DVAE_MCEM_TILE) -- 4
+    (csrc/mcem_resident4.hip: exact fp32 only, what short fp32 chains take by default), 16 (csrc/mcem_resident16.hip, what chains take by
+    default while their 16-frame tiles fit the chip in one round) or 32 (csrc/mcem_resident.hip).  "stream": the streaming chain of
+    csrc/mcem.hip (DVAE_MCEM_CHAIN=stream, read by the library on every call), which otherwise serves only calls of 2 GB and more."""
     if tile == "4" and precision != "fp32":
         pytest.skip("the 4-frame chain kernel exists for the exact-fp32 policy")
-    monkeypatch.setenv("DVAE_MCEM_TILE", tile)
+    if tile == "stream":
+        monkeypatch.setenv("DVAE_MCEM_CHAIN", "stream")
+        monkeypatch.delenv("DVAE_MCEM_TILE", raising=False)
+    else:
+        monkeypatch.delenv("DVAE_MCEM_CHAIN", raising=False)
+        monkeypatch.setenv("DVAE_MCEM_TILE", tile)
+
+
+def bar_units(got, ref, rtol, atol):
+    """Worst |got - ref| in units of the assert_allclose bound atol + rtol |ref| (<= 1 passes)."""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    return float(np.max(np.abs(got - ref) / (atol + rtol * np.abs(ref)))) if got.size else 0.0
+
+
+ORACLE_CASES = [("M1", 0, 45, False), ("M2", 1, 70, False), ("M2", 513, 33, False), ("M2_info", 1, 100, False)] + mc.LABEL_CASES
+# one frame, either side of a 16- and a 32-frame tile with one label row; the other label widths and the soft labels at one frame and
+# one frame past either tile: (N, y_dim, soft)
+RAGGED_CASES = [(N, 1, False) for N in (1, 15, 16, 17, 31, 33)] + [(N, c[1], c[3]) for c in mc.LABEL_CASES for N in (1, 17, 33)]
 
 
 def chains_agree(accd, trace_a):
@@ -61,13 +74,16 @@ def chains_agree(accd, trace_a):
     return first
 
 
-@pytest.mark.parametrize("tile", ["4", "16", "32"])
+@pytest.mark.parametrize("tile", CHAINS)
 @pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
-@pytest.mark.parametrize("model,y_dim,N", [("M1", 0, 45), ("M2", 1, 70), ("M2", 513, 33), ("M2_info", 1, 100)])
-def test_sample_posterior_matches_oracle(model, y_dim, N, precision, tile, monkeypatch):
-    """fp32 = exact fp32 products; bf16x3 = split-bf16 operands (16 mantissa bits, three MFMAs per product): the same bounds."""
+@pytest.mark.parametrize("model,y_dim,N,soft", ORACLE_CASES, ids=[f"{c[0]}-{c[1]}-{c[2]}" + ("-soft" if c[3] else "") for c in ORACLE_CASES])
+def test_sample_posterior_matches_oracle(model, y_dim, N, soft, precision, tile, monkeypatch):
+    """fp32 = exact fp32 products; bf16x3 = split-bf16 operands (16 mantissa bits, three MFMAs per product): the same bounds.
+    Label widths 2..16 run the zero-padding of label rows y_dim..15; soft (fractional) labels put something other than zero into
+    the lo plane of the split-bf16 label image.  test_mcem_oracle_chain.py holds the reference alone to a tenth of these bars on
+    the same inputs."""
     pick_tile(monkeypatch, tile, precision)
-    params, prefix, pack, X2, y, Z, g, W, H, rng = setup(model, y_dim, N, 5, precision=precision)
+    params, prefix, pack, X2, y, Z, g, W, H, rng = setup(model, y_dim, N, 5, precision=precision, soft=soft)
     nit, burnin = 12, 5
     noise = rng.standard_normal((nit, 16, N)).astype(np.float32)
     logu = np.log(rng.random((nit, N)).astype(np.float32))
@@ -76,24 +92,28 @@ def test_sample_posterior_matches_oracle(model, y_dim, N, precision, tile, monke
     Zs, Vs, accp, accd = pack.sample(t(Z), t(y), t(g), t(Vb), t(X2), t(noise), t(logu), burnin, trace=True)
     Zs, Vs, accp, accd = Zs.cpu().numpy(), Vs.cpu().numpy(), accp.cpu().numpy(), accd.cpu().numpy().astype(bool)
     first = chains_agree(accd, ta)
+    same = first == nit
+    Vs_o = mo.compute_vs(params, prefix, Zs, y)
+    in_state = np.arange(nit)[:, None] <= first[None, :]
+    print(f"worst error in units of the bar: log ratio {bar_units(accp[in_state], tp[in_state], 2e-4, 2e-3):.3f}, "
+          f"kept samples {bar_units(Zs[same], Zs_o[same], 1e-5, 1e-6):.3f}, Vs {bar_units(Vs, Vs_o, 1e-4, 1e-9):.3f}; "
+          f"same decisions {same.mean():.3f}, acceptance {accd.mean():.3f}")
     # log acceptance ratios agree as long as the two chains are in the same state (sums of 513 terms of size ~5:
     # the reference's own float32 summation noise is ~1e-4 absolute)
     for n in range(N):
         k = min(first[n] + 1, nit)
         np.testing.assert_allclose(accp[:k, n], tp[:k, n], rtol=2e-4, atol=2e-3)
-    same = first == nit
     assert same.mean() >= 0.97, same.mean()
     np.testing.assert_allclose(Zs[same], Zs_o[same], rtol=1e-5, atol=1e-6)
     assert 0.02 < accd.mean() < 0.98            # the chain actually moves and actually rejects
     # variances of the kept samples (compute_Vs) in the same launch
-    Vs_o = mo.compute_vs(params, prefix, Zs, y)
     np.testing.assert_allclose(Vs, Vs_o, rtol=1e-4, atol=1e-9)
     # and alone
     Vs2 = pack.decode(t(Zs), t(y)).cpu().numpy()
     np.testing.assert_array_equal(Vs2, Vs)
 
 
-@pytest.mark.parametrize("tile", ["4", "16", "32"])
+@pytest.mark.parametrize("tile", CHAINS)
 @pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
 @pytest.mark.parametrize("decisions", ["mixed", "accept", "reject"])
 @pytest.mark.parametrize("nit,burnin", [(1, 0), (4, 0), (5, 4), (12, 5), (70, 2)])
@@ -147,14 +167,15 @@ def test_m_step_and_wiener_match_oracle(N, R, K):
     np.testing.assert_allclose((WFs + WFn).cpu().numpy(), 1.0, rtol=1e-5)        # the two gains partition the mixture
 
 
-@pytest.mark.parametrize("tile", ["4", "16", "32"])
+@pytest.mark.parametrize("tile", CHAINS)
 @pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
-@pytest.mark.parametrize("N", [1, 15, 16, 17, 31, 33])
-def test_chain_on_tiny_and_ragged_frame_counts(N, precision, tile, monkeypatch):
+@pytest.mark.parametrize("N,y_dim,soft", RAGGED_CASES, ids=[str(c[0]) + (f"-y{c[1]}" + ("-soft" if c[2] else "") if (c[1], c[2]) != (1, False) else "")
+                                                             for c in RAGGED_CASES])
+def test_chain_on_tiny_and_ragged_frame_counts(N, y_dim, soft, precision, tile, monkeypatch):
     """One frame, one short of a tile, exactly a tile, one more (both tile sizes): log acceptance ratios of the first chain step (every chain
     still in its initial state) against the oracle, kept samples finite, nothing written outside the N frames."""
     pick_tile(monkeypatch, tile, precision)
-    params, prefix, pack, X2, y, Z, g, W, H, rng = setup("M2", 1, N, 11, precision=precision)
+    params, prefix, pack, X2, y, Z, g, W, H, rng = setup("M2", y_dim, N, 11, precision=precision, soft=soft)
     nit, burnin = 6, 2
     noise = rng.standard_normal((nit, 16, N)).astype(np.float32)
     logu = np.log(rng.random((nit, N)).astype(np.float32))
@@ -162,6 +183,7 @@ def test_chain_on_tiny_and_ragged_frame_counts(N, precision, tile, monkeypatch):
     Zs_o, tp, ta = mo.sample_posterior(params, prefix, Z, y, g, Vb, X2, noise, logu, burnin, return_trace=True)
     Zs, Vs, accp, accd = pack.sample(t(Z), t(y), t(g), t(Vb), t(X2), t(noise), t(logu), burnin, trace=True)
     assert Zs.shape == (N, nit - burnin, 16) and Vs.shape == (nit - burnin, 513, N)
+    print(f"worst first-step log ratio error: {bar_units(accp.cpu().numpy()[0], tp[0], 2e-4, 2e-3):.3f} of the bar")
     np.testing.assert_allclose(accp.cpu().numpy()[0], tp[0], rtol=2e-4, atol=2e-3)
     assert torch.isfinite(Zs).all() and torch.isfinite(Vs).all() and (Vs > 0).all()
     first = chains_agree(accd.cpu().numpy().astype(bool), ta)
@@ -169,12 +191,12 @@ def test_chain_on_tiny_and_ragged_frame_counts(N, precision, tile, monkeypatch):
     np.testing.assert_allclose(Zs.cpu().numpy()[same], Zs_o[same], rtol=1e-5, atol=1e-6)
 
 
-@pytest.mark.parametrize("tile", ["4", "16", "32"])
+@pytest.mark.parametrize("tile", CHAINS)
 @pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
 @pytest.mark.parametrize("case", mc.CASES, ids=[c["name"] for c in mc.CASES])
 def test_full_run_matches_reference_golden(case, precision, tile, monkeypatch):
     """EM.run on the draws recorded from the reference: state after every iteration vs the reference's (exact-fp32 and split-bf16
-    chain policies, 16- and 32-frame chain kernels, against the same bounds)."""
+    chain policies, every chain kernel -- 4-, 16- and 32-frame weight-stationary tiles and the streaming chain -- against the same bounds)."""
     pick_tile(monkeypatch, tile, precision)
     fix = case_fix(case["name"])
     dims = mc.DIMS[case["model"]]
@@ -205,14 +227,15 @@ def test_full_run_matches_reference_golden(case, precision, tile, monkeypatch):
     assert (np.abs(WFn.cpu().numpy() - fix["WFn"]) > 5e-3).mean() < 0.05
 
 
-@pytest.mark.parametrize("tile", ["4", "16", "32"])
+@pytest.mark.parametrize("tile", CHAINS)
 @pytest.mark.parametrize("precision", ["fp32", "bf16x3", "bf16"])
 @pytest.mark.parametrize("model,y_dim,N", [("M2", 1, 300), ("M2", 513, 200), ("M1", 0, 257)])
 def test_chain_launches_are_bit_identical(model, y_dim, N, precision, tile, monkeypatch):
     """The weight-stationary chain feeds its output-layer MFMAs from AGPR-pinned fragments through inline asm, i.e. outside the compiler's
     hazard bookkeeping (csrc/mcem_resident.hip): a write-after-read slip there shows up as bf16-level differences that change from launch
     to launch (that is how the first version was caught).  Four launches on the same draws return the same bits, every policy and label
-    variant, both tile sizes, full-length E-step chain."""
+    variant, every tile size, full-length E-step chain.  The streaming chain (csrc/mcem.hip) walks its output-layer fragments through a
+    register ring whose prefetch wraps from the last output tile into the next decoder pass: held to the same."""
     pick_tile(monkeypatch, tile, precision)
     params, prefix, pack, X2, y, Z, g, W, H, rng = setup(model, y_dim, N, 5, precision=precision)
     nit, burnin = 40, 30
@@ -229,9 +252,57 @@ def test_chain_launches_are_bit_identical(model, y_dim, N, precision, tile, monk
         np.testing.assert_array_equal(Vs, outs[0][1])
 
 
-def test_bf16_chain_is_statistically_close():
+@pytest.mark.parametrize("tile", CHAINS)
+@pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
+def test_label_rows_past_y_dim_are_zero_padding(precision, tile, monkeypatch):
+    """A decoder with 7 label rows runs as one with 16 on the device: label rows 7..15 of the tile image and the weight columns that
+    meet them are zero padding.  A 16-row decoder that shares the first 7 label columns of W3 (the other nine columns hold weights
+    of their own) on labels whose last nine rows are zero is the same function: same log ratios within the chain bars wherever
+    the two chains took the same decisions so far, so neither side of the padding leaks anything into the sum."""
+    pick_tile(monkeypatch, tile, precision)
+    N, nit, burnin = 45, 12, 5
+    params7, prefix, pack7, X2, y7, Z, g, W, H, rng = setup("M2", 7, N, 5, precision=precision, soft=True)
+    dims = dict(x_dim=513, y_dim=16, z_dim=16, h_dim=(128, 128))
+    params16 = gu.make_params("M2", dims, 6)
+    for k, v in params7.items():
+        if k.startswith(prefix) and k != prefix + "hidden.0.weight":
+            params16[k] = v.copy()
+    params16[prefix + "hidden.0.weight"][:, :16 + 7] = params7[prefix + "hidden.0.weight"]
+    assert np.abs(params16[prefix + "hidden.0.weight"][:, 16 + 7:]).min() > 0
+    m = build_model("M2", dims)
+    m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in params16.items()})
+    m.cuda()
+    pack16 = mcem_dev.DecoderPack(m.decoder, 16, precision)
+    y16 = np.concatenate([y7, np.zeros((9, N), np.float32)], axis=0)
+    noise = rng.standard_normal((nit, 16, N)).astype(np.float32)
+    logu = np.log(rng.random((nit, N)).astype(np.float32))
+    Vb = (W @ H).astype(np.float32)
+    out = []
+    for pack, y in ((pack7, y7), (pack16, y16)):
+        Zs, Vs, accp, accd = pack.sample(t(Z), t(y), t(g), t(Vb), t(X2), t(noise), t(logu), burnin, trace=True)
+        out.append((Zs.cpu().numpy(), Vs.cpu().numpy(), accp.cpu().numpy(), accd.cpu().numpy().astype(bool)))
+    (Zs7, Vs7, p7, d7), (Zs16, Vs16, p16, d16) = out
+    first = chains_agree(d7, d16)
+    in_state = np.arange(nit)[:, None] <= first[None, :]
+    same = first == nit
+    print(f"16 rows against 7, worst error in units of the bar: log ratio {bar_units(p16[in_state], p7[in_state], 2e-4, 2e-3):.3f}, "
+          f"kept samples {bar_units(Zs16[same], Zs7[same], 1e-5, 1e-6):.3f}; same decisions {same.mean():.3f}")
+    np.testing.assert_allclose(p16[in_state], p7[in_state], rtol=2e-4, atol=2e-3)
+    assert same.mean() >= 0.97, same.mean()
+    np.testing.assert_allclose(Zs16[same], Zs7[same], rtol=1e-5, atol=1e-6)
+    assert 0.02 < d7.mean() < 0.98
+
+
+@pytest.mark.parametrize("chain", ["resident", "stream"])
+def test_bf16_chain_is_statistically_close(chain, monkeypatch):
     """Throughput mode (bf16 matrix-core operands): first-iteration log ratios within bf16 noise of the oracle,
-    same acceptance rate to a few percent."""
+    same acceptance rate to a few percent.  resident: the weight-stationary chain as selected; stream: the streaming chain
+    (mcem_mh_kernel<PolBF16, 16, 1>, decoder layers 1-2 in registers)."""
+    monkeypatch.delenv("DVAE_MCEM_TILE", raising=False)
+    if chain == "stream":
+        monkeypatch.setenv("DVAE_MCEM_CHAIN", "stream")
+    else:
+        monkeypatch.delenv("DVAE_MCEM_CHAIN", raising=False)
     params, prefix, pack, X2, y, Z, g, W, H, rng = setup("M2", 1, 256, 9, precision="bf16")
     nit, burnin = 20, 10
     noise = rng.standard_normal((nit, 16, 256)).astype(np.float32)

@@ -1,7 +1,9 @@
 """The batched M-step and the fused EM iteration (McemBatch) against the float64 oracle, at the shapes the batch path runs:
 every frames-per-workgroup variant of the register-resident frames kernel (4 / 8 / 16, forced and as selected), the W update's
 straight-line form and its double-buffered loop, the three-pass kernels (R > 10 kept samples, ranks other than 10), ragged
-batches with padding, the weight-stationary and the streaming chain, the lazy and the three-launch iteration."""
+batches with padding, the lazy and the three-launch iteration.  The EM iteration runs on the weight-stationary chain, which writes
+the final state itself (every model, the 513-row labels included), and -- the "-stream" cases, DVAE_MCEM_CHAIN=stream -- on the streaming
+chain of csrc/mcem.hip, where last_sample_kernel writes Z over the chain's own initial state."""
 import importlib
 from concurrent.futures import ThreadPoolExecutor
 
@@ -217,7 +219,7 @@ EM_MODELS = {
     # name: (model, y_dim, McemBatch flags)
     "M1": ("M1", 0, dict(label_in_encoder=False, label_in_decoder=False)),
     "M2_y1": ("M2", 1, dict()),
-    "M2_y513_stream": ("M2", 513, dict()),                        # 513-row labels: the streaming chain + last_sample_kernel
+    "M2_y513": ("M2", 513, dict()),                               # 513-row labels (528 padded rows in the chain's label image)
     "M2_info": ("M2_info", 1, dict(label_in_encoder=False)),
 }
 
@@ -255,12 +257,20 @@ def np_(a):
 
 
 # MCEM_M1 keeps 30 samples: the three-pass M-step, which has no lazy form (McemBatch.run takes the eager iteration there)
-EM_CASES = [pytest.param(name, precision, mode, id=f"{name}-{precision}-{mode}") for name in EM_MODELS for precision in ("fp32", "bf16x3")
-            for mode in ("eager", "lazy") if not (name == "M1" and mode == "lazy")]
+# chain None: the weight-stationary chain as selected; "stream": DVAE_MCEM_CHAIN=stream -- mcem_mh_kernel, then last_sample_kernel with Zlast
+# aliasing Z0 (check (a) below)
+EM_CASES = [pytest.param(name, precision, mode, chain, id=f"{name}-{precision}-{mode}" + (f"-{chain}" if chain else ""))
+            for chain in (None, "stream") for name in EM_MODELS for precision in ("fp32", "bf16x3") for mode in ("eager", "lazy")
+            if not (name == "M1" and mode == "lazy") and not (chain == "stream" and name == "M2_info")]
 
 
-@pytest.mark.parametrize("name,precision,mode", EM_CASES)
-def test_em_iteration_matches_oracle(name, precision, mode):
+@pytest.mark.parametrize("name,precision,mode,chain", EM_CASES)
+def test_em_iteration_matches_oracle(name, precision, mode, chain, monkeypatch):
+    monkeypatch.delenv("DVAE_MCEM_TILE", raising=False)
+    if chain is None:
+        monkeypatch.delenv("DVAE_MCEM_CHAIN", raising=False)
+    else:
+        monkeypatch.setenv("DVAE_MCEM_CHAIN", chain)
     mb, params, prefix = em_setup(name, precision)
     lazy = mode == "lazy"
     U, ntot, R, nit = len(mb.counts), mb.ntot, mb.n_e, mb.n_e + mb.b_e
