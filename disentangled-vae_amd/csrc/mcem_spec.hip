@@ -5,6 +5,8 @@
 //
 // The magnitude is numpy's for complex64, squared in float32 (spec_power.hpp, shared with classify.hip): bit-identical to
 // `(np.abs(X) ** 2).astype(np.float32)`.
+//
+// Beside it the start of the NMF factors for the same layout (dvae_mcem_nmf_start, below): clamps and Vb = W H for all utterances.
 #include "common.hpp"
 #include "spec_power.hpp"
 #include "../../include/dvae_mcem.h"
@@ -55,6 +57,56 @@ __global__ __launch_bounds__(256) void mcem_spec_init_kernel(const float2* __res
     }
 }
 
+// The NMF factors' start for all utterances in one launch (McemBatch.init_parameters(fused_start=True); the reference's mcem.py:42-52).
+// On entry W [U][513][K] and the real columns of H [K][ntot] hold uniform draws; on exit W = max(W, eps), real columns of H = max(H,
+// eps), Vb[f][n] = sum_k W[u(n)][f][k] H[k][n] as ONE fma chain from 0 with k ascending, and the pad columns (in no utterance's range)
+// of H and Vb are 1.  tab as above.  A workgroup is 64 columns x 64 bins, thread -> column (tid & 63), bins (tid >> 6) + 4 i.  Every
+// reader of a draw clamps it itself, so the thread that stores the clamped value back (W: the utterance's first column; H: the first
+// bin tile) can do so while others still read: they see the draw or its clamp, and take the same maximum.  The utterance index comes
+// from a search that stays inside the table's entries, so whatever the table holds, nothing outside W, H and Vb is touched.
+constexpr int NMF_KMAX = 16;
+
+__global__ __launch_bounds__(256) void mcem_nmf_start_kernel(float* __restrict__ W, float* __restrict__ H, float* __restrict__ Vb, int64_t ntot, int K, int U,
+                                                             const int64_t* __restrict__ tab, float eps) {
+    constexpr int F = 513;
+    const int q = threadIdx.x >> 6;
+    const int64_t n = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
+    if (n >= ntot) return;
+    int a = 0, b = U;                                              // col[a] <= n < col[b]
+    while (b - a > 1) {
+        const int mid = (a + b) >> 1;
+        if (tab[U + 1 + mid] <= n) a = mid; else b = mid;
+    }
+    const int64_t d = n - tab[U + 1 + a], cnt = tab[a + 1] - tab[a];
+    const bool real = d >= 0 && d < cnt;
+    float hk[NMF_KMAX];
+#pragma unroll
+    for (int k = 0; k < NMF_KMAX; ++k) hk[k] = (k < K && real) ? fmaxf(H[(int64_t)k * ntot + n], eps) : 1.f;
+    if (blockIdx.y == 0) {
+#pragma unroll
+        for (int k = 0; k < NMF_KMAX; ++k)
+            if (k < K && (k & 3) == q) H[(int64_t)k * ntot + n] = hk[k];
+    }
+    for (int i = 0; i < 16; ++i) {
+        const int f = blockIdx.y * 64 + q + 4 * i;
+        if (f >= F) break;
+        float s = 1.f;
+        if (real) {
+            float* w = W + ((int64_t)a * F + f) * K;
+            s = 0.f;
+#pragma unroll
+            for (int k = 0; k < NMF_KMAX; ++k) {
+                if (k < K) {
+                    const float wk = fmaxf(w[k], eps);
+                    s = __fmaf_rn(wk, hk[k], s);
+                    if (d == 0) w[k] = wk;
+                }
+            }
+        }
+        Vb[(int64_t)f * ntot + n] = s;
+    }
+}
+
 }  // namespace dvae
 
 using namespace dvae;
@@ -66,5 +118,14 @@ extern "C" int dvae_mcem_spec_init(const void* S, int64_t T_total, int U, const 
     hipLaunchKernelGGL(mcem_spec_init_kernel, dim3((unsigned)cdiv(T_total, 64), 9), dim3(256), 0, (hipStream_t)stream, (const float2*)S, T_total, U,
                        tables, X2, ntot);
     DVAE_LAUNCH_OK("mcem_spec_init_kernel");
+    return 0;
+}
+
+extern "C" int dvae_mcem_nmf_start(float* W, float* H, float* Vb, int64_t ntot, int K, int U, const int64_t* tables, float eps, void* stream) {
+    DVAE_CHECK_ARG(W && H && Vb && tables, "mcem_nmf_start: null pointer");
+    DVAE_CHECK_ARG(ntot > 0 && U > 0 && K > 0 && K <= NMF_KMAX, "mcem_nmf_start: need ntot > 0, U > 0, 0 < K <= %d", NMF_KMAX);
+    DVAE_CHECK_ARG(cdiv(ntot, 64) < ((int64_t)1 << 31), "mcem_nmf_start: %lld columns", (long long)ntot);
+    hipLaunchKernelGGL(mcem_nmf_start_kernel, dim3((unsigned)cdiv(ntot, 64), 9), dim3(256), 0, (hipStream_t)stream, W, H, Vb, ntot, K, U, tables, eps);
+    DVAE_LAUNCH_OK("mcem_nmf_start_kernel");
     return 0;
 }

@@ -181,11 +181,17 @@ class McemBatch:
         i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
         return starts, pos, i32(starts), i32(counts), i32(tile_seg)
 
-    def init_parameters(self, X_list, y_list=None, device="cuda", use="hard"):
+    def init_parameters(self, X_list, y_list=None, device="cuda", use="hard", fused_start=False):
         """X_list: complex mixture STFTs (F, N_u) (numpy), or a SpecBatch of complex frames (stft.stft_batch) that stays on the
         device: |X|^2 is then formed there (dvae_mcem_spec_init, the same bits) and run() keeps the Wiener gains there for enhance().
         y_list: labels (y_dim, N_u) tensors/arrays, a LabelBatch (classify.classify_batch) whose `use` labels ("hard" as the
-        reference's evaluation hands them over, or "soft") are taken device to device, or None."""
+        reference's evaluation hands them over, or "soft") are taken device to device, or None.
+        fused_start=True (needs a SpecBatch): the same start without the loop over utterances -- Z from ONE encoder launch on the
+        SpecBatch's frames (encode.encode_rows with the column output, the labels of M2 read as rows: no transposed or concatenated
+        encoder input), W and H from ONE torch.rand each for all utterances (a DIFFERENT draw order from the loop below, which draws
+        W[u], H[u] utterance by utterance: the same seed gives other factors) and one dvae_mcem_nmf_start launch for the clamps and
+        Vb = W H (one ascending-k fma chain per element, not rocBLAS's order).  X2 and y are the default path's bits; Z is
+        encode_batch's mu, within rounding of the default path's.  The default stays the loop: its draws are what seeds rest on."""
         from .classify import LabelBatch
         labels = y_list if isinstance(y_list, LabelBatch) else None
         spec = X_list if isinstance(X_list, STFT.SpecBatch) else None
@@ -204,6 +210,8 @@ class McemBatch:
         self.X_list = None if spec is not None else X_list
         self._S_hat = self._N_hat = None
         self._bufs = None                    # the M-step workspace depends on the utterance count, not only on the padded frame total
+        if fused_start and spec is None:
+            raise TypeError("McemBatch.init_parameters: fused_start needs a SpecBatch of complex frames (stft.stft_batch)")
         if labels is not None and list(labels.counts) != counts:
             bad = next((u for u, (a, b) in enumerate(zip(labels.counts, counts)) if a != b), min(len(labels.counts), len(counts)))
             raise ValueError(f"McemBatch.init_parameters: utterance {bad}: the LabelBatch's frame counts differ from the spectrograms' "
@@ -217,6 +225,8 @@ class McemBatch:
             tab_dev = torch.from_numpy(tab).to(dev)
             N.check(N.load().dvae_mcem_spec_init(N.ptr(spec.frames), int(spec.frame_off[-1]), U, N.ptr(tab_dev), N.ptr(self.X2), self.ntot, N.stream()),
                     "dvae_mcem_spec_init")
+        if fused_start:
+            return self._fused_start(spec, labels, y_list, use, tab, tab_dev, dev)
         self.H = torch.ones((K, self.ntot), dtype=torch.float32, device=dev)
         self.Vb = torch.ones((F_BINS, self.ntot), dtype=torch.float32, device=dev)
         self.g = torch.ones(self.ntot, dtype=torch.float32, device=dev)
@@ -241,6 +251,40 @@ class McemBatch:
         self.Z = torch.t(mu).contiguous()
         y_dim = self.y.shape[0] if self.y is not None else 0
         self._pack = DecoderPack(self.vae.decoder, y_dim, self.precision)
+
+    def _fused_start(self, spec, labels, y_list, use, tab, tab_dev, dev):
+        """The rest of init_parameters(fused_start=True) once X2 stands: labels, Z, W, H, Vb, g in a fixed number of launches."""
+        from . import encode as E
+        U, K, n = len(self.counts), self.K, int(spec.frame_off[-1])
+        lib = N.load()
+        self.g = torch.ones(self.ntot, dtype=torch.float32, device=dev)
+        self.y, yrows = None, None
+        if self.label_in_decoder or self.label_in_encoder:
+            if labels is not None:
+                if use not in ("hard", "soft"):
+                    raise ValueError(f"LabelBatch: use 'hard' or 'soft', got {use!r}")
+                yrows = getattr(labels, use).to(dev)
+            else:                                                   # host labels (y_dim, N_u): one upload of all rows
+                yrows = torch.from_numpy(np.concatenate([np.asarray(torch.as_tensor(y).cpu(), np.float32).T for y in y_list]).astype(np.float32, copy=False)).to(dev)
+            if yrows.dim() != 2 or yrows.shape[0] != n:
+                raise ValueError(f"McemBatch.init_parameters: {tuple(yrows.shape)} label rows for {n} frames")
+            yrows = yrows.to(torch.float32).contiguous()
+            # the column of every frame: starts[u] + (r - frame_off[u])
+            colidx = torch.from_numpy(np.repeat(np.asarray(self.starts, np.int64) - spec.frame_off[:-1], self.counts) + np.arange(n, dtype=np.int64)).to(dev)
+            self.y = torch.zeros((yrows.shape[1], self.ntot), dtype=torch.float32, device=dev)
+            self.y.index_copy_(1, colidx, yrows.T)
+        enc_y = self.y.shape[0] if self.label_in_encoder else 0
+        self.Z = torch.zeros((Z_DIM, self.ntot), dtype=torch.float32, device=dev)
+        E.encode_rows(E.EncoderPack(self.vae.encoder, enc_y), spec.frames, spec.frame_off, y=yrows if enc_y else None, Z=self.Z, cols=self.starts,
+                      tables_dev=tab_dev)
+        self.W = torch.rand((U, F_BINS, K), dtype=torch.float32, device=dev)                        # mcem.py:42, all utterances in one draw
+        self.H = torch.rand((K, self.ntot), dtype=torch.float32, device=dev)                        # mcem.py:43
+        self.Vb = torch.empty((F_BINS, self.ntot), dtype=torch.float32, device=dev)
+        N.check(lib.dvae_mcem_nmf_start(N.ptr(self.W), N.ptr(self.H), N.ptr(self.Vb), self.ntot, K, U, N.ptr(tab_dev), float(self.eps), N.stream()),
+                "dvae_mcem_nmf_start")                                                              # clamps, mcem.py:52, pads = 1
+        if not self.label_in_decoder:
+            self.y = None
+        self._pack = DecoderPack(self.vae.decoder, self.y.shape[0] if self.y is not None else 0, self.precision)
 
     def _chain(self, nsamples, burnin, draws=None):
         nit = nsamples + burnin

@@ -81,6 +81,8 @@ SIGNATURES = {
     "dvae_classify_weights_floats": (c_sz, [c_i]),
     "dvae_classify_batch": (c_i, [c_vp, c_i, c_i64, c_i64, c_i, c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp]),
     "dvae_label_counts_batch": (c_i, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i, c_i, c_vp, c_vp, c_vp, c_vp]),
+    "dvae_encode_weights_floats": (c_sz, [c_i]),
+    "dvae_encode_batch": (c_i, [c_vp, c_i, c_i64, c_vp, c_i64, c_i64, c_i, c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     # include/dvae_train.h (plan pointers are passed with ctypes.byref)
     "dvae_train_plan": (c_i, [c_i, c_i, c_i, c_i64, c_i, c_vp]),
     "dvae_train_init": (c_i, [c_vp, c_vp, c_vp, c_vp]),
@@ -123,6 +125,7 @@ SIGNATURES = {
     "dvae_mcem_cost_flush": (c_i, [c_i, c_i64, c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dvae_mcem_wiener": (c_i, [c_vp, c_i, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dvae_mcem_spec_init": (c_i, [c_vp, c_i64, c_i, c_vp, c_vp, c_i64, c_vp]),
+    "dvae_mcem_nmf_start": (c_i, [c_vp, c_vp, c_vp, c_i64, c_i, c_i, c_vp, c_f, c_vp]),
 }
 
 

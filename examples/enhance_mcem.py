@@ -75,6 +75,8 @@ def main():
     ap.add_argument("--niter", type=int, default=100)
     ap.add_argument("--precision", choices=["fp32", "bf16"], default="fp32")
     ap.add_argument("--out", default="enhanced")
+    ap.add_argument("--fused-start", action="store_true", help="McemBatch.init_parameters(fused_start=True): the start of the EM loop in a fixed "
+                    "number of launches (one encoder launch for Z, one draw each for W and H); another draw order than the default")
     ap.add_argument("--score", action="store_true", help="with --synthetic (whose speech is known): SI-SDR and ESTOI of mixture and estimate per utterance")
     ap.add_argument("--snr", type=float, nargs="+", default=None, help="with --synthetic: mix every utterance with synthetic noise at each of "
                     "these SNRs (dB) on the device instead of adding a fixed 0.2 * randn on the host")
@@ -132,7 +134,7 @@ def main():
                               vad_threshold=1.70) for w in waves]                                              # (1, N_u)
         mb = McemBatch(vae, niter=a.niter, nsamples_E_step=10, burnin_E_step=30, nsamples_WF=25, burnin_WF=75, var_RW=0.01,
                        nmf_rank=10, precision=a.precision)                                                      # evaluate_ntcd_M2.py:92-99
-    mb.init_parameters(X, Y)
+    mb.init_parameters(X, Y, fused_start=a.fused_start)
     cost = mb.run()
     # Wiener filtering and ISTFT of both estimates in one launch: istft(S_hat, max_len=len(w)) / istft(N_hat, ...) per utterance
     s_hat, n_hat = mb.enhance(max_len=[len(w) for w in waves])

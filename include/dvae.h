@@ -436,6 +436,35 @@ int dvae_classify_batch(const void* src, int src_complex, int64_t ld, int64_t N,
 int dvae_label_counts_batch(const float* pred, int64_t ldp, const float* truth, int64_t ldt, int64_t N, int y_dim, int U,
                             const int64_t* frame_off_host, const int64_t* frame_off_dev, int64_t* counts, void* stream);
 
+/* ---- the VAE encoder over a ragged batch (packages/models/mcem.py:200, 364; scripts/reconstruct_ntcd_M2.py:231-358) ----
+ * dvae_encode_batch: the reference's Encoder([513 + y_dim, [128, 128], 16]) (packages/models/models.py:91-105), [x | y] -> 128 (tanh) ->
+ *   128 (tanh) -> {mu 16, log_var 16}, y_dim 0 (M1 and the x-only encoders of _v3 / _v5), 1 or 513 (M2), over the frames of a ragged
+ *   batch in one launch on `stream`, no host synchronisation, no atomics, float32 throughout.
+ *   Input as for dvae_classify_batch: src_complex = 1: complex64 frames [N][513], the power formed in the kernel with the bits of
+ *   dvae_mcem_spec_init; src_complex = 0: float32 power rows, ld >= 513.  y: float32 label rows, row r at y + r ldy, ldy >= y_dim;
+ *   required exactly when y_dim > 0.
+ *   weights (device, float32, dvae_encode_weights_floats(y_dim) of them; 0 for a y_dim not covered): the state_dict tensors in their
+ *   own [out][in] layout, one after the other: W1 [128][513 + y_dim] | b1 [128] | W2 [128][128] | b2 [128] | Wmu [16][128] | bmu [16] |
+ *   Wlv [16][128] | blv [16].
+ *   Per frame with power p and labels l, v = [p | l] as torch.cat([x, y], 1) lays it:  h1[j] = tanhf((sum_k v[k] W1[j][k]) + b1[j]);
+ *   h2[j] = tanhf((sum_k h1[k] W2[j][k]) + b2[j]);  mu[c] = (sum_k h2[k] Wmu[c][k]) + bmu[c];  log_var likewise;
+ *   z[c] = mu[c] + expf(0.5f log_var[c]) eps[c], product and sum rounded separately (log_var.mul(0.5).exp_(), mu.addcmul(std, eps)).
+ *   Every sum is ONE float32 chain from 0 with k ascending (on the matrix unit two products per step, as v_mfma_f32_32x32x2_f32 adds
+ *   them; layer 1 is padded with zero products to the next multiple of 32), the bias added after it: the order does not depend on the
+ *   frame's place in a tile, on the tile's place in the grid or on the batch, so a frame gives the same bits alone, in any batch and
+ *   from run to run.
+ *   frame_off_host (HOST int64 [U + 1]) as for dvae_classify_batch: checked before anything is launched; rows outside
+ *   [frame_off[0], frame_off[U]) are neither read nor written.
+ *   Outputs, each may be NULL, at least one must not be: mu, log_var [N][16]; z [N][16], which needs eps [N][16]; Z [16][ntot], the
+ *   layout of McemBatch: mu of row r of utterance u goes to column col[u] + (r - frame_off[u]), every other column is left as it is.
+ *   Z needs col_host (HOST int64 [U]: checked here against frame_off_host and ntot: col[u] >= col[u - 1] + frames of u - 1,
+ *   col[u] + frames of u <= ntot, else DVAE_E_BADARG naming the utterance) and tables_dev (DEVICE int64 [frame_off (U + 1) | col (U)],
+ *   the table of dvae_mcem_spec_init; a frame whose column by the device copy falls outside [0, ntot) is not written). */
+size_t dvae_encode_weights_floats(int y_dim);
+int dvae_encode_batch(const void* src, int src_complex, int64_t ld, const float* y, int64_t ldy, int64_t N, int U,
+                      const int64_t* frame_off_host, const float* weights, int y_dim, const float* eps, float* mu, float* log_var,
+                      float* z, float* Z, int64_t ntot, const int64_t* col_host, const int64_t* tables_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

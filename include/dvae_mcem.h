@@ -106,6 +106,13 @@ int dvae_mcem_wiener(const float* Vs, int R, int64_t N, const float* g, const fl
  * absolute value.  Frames outside the tables' range, or whose columns would leave [0, ntot), are skipped. */
 int dvae_mcem_spec_init(const void* S, int64_t T_total, int U, const int64_t* tables, float* X2, int64_t ntot, void* stream);
 
+/* The start of the NMF factors for all utterances of a McemBatch in one launch (mcem.py:42-43, 52: W = max(rand, eps), H = max(rand, eps),
+ * Vb = W H).  On entry W [U][513][K] and the columns of H [K][ntot] hold uniform draws.  On exit W = max(W, eps); the columns
+ * [col[u], col[u] + frames[u + 1] - frames[u]) of H are max(H, eps) and there Vb[f][n] = sum_k W[u][f][k] H[k][n], one float32 fma chain
+ * from 0 with k ascending; every other column of H and of Vb [513][ntot] is 1.  tables as for dvae_mcem_spec_init; the utterance of a
+ * column is searched inside the table's entries, so no table takes an access outside W, H and Vb.  0 < K <= 16. */
+int dvae_mcem_nmf_start(float* W, float* H, float* Vb, int64_t ntot, int K, int U, const int64_t* tables, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
