@@ -39,6 +39,38 @@ class gemm_hook:
         return False
 
 
+# Optional elementwise hook (tests/module_cases.py: the float32 restatement of the 16-bit policies' transcendentals).  None, the default,
+# leaves np.tanh / np.exp exactly as written.  A hook object restates the tanh of the hidden stacks and the two exp of the model's forward
+# (the standard deviation exp(0.5 log_var) and the reconstruction exp(a)):   tanh(v)   exp(v)
+_ELEMENTWISE_HOOK = None
+
+
+class elementwise_hook:
+    """`with elementwise_hook(h): ...` routes the tanh of mlp_hidden_fwd() and the exp of encoder_fwd() / decoder_fwd() through h inside
+    the block."""
+
+    def __init__(self, hook):
+        self.hook = hook
+
+    def __enter__(self):
+        global _ELEMENTWISE_HOOK
+        self.prev, _ELEMENTWISE_HOOK = _ELEMENTWISE_HOOK, self.hook
+        return self.hook
+
+    def __exit__(self, *exc):
+        global _ELEMENTWISE_HOOK
+        _ELEMENTWISE_HOOK = self.prev
+        return False
+
+
+def _tanh(v):
+    return np.tanh(v) if _ELEMENTWISE_HOOK is None else _ELEMENTWISE_HOOK.tanh(v)
+
+
+def _exp(v):
+    return np.exp(v) if _ELEMENTWISE_HOOK is None else _ELEMENTWISE_HOOK.exp(v)
+
+
 def linear(x, W, b, name=None):
     """torch.nn.Linear: y = x @ W.T + b."""
     if _GEMM_HOOK is not None:
@@ -62,7 +94,7 @@ def mlp_hidden_fwd(params, prefix, x, act):
     outs = []
     for name in _hidden_names(params, prefix):
         pre = linear(x, params[name + ".weight"], params[name + ".bias"], name)
-        x = np.tanh(pre) if act == "tanh" else np.maximum(pre, 0)
+        x = _tanh(pre) if act == "tanh" else np.maximum(pre, 0)
         outs.append(x)
     return outs
 
@@ -75,7 +107,7 @@ def encoder_fwd(params, prefix, inp, eps_noise):
     h = hs[-1]
     mu = linear(h, params[prefix + "sample.mu.weight"], params[prefix + "sample.mu.bias"], prefix + "sample.mu")
     lv = linear(h, params[prefix + "sample.log_var.weight"], params[prefix + "sample.log_var.bias"], prefix + "sample.log_var")
-    std = np.exp(lv * inp.dtype.type(0.5))
+    std = _exp(lv * inp.dtype.type(0.5))
     z = mu + std * eps_noise
     return dict(inp=inp, hs=hs, mu=mu, lv=lv, std=std, z=z, eps_noise=eps_noise)
 
@@ -84,7 +116,7 @@ def decoder_fwd(params, prefix, inp):
     """Decoder.forward (packages/models/models.py:119-122): exp(reconstruction(tanh stack))."""
     ds = mlp_hidden_fwd(params, prefix, inp, "tanh")
     a = linear(ds[-1], params[prefix + "reconstruction.weight"], params[prefix + "reconstruction.bias"], prefix + "reconstruction")
-    r = np.exp(a)
+    r = _exp(a)
     return dict(inp=inp, ds=ds, a=a, r=r)
 
 
