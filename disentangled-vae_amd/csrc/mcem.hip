@@ -597,17 +597,21 @@ static int launch_mh(const MhArgs& a, hipStream_t s) {
 
 static unsigned long long* g_mcem_dbg = nullptr;      // set by dvae_mcem_debug_stamps
 
-// Z (16, N) <- the last kept sample of every frame's chain, Zs (N, R, 16): EM.run's `self.Z = Z_sampled_t[:, -1, :].T` (mcem.py:234, 300)
-__global__ __launch_bounds__(256) void last_sample_kernel(const float* __restrict__ Zs, int R, int64_t N, float* __restrict__ Z) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;          // i = n * 16 + l: coalesced read of the sample, strided 4-byte writes (64 KB in all)
-    if (i >= N * ZD) return;
-    const int64_t n = i / ZD;
-    const int l = (int)(i - n * ZD);
-    Z[(int64_t)l * N + n] = Zs[(n * R + (R - 1)) * ZD + l];
+// Z (zd, N) <- the last kept sample of every frame's chain, Zs (N, R, zd): EM.run's `self.Z = Z_sampled_t[:, -1, :].T` (mcem.py:234, 300)
+__global__ __launch_bounds__(256) void last_sample_kernel(const float* __restrict__ Zs, int R, int64_t N, float* __restrict__ Z, int zd) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;          // i = n * zd + l: coalesced read of the sample, strided 4-byte writes (64 KB in all)
+    if (i >= N * zd) return;
+    const int64_t n = i / zd;
+    const int l = (int)(i - n * zd);
+    Z[(int64_t)l * N + n] = Zs[(n * R + (R - 1)) * zd + l];
 }
 
 
 static int run_mh(const dvae_mcem_plan_t* plan, const void* wcopy, MhArgs& a, hipStream_t s) {
+    if (plan->h2_dim != 0) {                                    // a plan of dvae_mcem_plan_dims: the generic chain (it writes Zlast itself)
+        a.ydim = plan->y_dim;
+        return launch_generic_chain(plan, wcopy, a, s);
+    }
     a.dbg = g_mcem_dbg;
     const McemLayout L = mcem_layout(plan->y_dim, plan->precision);
     a.ydim = plan->y_dim;
@@ -630,7 +634,7 @@ static int run_mh(const dvae_mcem_plan_t* plan, const void* wcopy, MhArgs& a, hi
         const MhArgs& a; hipStream_t s;
         int operator()(int rc) const {
             if (rc == 0 && a.Zlast != nullptr && a.nit > 0) {
-                hipLaunchKernelGGL(last_sample_kernel, dim3((unsigned)((a.N * ZD + 255) / 256)), dim3(256), 0, s, a.Zs, a.R, a.N, a.Zlast);
+                hipLaunchKernelGGL(last_sample_kernel, dim3((unsigned)((a.N * ZD + 255) / 256)), dim3(256), 0, s, a.Zs, a.R, a.N, a.Zlast, ZD);
                 DVAE_LAUNCH_OK("last_sample_kernel");
             }
             return rc;
@@ -673,9 +677,30 @@ extern "C" int dvae_mcem_plan(int y_dim, int precision, dvae_mcem_plan_t* plan) 
     return 0;
 }
 
+extern "C" int dvae_mcem_plan_dims(int z_dim, int h1, int h2, int y_dim, int precision, dvae_mcem_plan_t* plan) {
+    DVAE_CHECK_ARG(plan != nullptr, "mcem_plan_dims: null plan");
+    DVAE_CHECK_ARG(z_dim >= 1 && z_dim <= 128, "mcem_plan_dims: z_dim %d outside 1..128", z_dim);
+    DVAE_CHECK_ARG(h1 >= 1 && h1 <= 512 && h2 >= 1 && h2 <= 512, "mcem_plan_dims: hidden widths (%d, %d) outside 1..512", h1, h2);
+    DVAE_CHECK_ARG(y_dim >= 0 && y_dim <= XD, "mcem_plan_dims: y_dim %d outside 0..513", y_dim);
+    DVAE_CHECK_ARG(precision == DVAE_PREC_F32 || precision == DVAE_PREC_BF16 || precision == DVAE_PREC_BF16X3, "mcem_plan_dims: bad precision %d", precision);
+    if (precision != DVAE_PREC_F32) {
+        set_error("mcem_plan_dims: the generic chain computes in fp32 only (DVAE_PREC_F32); bf16 and bf16x3 exist for the 16 / 128 / 128 decoder of dvae_mcem_plan");
+        return DVAE_E_UNSUPPORTED;
+    }
+    memset(plan, 0, sizeof(*plan));
+    plan->y_dim = y_dim; plan->precision = precision; plan->x_dim = XD; plan->z_dim = z_dim; plan->h_dim = h1; plan->h2_dim = h2;
+    plan->weights_bytes = generic_weights_bytes(z_dim, h1, h2, y_dim);
+    return 0;
+}
+
 extern "C" int dvae_mcem_pack(const dvae_mcem_plan_t* plan, const float* W3, int ld3, const float* b3, const float* W4, int ld4,
                               const float* b4, const float* W5, int ld5, const float* b5, void* weights, void* stream) {
     DVAE_CHECK_ARG(plan && W3 && b3 && W4 && b4 && W5 && b5 && weights, "mcem_pack: null argument");
+    if (plan->h2_dim != 0) {
+        DVAE_CHECK_ARG(ld3 >= plan->z_dim + plan->y_dim && ld4 >= plan->h_dim && ld5 >= plan->h2_dim,
+                       "mcem_pack: row strides (%d, %d, %d) too small for the plan's (%d, %d, %d)", ld3, ld4, ld5, plan->z_dim + plan->y_dim, plan->h_dim, plan->h2_dim);
+        return generic_pack(plan, W3, ld3, b3, W4, ld4, b4, W5, ld5, b5, weights, (hipStream_t)stream);
+    }
     DVAE_CHECK_ARG(ld3 >= ZD + plan->y_dim && ld4 >= HD && ld5 >= HD, "mcem_pack: row strides too small");
     const McemLayout L = mcem_layout(plan->y_dim, plan->precision);
     hipStream_t s = (hipStream_t)stream;

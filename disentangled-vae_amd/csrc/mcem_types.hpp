@@ -3,6 +3,7 @@
 #include <stdint.h>
 #include <hip/hip_runtime.h>
 #include "common.hpp"
+#include "../../include/dvae_mcem.h"
 
 namespace dvae {
 namespace fused {
@@ -91,6 +92,12 @@ int launch_resident16_chain(int precision, int yp, const MhArgs& a, hipStream_t 
 // chip in two rounds (DVAE_MCEM_TILE=4 forces it)
 bool resident4_chain_supported(int precision, int yp);
 int launch_resident4_chain(int yp, const MhArgs& a, hipStream_t s);
+
+// the chain for a decoder of any size (mcem_generic.hip; plans made by dvae_mcem_plan_dims: h2_dim != 0).  Sizes come from the plan.
+int64_t generic_weights_bytes(int z_dim, int h1, int h2, int y_dim);
+int generic_pack(const dvae_mcem_plan_t* plan, const float* W3, int ld3, const float* b3, const float* W4, int ld4, const float* b4,
+                 const float* W5, int ld5, const float* b5, void* weights, hipStream_t s);
+int launch_generic_chain(const dvae_mcem_plan_t* plan, const void* wcopy, const MhArgs& a, hipStream_t s);
 
 }  // namespace fused
 }  // namespace dvae

@@ -13,12 +13,13 @@ from . import native as N
 from . import stft as STFT
 
 F_BINS, Z_DIM, H_DIM = 513, 16, 128
+Z_MAX, H_MAX = 128, 512                         # limits of the generic chain (dvae_mcem_plan_dims)
 PREC = {"fp32": 0, "bf16": 1, "bf16x3": 2}      # bf16x3: split-bf16 operands (hi + lo planes, three MFMAs per product): parity grade
 
 
 class McemPlan(ctypes.Structure):
     _fields_ = [("y_dim", ctypes.c_int32), ("precision", ctypes.c_int32), ("x_dim", ctypes.c_int32),
-                ("z_dim", ctypes.c_int32), ("h_dim", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("z_dim", ctypes.c_int32), ("h_dim", ctypes.c_int32), ("h2_dim", ctypes.c_int32),
                 ("weights_bytes", ctypes.c_int64)]
 
 
@@ -40,16 +41,50 @@ def decoder_supported(decoder, y_dim):
             and (y_dim == 0 or 1 <= y_dim <= 16 or y_dim == F_BINS))
 
 
-class DecoderPack:
-    """Kernel-layout copy of `vae.decoder` (packages/models/models.py:108-122) for the MCEM kernels."""
+def _generic_dims(decoder, y_dim):
+    """(z_dim, h1, h2) where the generic chain covers the decoder, else None: two hidden layers, [z + y_dim] -> h1 -> h2 -> 513."""
+    hs = list(decoder.hidden)
+    if len(hs) != 2 or decoder.reconstruction.out_features != F_BINS:
+        return None
+    z, h1, h2 = hs[0].in_features - y_dim, hs[0].out_features, hs[1].out_features
+    if hs[1].in_features != h1 or decoder.reconstruction.in_features != h2:
+        return None
+    if not (1 <= z <= Z_MAX and 1 <= h1 <= H_MAX and 1 <= h2 <= H_MAX and 0 <= y_dim <= F_BINS):
+        return None
+    return z, h1, h2
 
-    def __init__(self, decoder, y_dim, precision="fp32"):
+
+def chain_kind(decoder, y_dim):
+    """Which Metropolis-Hastings chain serves `decoder` fed [z | y_dim label rows]: "resident" (the hand-tuned kernels of the
+    reference's geometry, decoder_supported), "generic" (csrc/mcem_generic.hip: two hidden layers, z_dim 1..128, hidden widths 1..512,
+    y_dim 0..513, 513 bins, fp32) or None.  Reads layer shapes only: works on CPU modules."""
+    if _generic_dims(decoder, y_dim) is None:
+        return None
+    return "resident" if decoder_supported(decoder, y_dim) else "generic"
+
+
+class DecoderPack:
+    """Kernel-layout copy of `vae.decoder` (packages/models/models.py:108-122) for the MCEM kernels.  generic=True puts a decoder
+    of the reference's geometry on the generic kernel too (every other covered size is there anyway)."""
+
+    def __init__(self, decoder, y_dim, precision="fp32", generic=False):
         self.lib = N.load()
-        if not decoder_supported(decoder, y_dim):
-            raise RuntimeError("MCEM kernels: decoder geometry not supported (need [16+y_dim]-128-128-513, y_dim 0/1..16/513)")
+        kind = chain_kind(decoder, y_dim)
+        if kind is None:
+            raise RuntimeError("MCEM kernels: decoder geometry not supported (need two hidden layers, [z_dim+y_dim]-h1-h2-513 with z_dim 1..128, "
+                               "h1 / h2 1..512, y_dim 0..513)")
         self.y_dim = y_dim
         self.plan = McemPlan()
-        N.check(self.lib.dvae_mcem_plan(y_dim, PREC[precision], ctypes.byref(self.plan)), "dvae_mcem_plan")
+        self.generic = generic or kind == "generic"
+        if self.generic:
+            if precision != "fp32":
+                raise RuntimeError(f"MCEM kernels: precision {precision!r} exists for the [16+y_dim]-128-128-513 decoder only (y_dim 0/1..16/513); "
+                                   "the generic chain computes in fp32")
+            z, h1, h2 = _generic_dims(decoder, y_dim)
+            N.check(self.lib.dvae_mcem_plan_dims(z, h1, h2, y_dim, PREC[precision], ctypes.byref(self.plan)), "dvae_mcem_plan_dims")
+        else:
+            N.check(self.lib.dvae_mcem_plan(y_dim, PREC[precision], ctypes.byref(self.plan)), "dvae_mcem_plan")
+        self.z_dim = int(self.plan.z_dim)
         dev = decoder.reconstruction.weight.device
         self.weights = torch.empty(self.plan.weights_bytes, dtype=torch.uint8, device=dev)
         self.repack(decoder)
@@ -65,6 +100,7 @@ class DecoderPack:
     # sample_posterior (mcem.py:207-277, 372-448) [+ compute_Vs of the kept samples when want_vs]
     def sample(self, Z, y, g, Vb, X2, noise, logu, burnin, var_rw=0.01, want_vs=True, trace=False):
         nit, L, n = noise.shape
+        Z_DIM = self.z_dim
         assert L == Z_DIM and Z.shape == (Z_DIM, n) and logu.shape == (nit, n) and Vb.shape == (F_BINS, n) and X2.shape == (F_BINS, n)
         R = nit - burnin
         Z, g, Vb, X2, noise, logu = (_f32c(a, nm) for a, nm in ((Z, "Z"), (g, "g"), (Vb, "Vb"), (X2, "X2"), (noise, "noise"), (logu, "logu")))
@@ -83,7 +119,7 @@ class DecoderPack:
     # compute_Vs (mcem.py:280-290): Zs (N, R, 16) -> (R, F, N)
     def decode(self, Zs, y):
         n, R, L = Zs.shape
-        assert L == Z_DIM
+        assert L == self.z_dim
         Zs = _f32c(Zs, "Zs")
         y = _f32c(y, "y") if self.y_dim else None
         Vs = torch.empty((R, F_BINS, n), dtype=torch.float32, device=Zs.device)
@@ -230,7 +266,6 @@ class McemBatch:
         self.H = torch.ones((K, self.ntot), dtype=torch.float32, device=dev)
         self.Vb = torch.ones((F_BINS, self.ntot), dtype=torch.float32, device=dev)
         self.g = torch.ones(self.ntot, dtype=torch.float32, device=dev)
-        self.Z = torch.zeros((Z_DIM, self.ntot), dtype=torch.float32, device=dev)
         self.W = torch.empty((U, F_BINS, K), dtype=torch.float32, device=dev)
         self.y = None
         if self.label_in_decoder:
@@ -274,6 +309,9 @@ class McemBatch:
             self.y = torch.zeros((yrows.shape[1], self.ntot), dtype=torch.float32, device=dev)
             self.y.index_copy_(1, colidx, yrows.T)
         enc_y = self.y.shape[0] if self.label_in_encoder else 0
+        if not E.encoder_supported(self.vae.encoder, enc_y):
+            raise ValueError("McemBatch.init_parameters: fused_start needs an encoder that encode.EncoderPack covers ([513+y]-128-128-16, y_dim 0, 1 "
+                             "or 513); the default start (fused_start=False) runs vae.encoder at any size")
         self.Z = torch.zeros((Z_DIM, self.ntot), dtype=torch.float32, device=dev)
         E.encode_rows(E.EncoderPack(self.vae.encoder, enc_y), spec.frames, spec.frame_off, y=yrows if enc_y else None, Z=self.Z, cols=self.starts,
                       tables_dev=tab_dev)
@@ -289,7 +327,7 @@ class McemBatch:
     def _chain(self, nsamples, burnin, draws=None):
         nit = nsamples + burnin
         if draws is None:
-            noise = torch.randn(nit, Z_DIM, self.ntot, device=self.Z.device)
+            noise = torch.randn(nit, self._pack.z_dim, self.ntot, device=self.Z.device)
             logu = torch.log(torch.rand(nit, self.ntot, device=self.Z.device))
         else:
             noise, logu = draws
@@ -300,7 +338,7 @@ class McemBatch:
         dev = self.Z.device
         if getattr(self, "_bufs", None) is None or self._bufs[0].shape[0] != self.ntot or self._bufs[0].shape[1] != self.n_e:
             lib = self._pack.lib
-            self._bufs = (torch.empty((self.ntot, self.n_e, Z_DIM), dtype=torch.float32, device=dev),
+            self._bufs = (torch.empty((self.ntot, self.n_e, self._pack.z_dim), dtype=torch.float32, device=dev),
                           torch.empty((self.n_e, F_BINS, self.ntot), dtype=torch.float32, device=dev),
                           torch.empty(lib.dvae_mcem_m_step_workspace_bytes(self.ntot, self.K, len(self.counts)), dtype=torch.uint8, device=dev))
         return self._bufs
@@ -342,6 +380,7 @@ class McemBatch:
         U = len(self.counts)
         cost = torch.empty((self.niter, U), dtype=torch.float32, device=dev)
         nit = self.n_e + self.b_e
+        Z_DIM = self._pack.z_dim
         for a, nm in ((self.Z, "Z"), (self.g, "g"), (self.Vb, "Vb"), (self.X2, "X2"), (self.W, "W"), (self.H, "H")):
             if not (a.is_cuda and a.dtype == torch.float32 and a.is_contiguous()):
                 raise RuntimeError(f"McemBatch.run: {nm} must be a contiguous float32 CUDA tensor")

@@ -112,6 +112,7 @@ SIGNATURES = {
     "dvae_comm_destroy": (c_i, [c_vp]),
     # include/dvae_mcem.h
     "dvae_mcem_plan": (c_i, [c_i, c_i, c_vp]),
+    "dvae_mcem_plan_dims": (c_i, [c_i, c_i, c_i, c_i, c_i, c_vp]),
     "dvae_mcem_pack": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_i, c_vp, c_vp, c_i, c_vp, c_vp, c_vp]),
     "dvae_mcem_sample": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_f, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dvae_mcem_decode": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i, c_i64, c_vp, c_vp]),

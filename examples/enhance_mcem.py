@@ -80,12 +80,18 @@ def main():
     ap.add_argument("--score", action="store_true", help="with --synthetic (whose speech is known): SI-SDR and ESTOI of mixture and estimate per utterance")
     ap.add_argument("--snr", type=float, nargs="+", default=None, help="with --synthetic: mix every utterance with synthetic noise at each of "
                     "these SNRs (dB) on the device instead of adding a fixed 0.2 * randn on the host")
+    ap.add_argument("--z-dim", type=int, default=16, help="latent size of the random-weight model (any 1..128: sizes other than the "
+                    "reference's 16 / 128 / 128 run the generic fp32 chain, mcem.chain_kind)")
+    ap.add_argument("--h-dim", type=int, nargs=2, default=[128, 128], metavar=("H1", "H2"), help="hidden widths of the random-weight model (1..512 each)")
     ap.add_argument("--trim", type=int, default=800, help="samples cut at both ends before scoring (run_metrics.py:117-121: 0.05 s)")
     a = ap.parse_args()
     if a.score and (a.wav or not a.synthetic):
         ap.error("--score needs the clean speech, which only --synthetic mixtures come with")
     if a.snr is not None and (a.wav or not a.synthetic):
         ap.error("--snr mixes the --synthetic utterances")
+    if (a.z_dim, list(a.h_dim)) != (16, [128, 128]) and (a.checkpoint or a.fused_start or a.labels == "classifier" or a.precision != "fp32"):
+        ap.error("--z-dim / --h-dim size the random-weight model of the default flow: fp32, VAD labels, no --checkpoint, no --fused-start "
+                 "(the encoder and classifier kernels cover 513-128-128-16 only)")
     names, waves, clean = [], [], []
     for p in a.wav:
         fs, w = wavfile.read(p)
@@ -97,7 +103,8 @@ def main():
     if not waves:
         ap.error("give --wav files or --synthetic N")
     torch.manual_seed(0)
-    vae = DeepGenerativeModel_v5([513, 1, 16, [128, 128]]) if a.labels == "classifier" else DeepGenerativeModel([513, 1, 16, [128, 128]], None)
+    sizes = [513, 1, a.z_dim, list(a.h_dim)]
+    vae = DeepGenerativeModel_v5(sizes) if a.labels == "classifier" else DeepGenerativeModel(sizes, None)
     if a.checkpoint:
         vae.load_state_dict(torch.load(a.checkpoint, map_location="cpu", weights_only=True))
     vae = vae.cuda().eval()

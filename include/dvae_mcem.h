@@ -2,10 +2,13 @@
  *
  * Reference: packages/models/mcem.py (classes EM, MCEM_M1, MCEM_M2, MCEM_M2v2, MCEM_M2v3), driven by
  * scripts/evaluate_ntcd_M1.py / _M2.py / _M2_info_vad.py (`mcem.init_parameters(...)`, `mcem.run()`).
- * For the geometry those scripts use (F = 513 bins, latent 16, decoder 128-128-513, y_dim 0 / 1 / 513).
+ * dvae_mcem_plan: the geometry those scripts use (F = 513 bins, latent 16, decoder 128-128-513, y_dim 0 / 1..16 / 513), hand-tuned kernels.
+ * dvae_mcem_plan_dims: any decoder with two tanh hidden layers, [z_dim + y_dim] -> h1 -> h2 -> 513, on one generic fp32 kernel.
  *
  * Array shapes are the reference's own (row-major, fp32): X2, Vb, WFs, WFn (F, N); Vs (R, F, N);
- * Z (16, N); y (y_dim, N); g (N); W (F, K); H (K, N); sampled latents (N, R, 16).
+ * Z (16, N); y (y_dim, N); g (N); W (F, K); H (K, N); sampled latents (N, R, 16).  Under a plan of dvae_mcem_plan_dims every "16"
+ * below reads plan.z_dim: Z (z_dim, N), noise (nit, z_dim, N), Zs (N, R, z_dim); the decoder's layers are hidden.0 [h1][z_dim + y_dim],
+ * hidden.1 [h2][h1], reconstruction [513][h2].
  * All pointers are caller-owned device memory; calls enqueue on `stream` and do not synchronise.
  * Every random number is an argument: the caller draws `noise` and `logu` (the reference draws them with
  * torch.randn / torch.rand inside the loop, mcem.py:244,257).
@@ -25,12 +28,20 @@ typedef struct {
     int32_t y_dim;            /* label rows fed to the decoder next to z: 0 (MCEM_M1), 1..16 or 513 */
     int32_t precision;        /* DVAE_PREC_F32 (exact fp32 products), DVAE_PREC_BF16X3 (split-bf16 operands: 16 mantissa bits, three MFMAs
                                  per product -- parity grade at a fraction of the fp32 matrix cost) or DVAE_PREC_BF16 (one bf16 per operand) */
-    int32_t x_dim, z_dim, h_dim;   /* echoed: 513, 16, 128 */
-    int32_t reserved;
+    int32_t x_dim, z_dim, h_dim;   /* echoed: 513, 16, 128; dvae_mcem_plan_dims: 513, z_dim, h1 */
+    int32_t h2_dim;           /* 0: a plan of dvae_mcem_plan (the hand-tuned kernels); dvae_mcem_plan_dims: h2, and the plan selects the generic kernel */
     int64_t weights_bytes;    /* size of the kernel-layout decoder copy filled by dvae_mcem_pack */
 } dvae_mcem_plan_t;
 
 int dvae_mcem_plan(int y_dim, int precision, dvae_mcem_plan_t* plan);
+
+/* The plan of a decoder of any size: z_dim 1..128, h1 and h2 1..512, y_dim 0..513 (any value), 513 bins; DVAE_E_BADARG names the limit
+ * otherwise.  precision: DVAE_PREC_F32 only (exact fp32 products); the other two return DVAE_E_UNSUPPORTED.  Such a plan ALWAYS selects
+ * the generic kernel (csrc/mcem_generic.hip), at 16 / 128 / 128 too, so both kernels can be put on the same inputs; dvae_mcem_plan is
+ * unchanged and remains the way to the hand-tuned kernels.  dvae_mcem_pack (row strides checked against the plan's sizes),
+ * dvae_mcem_sample, dvae_mcem_decode, dvae_mcem_em_iteration and dvae_mcem_em_iteration_lazy take either plan.  The generic chain has no
+ * 2 GiB rule (64-bit indexing); a frame's chain gives the same bits alone and as any column of any launch. */
+int dvae_mcem_plan_dims(int z_dim, int h1, int h2, int y_dim, int precision, dvae_mcem_plan_t* plan);
 
 /* Measurement only (no reference counterpart): while buf != NULL the weight-stationary chain kernel adds, per (workgroup, wave), the shader
  * clocks it spends in each of its 9 chain-step phases into buf[(workgroup * 4 + wave) * 16 + phase] (tools/stamp_mcem.py); NULL switches it off. */

@@ -225,6 +225,8 @@ class _MCEM(EM):
     def _decoder_pack(self):
         if self._pack is None:
             y_dim = self.y.shape[0] if self._label_in_decoder else 0
+            # the hand-tuned chain where it applies, the generic fp32 chain for every other covered size; a non-fp32 precision with a
+            # generic decoder raises there
             self._pack = _native.mcem_dev().DecoderPack(self.vae.decoder, y_dim, self.precision)
         return self._pack
 
@@ -274,7 +276,7 @@ class _MCEM(EM):
         return self.nsamples_WF, self.burnin_WF
 
     def run(self):
-        """EM.run (reference mcem.py:156-179).  On the device, with the decoder geometry the kernels cover, the loop body -- E_step, M_step,
+        """EM.run (reference mcem.py:156-179).  On the device, with a decoder a chain kernel covers (mcem.chain_kind), the loop body -- E_step, M_step,
         cost -- is ONE library call per iteration (dvae_mcem_em_iteration) on buffers allocated once, the generator's draws are made for
         many iterations at a time, and the cost is read back once after the loop: the reference's loop stores `cost[n]` into a numpy array,
         i.e. it synchronises with the device and crosses the interpreter a dozen times in every iteration (evaluate_ntcd_M2.py:201-205
@@ -284,7 +286,7 @@ class _MCEM(EM):
         dev_mod = _native.mcem_dev() if self._on_device() else None
         y_dim = self.y.shape[0] if self._label_in_decoder else 0
         if (dev_mod is None or os.environ.get("DVAE_MCEM_RUN", "fused") == "steps" or self.W.dtype != torch.float32
-                or not dev_mod.decoder_supported(self.vae.decoder, y_dim) or self.W.shape[1] > 16):
+                or dev_mod.chain_kind(self.vae.decoder, y_dim) is None or self.W.shape[1] > 16):
             return EM.run(self)
         import ctypes
         Nn = dev_mod.N
