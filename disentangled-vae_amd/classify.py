@@ -20,6 +20,7 @@ from . import target as TGT
 
 F_BINS, H_DIM = 513, 128
 Y_DIMS = (1, F_BINS)
+H_MAX = 512                                     # limit of the generic kernel (csrc/mlp_generic.hip), that of dvae_mcem_plan_dims
 
 
 def _shape(clf):
@@ -46,15 +47,52 @@ def classifier_supported(clf):
             and out.in_features == H_DIM and out.out_features in Y_DIMS)
 
 
+def _generic_dims(clf):
+    """(h1, h2, y_dim) where the generic kernel covers the classifier, else None: a Classifier without batch norm, two hidden Linear
+    layers with biases, 513 -> h1 -> h2 -> y_dim within the limits."""
+    from packages.models.models import Classifier
+    if not isinstance(clf, Classifier):
+        return None
+    hs = list(clf.hidden)
+    out = clf.output_layer
+    if len(hs) != 2 or not all(isinstance(l, nn.Linear) and l.bias is not None for l in hs + [out]):
+        return None
+    h1, h2, y = hs[0].out_features, hs[1].out_features, out.out_features
+    if hs[0].in_features != F_BINS or hs[1].in_features != h1 or out.in_features != h2:
+        return None
+    if not (1 <= h1 <= H_MAX and 1 <= h2 <= H_MAX and 1 <= y <= F_BINS):
+        return None
+    return h1, h2, y
+
+
+def classifier_kind(clf):
+    """Which kernel serves `clf`: "resident" (classify.hip: the reference's geometry, classifier_supported), "generic"
+    (csrc/mlp_generic.hip: two hidden layers, hidden widths 1..512, y_dim 1..513, 513 bins, no batch norm, fp32) or None.  Reads
+    layer shapes only: works on CPU modules."""
+    if _generic_dims(clf) is None:
+        return None
+    return "resident" if classifier_supported(clf) else "generic"
+
+
 class ClassifierPack:
     """The six state_dict tensors of a Classifier in one contiguous float32 device buffer, the layout of dvae_classify_batch:
-    W1 [128][513] | b1 | W2 [128][128] | b2 | W3 [y_dim][128] | b3.  repack(clf) after training."""
+    W1 [128][513] | b1 | W2 [128][128] | b2 | W3 [y_dim][128] | b3.  repack(clf) after training.  generic=True: the fragment-order
+    copy of dvae_classify_generic_pack for the generic kernel, which covers every geometry classifier_kind names (the reference's
+    too); h1, h2, y_dim: the geometry."""
 
-    def __init__(self, clf):
-        if not classifier_supported(clf):
-            raise TypeError(f"classify_batch: the kernel covers Classifier [513->128, 128->128, 128->1 or 513] without batch norm, "
-                            f"got {_shape(clf)}")
-        self.y_dim = clf.output_layer.out_features
+    def __init__(self, clf, generic=False):
+        self.generic = bool(generic)
+        if self.generic:
+            dims = _generic_dims(clf)
+            if dims is None:
+                raise TypeError(f"classify_batch: the generic kernel covers Classifier [513->h1, h1->h2, h2->y_dim] without batch norm, "
+                                f"h1 / h2 1..{H_MAX}, y_dim 1..{F_BINS}, got {_shape(clf)}")
+            self.h1, self.h2, self.y_dim = dims
+        else:
+            if not classifier_supported(clf):
+                raise TypeError(f"classify_batch: the kernel covers Classifier [513->128, 128->128, 128->1 or 513] without batch norm, "
+                                f"got {_shape(clf)}")
+            self.h1, self.h2, self.y_dim = H_DIM, H_DIM, clf.output_layer.out_features
         self.weights = None
         self.repack(clf)
 
@@ -64,6 +102,21 @@ class ClassifierPack:
             raise RuntimeError("classify_batch: the classifier's parameters must be CUDA tensors (no CPU fallback)")
         if any(t.dtype != torch.float32 for t in ts):
             raise TypeError("classify_batch: the HIP path computes in float32")
+        if self.generic:
+            if _generic_dims(clf) != (self.h1, self.h2, self.y_dim):
+                raise TypeError(f"classify_batch: repack: {_shape(clf)} is not the geometry this pack was made for")
+            lib = N.load()
+            want = lib.dvae_classify_generic_weights_floats(self.h1, self.h2, self.y_dim)
+            dev = ts[0].device
+            if self.weights is None or self.weights.device != dev:
+                self.weights = torch.empty(want, dtype=torch.float32, device=dev)
+            ts = [t.contiguous() for t in ts]
+            with torch.cuda.device(dev):
+                N.check(lib.dvae_classify_generic_pack(self.h1, self.h2, self.y_dim, N.ptr(ts[0]), ts[0].stride(0), N.ptr(ts[1]), N.ptr(ts[2]),
+                                                       ts[2].stride(0), N.ptr(ts[3]), N.ptr(ts[4]), ts[4].stride(0), N.ptr(ts[5]),
+                                                       N.ptr(self.weights), N.stream()), "dvae_classify_generic_pack")
+            self._keep = ts                  # the pack kernels read them on the stream
+            return
         flat = torch.cat([t.reshape(-1) for t in ts])
         want = N.load().dvae_classify_weights_floats(self.y_dim)
         if flat.numel() != want:
@@ -72,6 +125,12 @@ class ClassifierPack:
             self.weights = flat
         else:
             self.weights.copy_(flat)
+
+
+def pack_classifier(clf):
+    """The pack of `clf` by classifier_kind: the resident pack wherever it applies, the generic one for every other covered
+    geometry; TypeError naming the shape and the limits for a classifier no kernel covers."""
+    return ClassifierPack(clf, generic=classifier_kind(clf) != "resident")
 
 
 def frame_table(op, counts, n_rows, first=0):
@@ -133,7 +192,8 @@ def _rows(op, t, name, width=None):
 
 def classify_rows(pack, src, frame_off, soft, hard, logits=None):
     """dvae_classify_batch on device buffers: src complex64 [N, 513] frames or float32 [N, >= 513 by stride] power rows, frame_off the
-    host prefix [U + 1], soft / hard / logits float32 [N, y_dim] written in place for the rows inside the table and nowhere else."""
+    host prefix [U + 1], soft / hard / logits float32 [N, y_dim] written in place for the rows inside the table and nowhere else.
+    With a generic pack the same through dvae_classify_generic_batch."""
     lib = N.load()
     is_complex = src.dtype == torch.complex64
     ld = F_BINS if is_complex else N.ld(src)
@@ -142,6 +202,11 @@ def classify_rows(pack, src, frame_off, soft, hard, logits=None):
         if o is not None and not (o.is_cuda and o.dtype == torch.float32 and o.is_contiguous() and tuple(o.shape) == (src.shape[0], pack.y_dim)):
             raise ValueError(f"classify_batch: {name} must be contiguous float32 CUDA rows [{src.shape[0]}, {pack.y_dim}]")
     with torch.cuda.device(src.device):
+        if pack.generic:
+            N.check(lib.dvae_classify_generic_batch(N.ptr(src), int(is_complex), ld, src.shape[0], off.size - 1, off.ctypes.data, N.ptr(pack.weights),
+                                                    pack.y_dim, pack.h1, pack.h2, N.ptr(soft), N.ptr(hard), N.ptr(logits), N.stream()),
+                    "dvae_classify_generic_batch")
+            return
         N.check(lib.dvae_classify_batch(N.ptr(src), int(is_complex), ld, src.shape[0], off.size - 1, off.ctypes.data, N.ptr(pack.weights), pack.y_dim,
                                         N.ptr(soft), N.ptr(hard), N.ptr(logits), N.stream()), "dvae_classify_batch")
 
@@ -149,7 +214,8 @@ def classify_rows(pack, src, frame_off, soft, hard, logits=None):
 def classify_batch(clf_or_pack, spec_or_rows, counts=None, want_logits=False):
     """The classifier's labels for every frame of a ragged batch -> LabelBatch.
 
-    clf_or_pack: a Classifier on the device (packed here) or its ClassifierPack (pack once, label many batches).  spec_or_rows: a
+    clf_or_pack: a Classifier on the device (packed here) or its ClassifierPack of either kind (pack once, label many batches;
+    pack_classifier picks the kernel).  spec_or_rows: a
     SpecBatch of complex frames (layout 2: |X|^2 is formed in the kernel, McemBatch.X2's bits) or of power frames (layout 1); a
     FrameBatch (its X rows); or float32 CUDA power rows [N, 513] (any row stride >= 513, e.g. DeviceFrames.x) with counts, the
     frames of each utterance laid end to end from row 0 (counts=None: one utterance of all rows).  TypeError naming the shape for a

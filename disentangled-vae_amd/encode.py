@@ -22,6 +22,7 @@ from .classify import LabelBatch, frame_table, _rows
 
 F_BINS, H_DIM, Z_DIM = 513, 128, 16
 Y_DIMS = (0, 1, F_BINS)
+Z_MAX, H_MAX = 128, 512                         # limits of the generic kernel (csrc/mlp_generic.hip), those of dvae_mcem_plan_dims
 
 
 def _shape(enc):
@@ -48,14 +49,53 @@ def encoder_supported(encoder, y_dim):
             and all(l.in_features == H_DIM and l.out_features == Z_DIM for l in heads))
 
 
+def _generic_dims(encoder, y_dim):
+    """(h1, h2, z_dim) where the generic kernel covers the encoder, else None: an Encoder with a GaussianSample layer and two hidden
+    Linear layers with biases, [513 + y_dim] -> h1 -> h2 -> {mu z, log_var z} within the limits."""
+    from packages.models.models import Encoder, GaussianSample
+    if not isinstance(encoder, Encoder) or type(getattr(encoder, "sample", None)) is not GaussianSample:
+        return None
+    y_dim = int(y_dim)
+    hs = list(encoder.hidden)
+    heads = [encoder.sample.mu, encoder.sample.log_var]
+    if len(hs) != 2 or not all(isinstance(l, nn.Linear) and l.bias is not None for l in hs + heads):
+        return None
+    h1, h2, z = hs[0].out_features, hs[1].out_features, heads[0].out_features
+    if hs[0].in_features != F_BINS + y_dim or hs[1].in_features != h1 or any(l.in_features != h2 or l.out_features != z for l in heads):
+        return None
+    if not (0 <= y_dim <= F_BINS and 1 <= h1 <= H_MAX and 1 <= h2 <= H_MAX and 1 <= z <= Z_MAX):
+        return None
+    return h1, h2, z
+
+
+def encoder_kind(encoder, y_dim):
+    """Which kernel serves `encoder` fed [x | y_dim label columns]: "resident" (encode.hip: the reference's geometry,
+    encoder_supported), "generic" (csrc/mlp_generic.hip: two hidden layers, hidden widths 1..512, z_dim 1..128, y_dim 0..513, 513
+    bins, fp32) or None.  Reads layer shapes only: works on CPU modules."""
+    if _generic_dims(encoder, y_dim) is None:
+        return None
+    return "resident" if encoder_supported(encoder, y_dim) else "generic"
+
+
 class EncoderPack:
     """The eight state_dict tensors of an Encoder in one contiguous float32 device buffer, the layout of dvae_encode_batch:
-    W1 [128][513 + y_dim] | b1 | W2 [128][128] | b2 | Wmu [16][128] | bmu | Wlv [16][128] | blv.  repack(encoder) after training."""
+    W1 [128][513 + y_dim] | b1 | W2 [128][128] | b2 | Wmu [16][128] | bmu | Wlv [16][128] | blv.  repack(encoder) after training.
+    generic=True: the fragment-order copy of dvae_encode_generic_pack for the generic kernel, which covers every geometry
+    encoder_kind names (the reference's too); z_dim, h1, h2, y_dim: the geometry."""
 
-    def __init__(self, encoder, y_dim):
-        if not encoder_supported(encoder, y_dim):
-            raise TypeError(f"encode_batch: the kernel covers Encoder [513+y->128, 128->128, 128->16, 128->16] with y_dim 0, 1 or 513, "
-                            f"got {_shape(encoder)} with y_dim {y_dim}")
+    def __init__(self, encoder, y_dim, generic=False):
+        self.generic = bool(generic)
+        if self.generic:
+            dims = _generic_dims(encoder, y_dim)
+            if dims is None:
+                raise TypeError(f"encode_batch: the generic kernel covers Encoder [513+y->h1, h1->h2, h2->z, h2->z] with y_dim 0..{F_BINS}, "
+                                f"h1 / h2 1..{H_MAX}, z 1..{Z_MAX}, got {_shape(encoder)} with y_dim {y_dim}")
+            self.h1, self.h2, self.z_dim = dims
+        else:
+            if not encoder_supported(encoder, y_dim):
+                raise TypeError(f"encode_batch: the kernel covers Encoder [513+y->128, 128->128, 128->16, 128->16] with y_dim 0, 1 or 513, "
+                                f"got {_shape(encoder)} with y_dim {y_dim}")
+            self.h1, self.h2, self.z_dim = H_DIM, H_DIM, Z_DIM
         self.y_dim = int(y_dim)
         self.weights = None
         self.repack(encoder)
@@ -66,6 +106,22 @@ class EncoderPack:
             raise RuntimeError("encode_batch: the encoder's parameters must be CUDA tensors (no CPU fallback)")
         if any(t.dtype != torch.float32 for t in ts):
             raise TypeError("encode_batch: the HIP path computes in float32")
+        if self.generic:
+            if _generic_dims(encoder, self.y_dim) != (self.h1, self.h2, self.z_dim):
+                raise TypeError(f"encode_batch: repack: {_shape(encoder)} is not the geometry this pack was made for")
+            lib = N.load()
+            want = lib.dvae_encode_generic_weights_floats(self.y_dim, self.h1, self.h2, self.z_dim)
+            dev = ts[0].device
+            if self.weights is None or self.weights.device != dev:
+                self.weights = torch.empty(want, dtype=torch.float32, device=dev)
+            ts = [t.contiguous() for t in ts]
+            with torch.cuda.device(dev):
+                N.check(lib.dvae_encode_generic_pack(self.y_dim, self.h1, self.h2, self.z_dim, N.ptr(ts[0]), ts[0].stride(0), N.ptr(ts[1]),
+                                                     N.ptr(ts[2]), ts[2].stride(0), N.ptr(ts[3]), N.ptr(ts[4]), ts[4].stride(0), N.ptr(ts[5]),
+                                                     N.ptr(ts[6]), ts[6].stride(0), N.ptr(ts[7]), N.ptr(self.weights), N.stream()),
+                        "dvae_encode_generic_pack")
+            self._keep = ts                  # the pack kernels read them on the stream
+            return
         flat = torch.cat([t.reshape(-1) for t in ts])
         want = N.load().dvae_encode_weights_floats(self.y_dim)
         if flat.numel() != want:
@@ -76,10 +132,16 @@ class EncoderPack:
             self.weights.copy_(flat)
 
 
+def pack_encoder(encoder, y_dim):
+    """The pack of `encoder` by encoder_kind: the resident pack wherever it applies, the generic one for every other covered
+    geometry; TypeError naming the shape and the limits for an encoder no kernel covers."""
+    return EncoderPack(encoder, y_dim, generic=encoder_kind(encoder, y_dim) != "resident")
+
+
 class LatentBatch:
-    """The latents of a ragged batch on the device, frame-major: mu, log_var float32 [N, 16], z [N, 16] or None (no eps given),
-    utterance u at rows frame_off[u] : frame_off[u + 1]; counts: T_u.  view(u, which): the (16, T_u) view of "mu", "log_var" or
-    "z", the orientation the reference's scripts hold latents in."""
+    """The latents of a ragged batch on the device, frame-major: mu, log_var float32 [N, z_dim], z [N, z_dim] or None (no eps
+    given), utterance u at rows frame_off[u] : frame_off[u + 1]; counts: T_u.  view(u, which): the (z_dim, T_u) view of "mu",
+    "log_var" or "z", the orientation the reference's scripts hold latents in."""
 
     def __init__(self, mu, log_var, z, counts, frame_off=None):
         self.mu, self.log_var, self.z = mu, log_var, z
@@ -124,10 +186,10 @@ def column_table(op, frame_off, cols, ntot):
     return cols
 
 
-def _out_ok(op, name, o, n_rows, dev):
+def _out_ok(op, name, o, n_rows, dev, z_dim=Z_DIM):
     if o is not None and not (torch.is_tensor(o) and o.is_cuda and o.device == dev and o.dtype == torch.float32 and o.is_contiguous()
-                              and tuple(o.shape) == (n_rows, Z_DIM)):
-        raise ValueError(f"{op}: {name} must be contiguous float32 CUDA rows [{n_rows}, {Z_DIM}] beside the frames")
+                              and tuple(o.shape) == (n_rows, z_dim)):
+        raise ValueError(f"{op}: {name} must be contiguous float32 CUDA rows [{n_rows}, {z_dim}] beside the frames")
 
 
 def encode_rows(pack, src, frame_off, y=None, eps=None, mu=None, log_var=None, z=None, Z=None, cols=None, tables_dev=None):
@@ -135,7 +197,8 @@ def encode_rows(pack, src, frame_off, y=None, eps=None, mu=None, log_var=None, z
     host prefix [U + 1], y float32 label rows [N, y_dim by stride] (exactly when the pack has y_dim > 0), eps / mu / log_var / z
     float32 [N, 16], written in place for the rows inside the table and nowhere else.  Z float32 [16, ntot] with cols, the first
     column of every utterance: mu transposed into McemBatch's layout, the other columns untouched (tables_dev: the device table
-    [frame_off | cols] if the caller has it already, e.g. from dvae_mcem_spec_init)."""
+    [frame_off | cols] if the caller has it already, e.g. from dvae_mcem_spec_init).  With a generic pack the same through
+    dvae_encode_generic_batch, 16 being the pack's z_dim."""
     op = "encode_batch"
     lib = N.load()
     is_complex = src.dtype == torch.complex64
@@ -148,18 +211,24 @@ def encode_rows(pack, src, frame_off, y=None, eps=None, mu=None, log_var=None, z
                               and (n == 1 or y.stride(0) >= pack.y_dim)):
         raise ValueError(f"{op}: labels must be float32 CUDA rows [{n}, {pack.y_dim}]")
     for name, o in (("eps", eps), ("mu", mu), ("log_var", log_var), ("z", z)):
-        _out_ok(op, name, o, n, src.device)
+        _out_ok(op, name, o, n, src.device, pack.z_dim)
     if z is not None and eps is None:
         raise ValueError(f"{op}: z needs eps")
     ntot, col = 0, None
     if Z is not None:
-        if not (Z.is_cuda and Z.dtype == torch.float32 and Z.is_contiguous() and Z.dim() == 2 and Z.shape[0] == Z_DIM):
-            raise ValueError(f"{op}: Z must be a contiguous float32 CUDA tensor [{Z_DIM}, ntot]")
+        if not (Z.is_cuda and Z.dtype == torch.float32 and Z.is_contiguous() and Z.dim() == 2 and Z.shape[0] == pack.z_dim):
+            raise ValueError(f"{op}: Z must be a contiguous float32 CUDA tensor [{pack.z_dim}, ntot]")
         ntot = Z.shape[1]
         col = np.ascontiguousarray(column_table(op, off, cols, ntot))
         if tables_dev is None:
             tables_dev = R.upload(np.concatenate([off, col]), src.device)
     with torch.cuda.device(src.device):
+        if pack.generic:
+            N.check(lib.dvae_encode_generic_batch(N.ptr(src), int(is_complex), ld, N.ptr(y), N.ld(y) if y is not None else 0, n, off.size - 1,
+                                                  off.ctypes.data, N.ptr(pack.weights), pack.y_dim, pack.h1, pack.h2, pack.z_dim, N.ptr(eps), N.ptr(mu),
+                                                  N.ptr(log_var), N.ptr(z), N.ptr(Z), ntot, col.ctypes.data if col is not None else None,
+                                                  N.ptr(tables_dev) if Z is not None else None, N.stream()), "dvae_encode_generic_batch")
+            return
         N.check(lib.dvae_encode_batch(N.ptr(src), int(is_complex), ld, N.ptr(y), N.ld(y) if y is not None else 0, n, off.size - 1, off.ctypes.data,
                                       N.ptr(pack.weights), pack.y_dim, N.ptr(eps), N.ptr(mu), N.ptr(log_var), N.ptr(z), N.ptr(Z), ntot,
                                       col.ctypes.data if col is not None else None, N.ptr(tables_dev) if Z is not None else None, N.stream()),
@@ -201,13 +270,13 @@ def encode_batch(encoder_or_pack, spec_or_rows, labels=None, counts=None, eps=No
     """The encoder's latents for every frame of a ragged batch -> LatentBatch.
 
     encoder_or_pack: an Encoder on the device (packed here; its label width is y_dim if given, else the labels' width, else 0) or
-    its EncoderPack (pack once, encode many batches).  spec_or_rows: what classify_batch accepts -- a SpecBatch of complex frames
-    (layout 2: |X|^2 is formed in the kernel, McemBatch.X2's bits) or of power frames (layout 1); a FrameBatch (its X rows); or
-    float32 CUDA power rows [N, 513] (any row stride >= 513) with counts, the frames of each utterance laid end to end from row 0
-    (counts=None: one utterance of all rows).  labels (exactly for an encoder that takes them): a LabelBatch (its `use` labels,
-    "hard" or "soft"), a FrameBatch (its Y) or float32 CUDA rows [N, y_dim].  eps: float32 CUDA rows [N, 16]; with it z = mu +
-    exp(log_var / 2) eps is formed.  TypeError naming the shape for an encoder the kernel does not cover; ValueError naming the
-    utterance for tables that do not fit."""
+    its EncoderPack of either kind (pack once, encode many batches; pack_encoder picks the kernel).  spec_or_rows: what
+    classify_batch accepts -- a SpecBatch of complex frames (layout 2: |X|^2 is formed in the kernel, McemBatch.X2's bits) or of
+    power frames (layout 1); a FrameBatch (its X rows); or float32 CUDA power rows [N, 513] (any row stride >= 513) with counts,
+    the frames of each utterance laid end to end from row 0 (counts=None: one utterance of all rows).  labels (exactly for
+    an encoder that takes them): a LabelBatch (its `use` labels, "hard" or "soft"), a FrameBatch (its Y) or
+    float32 CUDA rows [N, y_dim].  eps: float32 CUDA rows [N, z_dim]; with it z = mu + exp(log_var / 2) eps is formed.  TypeError
+    naming the shape for an encoder the kernel does not cover; ValueError naming the utterance for tables that do not fit."""
     op = "encode_batch"
     src, counts = _source(op, spec_or_rows, counts)
     if isinstance(encoder_or_pack, EncoderPack):
@@ -226,24 +295,34 @@ def encode_batch(encoder_or_pack, spec_or_rows, labels=None, counts=None, eps=No
     if y is not None and y.shape[0] != src.shape[0]:
         raise ValueError(f"{op}: {y.shape[0]} label rows for {src.shape[0]} frames")
     if eps is not None:
-        eps = _rows(op, eps, "eps", Z_DIM).contiguous()
-    mu, log_var = (torch.empty((src.shape[0], Z_DIM), dtype=torch.float32, device=src.device) for _ in range(2))
+        eps = _rows(op, eps, "eps", pack.z_dim).contiguous()
+    mu, log_var = (torch.empty((src.shape[0], pack.z_dim), dtype=torch.float32, device=src.device) for _ in range(2))
     z = torch.empty_like(mu) if eps is not None else None
     encode_rows(pack, src, off, y, eps, mu, log_var, z)
     return LatentBatch(mu, log_var, z, counts, off)
 
 
-def reconstruct_batch(vae, spec_or_rows, labels=None, eps=None, counts=None, use="hard", decode_labels=None, precision="fp32"):
+def reconstruct_batch(vae, spec_or_rows, labels=None, eps=None, counts=None, use="hard", decode_labels=None, precision="fp32", encoder_pack=None):
     """Encode, then decode (scripts/reconstruct_ntcd_M2.py:231-358: `_, z, _ = model.encoder(x)`, `model.decoder(z | y)` under the
     oracle label, all ones, all zeros) -> (variance [513, N], LatentBatch).  vae: a packages.models VAE (encoder / decoder); the
     encoder takes the labels exactly when its first layer is wider than 513, the decoder when its is wider than 16.  Decodes z, or
     mu when eps is None, with DecoderPack.decode (R = 1) under decode_labels (rows [N, y_dim], a LabelBatch or a FrameBatch;
-    default: `labels`).  Utterance u is variance[:, frame_off[u] : frame_off[u + 1]], (513, T_u) as the scripts plot it."""
+    default: `labels`).  Utterance u is variance[:, frame_off[u] : frame_off[u + 1]], (513, T_u) as the scripts plot it.
+    encoder_pack: an EncoderPack of vae.encoder (either kind, e.g. from pack_encoder): the encoding runs on it and the decoder's input
+    is split at its z_dim, so a model of any covered size is reconstructed (DecoderPack picks the generic chain's decode)."""
     from .mcem import DecoderPack
     op = "reconstruct_batch"
     enc_y = vae.encoder.hidden[0].in_features - F_BINS
-    dec_y = vae.decoder.hidden[0].in_features - Z_DIM
-    lat = encode_batch(vae.encoder, spec_or_rows, labels if enc_y > 0 else None, counts, eps, use, y_dim=enc_y)
+    if encoder_pack is not None:
+        if encoder_pack.y_dim != enc_y:
+            raise ValueError(f"{op}: the encoder pack takes {encoder_pack.y_dim} label columns, vae.encoder {enc_y}")
+        dec_y = vae.decoder.hidden[0].in_features - encoder_pack.z_dim
+        if dec_y < 0:
+            raise ValueError(f"{op}: the encoder pack's z_dim {encoder_pack.z_dim} exceeds the decoder's input width")
+        lat = encode_batch(encoder_pack, spec_or_rows, labels if enc_y > 0 else None, counts, eps, use)
+    else:
+        dec_y = vae.decoder.hidden[0].in_features - Z_DIM
+        lat = encode_batch(vae.encoder, spec_or_rows, labels if enc_y > 0 else None, counts, eps, use, y_dim=enc_y)
     dl = labels if decode_labels is None else decode_labels
     if (dec_y > 0) != (dl is not None):
         raise ValueError(f"{op}: the decoder takes {dec_y} label columns: labels are needed exactly then")

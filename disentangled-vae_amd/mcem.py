@@ -217,7 +217,7 @@ class McemBatch:
         i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
         return starts, pos, i32(starts), i32(counts), i32(tile_seg)
 
-    def init_parameters(self, X_list, y_list=None, device="cuda", use="hard", fused_start=False):
+    def init_parameters(self, X_list, y_list=None, device="cuda", use="hard", fused_start=False, encoder_pack=None):
         """X_list: complex mixture STFTs (F, N_u) (numpy), or a SpecBatch of complex frames (stft.stft_batch) that stays on the
         device: |X|^2 is then formed there (dvae_mcem_spec_init, the same bits) and run() keeps the Wiener gains there for enhance().
         y_list: labels (y_dim, N_u) tensors/arrays, a LabelBatch (classify.classify_batch) whose `use` labels ("hard" as the
@@ -227,7 +227,10 @@ class McemBatch:
         encoder input), W and H from ONE torch.rand each for all utterances (a DIFFERENT draw order from the loop below, which draws
         W[u], H[u] utterance by utterance: the same seed gives other factors) and one dvae_mcem_nmf_start launch for the clamps and
         Vb = W H (one ascending-k fma chain per element, not rocBLAS's order).  X2 and y are the default path's bits; Z is
-        encode_batch's mu, within rounding of the default path's.  The default stays the loop: its draws are what seeds rest on."""
+        encode_batch's mu, within rounding of the default path's.  The default stays the loop: its draws are what seeds rest on.
+        encoder_pack (with fused_start): an encode.EncoderPack of vae.encoder of either kind (encode.pack_encoder picks it): Z is
+        [pack.z_dim, ntot] from that one launch, so an encoder of any covered size starts on the device, and the pack is not made
+        again per call.  ValueError for a pack whose y_dim or z_dim does not fit the model and label_in_encoder."""
         from .classify import LabelBatch
         labels = y_list if isinstance(y_list, LabelBatch) else None
         spec = X_list if isinstance(X_list, STFT.SpecBatch) else None
@@ -248,6 +251,8 @@ class McemBatch:
         self._bufs = None                    # the M-step workspace depends on the utterance count, not only on the padded frame total
         if fused_start and spec is None:
             raise TypeError("McemBatch.init_parameters: fused_start needs a SpecBatch of complex frames (stft.stft_batch)")
+        if encoder_pack is not None and not fused_start:
+            raise ValueError("McemBatch.init_parameters: encoder_pack is the encoder of the fused start (fused_start=True)")
         if labels is not None and list(labels.counts) != counts:
             bad = next((u for u, (a, b) in enumerate(zip(labels.counts, counts)) if a != b), min(len(labels.counts), len(counts)))
             raise ValueError(f"McemBatch.init_parameters: utterance {bad}: the LabelBatch's frame counts differ from the spectrograms' "
@@ -262,7 +267,7 @@ class McemBatch:
             N.check(N.load().dvae_mcem_spec_init(N.ptr(spec.frames), int(spec.frame_off[-1]), U, N.ptr(tab_dev), N.ptr(self.X2), self.ntot, N.stream()),
                     "dvae_mcem_spec_init")
         if fused_start:
-            return self._fused_start(spec, labels, y_list, use, tab, tab_dev, dev)
+            return self._fused_start(spec, labels, y_list, use, tab, tab_dev, dev, encoder_pack)
         self.H = torch.ones((K, self.ntot), dtype=torch.float32, device=dev)
         self.Vb = torch.ones((F_BINS, self.ntot), dtype=torch.float32, device=dev)
         self.g = torch.ones(self.ntot, dtype=torch.float32, device=dev)
@@ -287,7 +292,7 @@ class McemBatch:
         y_dim = self.y.shape[0] if self.y is not None else 0
         self._pack = DecoderPack(self.vae.decoder, y_dim, self.precision)
 
-    def _fused_start(self, spec, labels, y_list, use, tab, tab_dev, dev):
+    def _fused_start(self, spec, labels, y_list, use, tab, tab_dev, dev, encoder_pack=None):
         """The rest of init_parameters(fused_start=True) once X2 stands: labels, Z, W, H, Vb, g in a fixed number of launches."""
         from . import encode as E
         U, K, n = len(self.counts), self.K, int(spec.frame_off[-1])
@@ -309,12 +314,22 @@ class McemBatch:
             self.y = torch.zeros((yrows.shape[1], self.ntot), dtype=torch.float32, device=dev)
             self.y.index_copy_(1, colidx, yrows.T)
         enc_y = self.y.shape[0] if self.label_in_encoder else 0
-        if not E.encoder_supported(self.vae.encoder, enc_y):
-            raise ValueError("McemBatch.init_parameters: fused_start needs an encoder that encode.EncoderPack covers ([513+y]-128-128-16, y_dim 0, 1 "
-                             "or 513); the default start (fused_start=False) runs vae.encoder at any size")
-        self.Z = torch.zeros((Z_DIM, self.ntot), dtype=torch.float32, device=dev)
-        E.encode_rows(E.EncoderPack(self.vae.encoder, enc_y), spec.frames, spec.frame_off, y=yrows if enc_y else None, Z=self.Z, cols=self.starts,
-                      tables_dev=tab_dev)
+        if encoder_pack is not None:
+            if encoder_pack.y_dim != enc_y:
+                raise ValueError(f"McemBatch.init_parameters: the encoder pack's y_dim {encoder_pack.y_dim} does not fit: the encoder is fed {enc_y} "
+                                 f"label rows (label_in_encoder={self.label_in_encoder})")
+            dec_z = self.vae.decoder.hidden[0].in_features - (self.y.shape[0] if self.label_in_decoder else 0)
+            if encoder_pack.z_dim != dec_z:
+                raise ValueError(f"McemBatch.init_parameters: the encoder pack's z_dim {encoder_pack.z_dim} does not fit: the decoder takes {dec_z} latents")
+            pack, z_dim = encoder_pack, encoder_pack.z_dim
+        else:
+            if not E.encoder_supported(self.vae.encoder, enc_y):
+                raise ValueError("McemBatch.init_parameters: fused_start needs an encoder that encode.EncoderPack covers ([513+y]-128-128-16, y_dim 0, 1 "
+                                 "or 513); the default start (fused_start=False) runs vae.encoder at any size, and encoder_pack="
+                                 "encode.pack_encoder(vae.encoder, y_dim) starts any covered size on the device")
+            pack, z_dim = E.EncoderPack(self.vae.encoder, enc_y), Z_DIM
+        self.Z = torch.zeros((z_dim, self.ntot), dtype=torch.float32, device=dev)
+        E.encode_rows(pack, spec.frames, spec.frame_off, y=yrows if enc_y else None, Z=self.Z, cols=self.starts, tables_dev=tab_dev)
         self.W = torch.rand((U, F_BINS, K), dtype=torch.float32, device=dev)                        # mcem.py:42, all utterances in one draw
         self.H = torch.rand((K, self.ntot), dtype=torch.float32, device=dev)                        # mcem.py:43
         self.Vb = torch.empty((F_BINS, self.ntot), dtype=torch.float32, device=dev)

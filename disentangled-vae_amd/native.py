@@ -83,6 +83,13 @@ SIGNATURES = {
     "dvae_label_counts_batch": (c_i, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i, c_i, c_vp, c_vp, c_vp, c_vp]),
     "dvae_encode_weights_floats": (c_sz, [c_i]),
     "dvae_encode_batch": (c_i, [c_vp, c_i, c_i64, c_vp, c_i64, c_i64, c_i, c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "dvae_encode_generic_weights_floats": (c_sz, [c_i, c_i, c_i, c_i]),
+    "dvae_classify_generic_weights_floats": (c_sz, [c_i, c_i, c_i]),
+    "dvae_encode_generic_pack": (c_i, [c_i, c_i, c_i, c_i, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "dvae_classify_generic_pack": (c_i, [c_i, c_i, c_i, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "dvae_encode_generic_batch": (c_i, [c_vp, c_i, c_i64, c_vp, c_i64, c_i64, c_i, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                        c_vp, c_vp, c_vp]),
+    "dvae_classify_generic_batch": (c_i, [c_vp, c_i, c_i64, c_i64, c_i, c_vp, c_vp, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp]),
     # include/dvae_train.h (plan pointers are passed with ctypes.byref)
     "dvae_train_plan": (c_i, [c_i, c_i, c_i, c_i64, c_i, c_vp]),
     "dvae_train_init": (c_i, [c_vp, c_vp, c_vp, c_vp]),

@@ -11,6 +11,10 @@ device between the batch STFT and the waveforms.
 
     python examples/enhance_mcem.py --synthetic 8 --labels classifier --score   # the M2_info flow: labels from the model's own classifier
 
+    python examples/enhance_mcem.py --synthetic 3 --z-dim 32 --h-dim 256 64 --fused-start --labels classifier --score
+                                                                        # a model of another size: the generic kernels for classifier,
+                                                                        # encoder and chain (pack_classifier / pack_encoder pick them)
+
 --labels vad (the default): the labels y fed to the M2 decoder are the time-domain VAD of the mixture
 (packages/processing/target.py); the reference's evaluate_ntcd_M2.py takes them from a video classifier or from the clean signal
 (oracle), neither of which ships with it.  --labels classifier: the flow of scripts/evaluate_ntcd_M2_info_vad.py:175-219 -- a
@@ -38,6 +42,7 @@ si_sdr_batch = importlib.import_module("disentangled-vae_amd.metrics").si_sdr_ba
 estoi_batch = importlib.import_module("disentangled-vae_amd.metrics").estoi_batch
 mix_at_snr_batch = importlib.import_module("disentangled-vae_amd.mix").mix_at_snr_batch
 classify = importlib.import_module("disentangled-vae_amd.classify")
+encode = importlib.import_module("disentangled-vae_amd.encode")
 utterances_to_frames = importlib.import_module("disentangled-vae_amd.target").utterances_to_frames
 STFT = dict(fs=16000, wlen_sec=64e-3, win="hann", hop_percent=0.25, center=False)      # evaluate_ntcd_M2.py:37-45
 
@@ -81,7 +86,7 @@ def main():
     ap.add_argument("--snr", type=float, nargs="+", default=None, help="with --synthetic: mix every utterance with synthetic noise at each of "
                     "these SNRs (dB) on the device instead of adding a fixed 0.2 * randn on the host")
     ap.add_argument("--z-dim", type=int, default=16, help="latent size of the random-weight model (any 1..128: sizes other than the "
-                    "reference's 16 / 128 / 128 run the generic fp32 chain, mcem.chain_kind)")
+                    "reference's 16 / 128 / 128 run the generic fp32 kernels -- chain, encoder of --fused-start, classifier of --labels classifier)")
     ap.add_argument("--h-dim", type=int, nargs=2, default=[128, 128], metavar=("H1", "H2"), help="hidden widths of the random-weight model (1..512 each)")
     ap.add_argument("--trim", type=int, default=800, help="samples cut at both ends before scoring (run_metrics.py:117-121: 0.05 s)")
     a = ap.parse_args()
@@ -89,9 +94,9 @@ def main():
         ap.error("--score needs the clean speech, which only --synthetic mixtures come with")
     if a.snr is not None and (a.wav or not a.synthetic):
         ap.error("--snr mixes the --synthetic utterances")
-    if (a.z_dim, list(a.h_dim)) != (16, [128, 128]) and (a.checkpoint or a.fused_start or a.labels == "classifier" or a.precision != "fp32"):
-        ap.error("--z-dim / --h-dim size the random-weight model of the default flow: fp32, VAD labels, no --checkpoint, no --fused-start "
-                 "(the encoder and classifier kernels cover 513-128-128-16 only)")
+    if (a.z_dim, list(a.h_dim)) != (16, [128, 128]) and (a.checkpoint or a.precision != "fp32"):
+        ap.error("--z-dim / --h-dim size the random-weight model: fp32 and no --checkpoint (other sizes run the generic fp32 kernels: "
+                 "mcem.chain_kind, encode.encoder_kind, classify.classifier_kind)")
     names, waves, clean = [], [], []
     for p in a.wav:
         fs, w = wavfile.read(p)
@@ -133,7 +138,8 @@ def main():
     if a.labels == "classifier":
         # y_hat_soft = model.classifier(|X|^2), y_hat_hard = y_hat_soft > 0.5 for every frame of the batch in one launch; the LabelBatch
         # stays on the device and MCEM_M2v3 (labels in the decoder only) takes its hard labels from there
-        Y = classify.classify_batch(vae.enc_dec_clf.classifier, X)
+        # (pack_classifier: the resident kernel at 513-128-128, the generic one at every other covered size)
+        Y = classify.classify_batch(classify.pack_classifier(vae.enc_dec_clf.classifier), X)
         mb = McemBatch(vae.enc_dec_clf, niter=a.niter, nsamples_E_step=10, burnin_E_step=30, nsamples_WF=25, burnin_WF=75, var_RW=0.01,
                        nmf_rank=10, precision=a.precision, label_in_encoder=False, label_in_decoder=True)
     else:
@@ -141,7 +147,9 @@ def main():
                               vad_threshold=1.70) for w in waves]                                              # (1, N_u)
         mb = McemBatch(vae, niter=a.niter, nsamples_E_step=10, burnin_E_step=30, nsamples_WF=25, burnin_WF=75, var_RW=0.01,
                        nmf_rank=10, precision=a.precision)                                                      # evaluate_ntcd_M2.py:92-99
-    mb.init_parameters(X, Y, fused_start=a.fused_start)
+    # the fused start's encoder by its kind too: labels reach the encoder of M2 (y_dim 1), not that of M2_info's M2v3 variant
+    enc_pack = encode.pack_encoder(mb.vae.encoder, 1 if mb.label_in_encoder else 0) if a.fused_start else None
+    mb.init_parameters(X, Y, fused_start=a.fused_start, encoder_pack=enc_pack)
     cost = mb.run()
     # Wiener filtering and ISTFT of both estimates in one launch: istft(S_hat, max_len=len(w)) / istft(N_hat, ...) per utterance
     s_hat, n_hat = mb.enhance(max_len=[len(w) for w in waves])

@@ -465,6 +465,49 @@ int dvae_encode_batch(const void* src, int src_complex, int64_t ld, const float*
                       const int64_t* frame_off_host, const float* weights, int y_dim, const float* eps, float* mu, float* log_var,
                       float* z, float* Z, int64_t ntot, const int64_t* col_host, const int64_t* tables_dev, void* stream);
 
+/* ---- the encoder and the classifier at any covered size (csrc/mlp_generic.hip) ----
+ * The two networks above for every geometry within the limits of dvae_mcem_plan_dims, exact float32 on v_mfma_f32_16x16x4_f32, one
+ * launch each on `stream`, no host synchronisation, no atomics.  The entry points above stay as they are and stay the default for
+ * 513-128-128; these serve the other sizes (and that one too, on request).
+ *   encoder:    [x | y] (513 + y_dim) -> h1 (tanh) -> h2 (tanh) -> {mu z_dim, log_var z_dim}; y_dim 0..513, h1 / h2 1..512, z_dim 1..128
+ *   classifier: x (513) -> h1 (relu) -> h2 (relu) -> y_dim logits (sigmoid); y_dim 1..513, h1 / h2 1..512, no batch norm
+ * Dims outside the limits: the size queries return 0, every other call DVAE_E_BADARG with the limits named, nothing launched.
+ * dvae_encode_generic_weights_floats / dvae_classify_generic_weights_floats: floats of the packed copy.
+ * dvae_encode_generic_pack / dvae_classify_generic_pack: write the packed copy on `stream` from the state_dict tensors (device,
+ *   float32, [out][in] with leading dimensions ld* >= their row length; biases packed).  Layout, with up16(v) the next multiple of 16:
+ *   W1x [up16(h1)][528] | W1y [up16(h1)][up16(y_dim)] (encoder with labels only) | W2 [up16(h2)][up16(h1)] | W3 [rows][up16(h2)] |
+ *   b1 [up16(h1)] | b2 [up16(h2)] | b3 [rows]; W3 / b3 are the heads, mu in rows 0 .. z_dim - 1 and log_var in rows up16(z_dim) ..
+ *   up16(z_dim) + z_dim - 1 of 2 up16(z_dim) rows, or the output layer in up16(y_dim) rows.  Every matrix is stored in fragment
+ *   order [row tile of 16][k block of 16][lane 0..63][4]: lane l holds row l & 15, inputs 16 b + 4 i + (l >> 4), i = 0..3.  Padding
+ *   rows, inputs and biases are zero: a padded hidden unit is tanh 0 = relu 0 = 0 and has zero out-weights, a padded output row is
+ *   computed and dropped.  The x block (columns 0..512 of W1) and the label block (columns 513..) are padded separately.
+ * dvae_encode_generic_batch: dvae_encode_batch's arguments and contract with the dims after y_dim: inputs, tables, outputs, the
+ *   table checks before anything is launched, z = mu + expf(0.5f log_var) eps with product and sum rounded separately, tanhf.  mu,
+ *   log_var, z, eps are [N][z_dim], Z is [z_dim][ntot].
+ * dvae_classify_generic_batch: dvae_classify_batch's arguments and contract with the dims after y_dim: soft = 1 / (1 + expf(-logit)),
+ *   hard = soft > 0.5 ? 1 : 0 decided from the float32 soft that is stored; soft, hard, logits (or NULL) [N][y_dim].
+ *   Summation: every pre-activation is ONE float32 chain from 0 with k ascending, four products per step as v_mfma_f32_16x16x4_f32
+ *   adds them, over the 528 padded x inputs first, then the up16(y_dim) padded label inputs (as torch.cat([x, y], 1) lays them), the
+ *   bias added after it.  A workgroup owns 16 frames; the order does not depend on the frame's place in its tile, on the tile's place
+ *   in the grid or on the batch, so a frame gives the same bits alone, in any batch and from run to run (the bits of the entry
+ *   points above, which add two products per step, are not promised; on the committed fixtures they came out equal).
+ *   Never touched: rows outside [frame_off[0], frame_off[U]) or past N are neither read nor written; label rows are read in place at
+ *   ldy; columns of Z outside the utterances' stay as they are, and a frame whose column by the device table falls outside
+ *   [0, ntot) is not written. */
+size_t dvae_encode_generic_weights_floats(int y_dim, int h1, int h2, int z_dim);
+size_t dvae_classify_generic_weights_floats(int h1, int h2, int y_dim);
+int dvae_encode_generic_pack(int y_dim, int h1, int h2, int z_dim, const float* W1, int64_t ld1, const float* b1, const float* W2,
+                             int64_t ld2, const float* b2, const float* Wmu, int64_t ldmu, const float* bmu, const float* Wlv, int64_t ldlv,
+                             const float* blv, float* weights, void* stream);
+int dvae_classify_generic_pack(int h1, int h2, int y_dim, const float* W1, int64_t ld1, const float* b1, const float* W2, int64_t ld2,
+                               const float* b2, const float* W3, int64_t ld3, const float* b3, float* weights, void* stream);
+int dvae_encode_generic_batch(const void* src, int src_complex, int64_t ld, const float* y, int64_t ldy, int64_t N, int U,
+                              const int64_t* frame_off_host, const float* weights, int y_dim, int h1, int h2, int z_dim, const float* eps,
+                              float* mu, float* log_var, float* z, float* Z, int64_t ntot, const int64_t* col_host,
+                              const int64_t* tables_dev, void* stream);
+int dvae_classify_generic_batch(const void* src, int src_complex, int64_t ld, int64_t N, int U, const int64_t* frame_off_host,
+                                const float* weights, int y_dim, int h1, int h2, float* soft, float* hard, float* logits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
