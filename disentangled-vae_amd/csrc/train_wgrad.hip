@@ -321,6 +321,28 @@ __device__ __forceinline__ void wgrad4_body(const Block4& bd, const Block4* __re
     for (int k = 0; k < NB; ++k) bp[k] = (gptr)(uintptr_t)(bd.Bt[k] ? bd.Bt[k] : bd.Bt[0]);
     const int64_t plb = spl * (int64_t)sizeof(T);                          // bytes between the hi and lo planes
     const unsigned loff = (unsigned)lane * 16u;
+    // Stash-fed bodies (RAW == 0): the operand stream as buffer loads, the form of the rows kernel's weight stream (wstream.hpp) -- one
+    // resource per operand matrix and plane in SGPRs, ONE per-lane offset (lane * 16) shared by every fragment, tile + k-step as the scalar
+    // offset: no 64-bit VGPR address per fragment.  An operand matrix = the block's present tiles, contiguous stash rows (fill_tables lays a
+    // block's tiles out in ascending rows, tile 0 first): the resource starts at tile 0 and its record count ends with the highest tile, so every
+    // request -- the clamped reloads of the last k-step included -- is inside it by construction; nothing relies on the range check.
+    constexpr bool BUF = RAW == 0;
+    const unsigned tileb = (unsigned)(32 * Bp * (int64_t)sizeof(T));       // bytes of one tile's rows (launch_wgrad4 bounds Bp)
+    __amdgpu_buffer_rsrc_t ars[NP], brs[NP];
+    unsigned aoff[NA], boff[NB];
+    if constexpr (BUF) {
+        const gptr a0 = (gptr)(uintptr_t)bd.At[0], b0 = (gptr)(uintptr_t)bd.Bt[0];      // tile 0: the lowest rows
+        unsigned am = 0, bm = 0;
+#pragma unroll
+        for (int k = 0; k < NA; ++k) { aoff[k] = (unsigned)(ap[k] - a0); am = aoff[k] > am ? aoff[k] : am; }
+#pragma unroll
+        for (int k = 0; k < NB; ++k) { boff[k] = (unsigned)(bp[k] - b0); bm = boff[k] > bm ? boff[k] : bm; }
+#pragma unroll
+        for (int pl = 0; pl < NP; ++pl) {
+            ars[pl] = __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)(a0 + pl * plb), 0, __builtin_amdgcn_readfirstlane((int)(am + tileb)), 0x00020000);   // (hipcc takes the maximum with a vector instruction)
+            brs[pl] = __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)(b0 + pl * plb), 0, __builtin_amdgcn_readfirstlane((int)(bm + tileb)), 0x00020000);
+        }
+    }
     f32x16 c[NA][NB];
 #pragma unroll
     for (int i = 0; i < NA; ++i)
@@ -348,10 +370,16 @@ __device__ __forceinline__ void wgrad4_body(const Block4& bd, const Block4* __re
     auto load = [&](auto sc, int64_t sk) __attribute__((always_inline)) {
         constexpr int s = decltype(sc)::value;
         const int64_t o = sk * FBB;
+        const unsigned so = (unsigned)o;                                     // BUF: the k-step as the loads' scalar offset
 #pragma unroll
         for (int k = 0; k < NA; ++k) {
-            a[s][k][0] = *(gfrag)(ap[k] + o + loff);
-            if constexpr (NP == 2) a[s][k][1] = *(gfrag)(ap[k] + plb + o + loff);
+            if constexpr (BUF) {
+#pragma unroll
+                for (int pl = 0; pl < NP; ++pl) a[s][k][pl] = __builtin_bit_cast(Frag, __builtin_amdgcn_raw_buffer_load_b128(ars[pl], (int)loff, (int)(aoff[k] + so), 0));
+            } else {
+                a[s][k][0] = *(gfrag)(ap[k] + o + loff);
+                if constexpr (NP == 2) a[s][k][1] = *(gfrag)(ap[k] + plb + o + loff);
+            }
         }
         if constexpr (RAW == 1) {
             const int64_t f0 = sk * KS + h * E;
@@ -371,8 +399,8 @@ __device__ __forceinline__ void wgrad4_body(const Block4& bd, const Block4* __re
         } else {
 #pragma unroll
             for (int k = 0; k < NB; ++k) {
-                b[s][k][0] = *(gfrag)(bp[k] + o + loff);
-                if constexpr (NP == 2 && BLO) b[s][k][1] = *(gfrag)(bp[k] + plb + o + loff);
+                b[s][k][0] = __builtin_bit_cast(Frag, __builtin_amdgcn_raw_buffer_load_b128(brs[0], (int)loff, (int)(boff[k] + so), 0));
+                if constexpr (NP == 2 && BLO) b[s][k][1] = __builtin_bit_cast(Frag, __builtin_amdgcn_raw_buffer_load_b128(brs[NP - 1], (int)loff, (int)(boff[k] + so), 0));
             }
         }
     };
@@ -471,7 +499,8 @@ __device__ __forceinline__ void wgrad4_body(const Block4& bd, const Block4* __re
     // No branch around the loop (an empty range runs zero laps; its clamped prologue loads re-read the slice's last k-step): a
     // conditional region here makes every accumulator a phi of (zero, loop result) and costs a 256-register copy.
     {
-        const int64_t slast = (send > s0 ? send : s0 + 1) - 1;
+        int64_t slast = (send > s0 ? send : s0 + 1) - 1;
+        if (slast > Bp / KS - 1) slast = Bp / KS - 1;                     // a slice that starts at the batch's end: still a k-step of the matrix
         static_for_w<0, RD>([&](auto sc) {
             int64_t sk = sbeg + decltype(sc)::value; sk = sk < slast ? sk : slast;
             load(sc, sk);
@@ -902,6 +931,8 @@ int launch_wgrad_lds(int precision, const BlockDesc* blocks, int nblocks, const 
 
 int launch_wgrad4(int precision, const Wgrad4Args& a, int grid, hipStream_t s) {
     const int dev = current_device();
+    // the operand stream addresses a block's four tiles (32 rows x Bp frames each) with 32-bit byte offsets into one buffer resource
+    if (a.Bp > ((int64_t)1 << 22)) { set_error("train_grads: more than 4194304 frames per step"); return DVAE_E_UNSUPPORTED; }
     const int rc = with_policy(precision, [&](auto pol) -> int {
         using P = decltype(pol);
         static bool attr_done[64] = {};      // per device: the attribute belongs to the device's copy of the code object
