@@ -1,0 +1,790 @@
+// The fused train step for M1 / M2 models of ANY covered size, exact fp32, three launches per step (include/dvae_train.h:
+// dvae_train_generic_*; disentangled-vae_amd/trainer_generic.py).  The resident step (train_rows*.hip, train_wgrad.hip, train_fused.hip)
+// is written for 513-128-128-16 and stays the default there; this file serves every other size within the limits of
+// dvae_mcem_plan_dims -- x 513, y_dim 0..513, h1 / h2 1..512, z 1..128 -- and the reference geometry too when asked.
+//
+// The design is mlp_generic.hip's, carried through the backward pass:
+//   * rows kernel: 256 threads own a tile of 16 frames.  Products run on v_mfma_f32_16x16x4_f32: 16 weight rows are the A operand, the
+//     tile's 16 frames the B columns; the four waves split a layer's row tiles.  Weights stream from packed copies in fragment order,
+//     zero-padded to multiples of 16 (runtime trip counts, no tails); the x / z block and the label block are padded separately and
+//     summed x (z) first, then y.  The backward-data products read a second, transposed packed copy.  Activations sit in LDS as
+//     [k][16]: the x tile (its place later takes d loss / d a), the label tile, two hidden tiles of max(h1, h2, z) rows and three
+//     latent tiles (mu / B, the KL part of d log_var, eps std / 2 -- then d mu, d log_var): 154 KB at 512 / 512 / z 128 / y 513, sized
+//     from the dims at launch.  The hidden activations of the encoder are NOT kept for the backward pass: every layer input and every
+//     pre-activation gradient goes to the stash ([frame][S] floats, 16-byte stores straight from the accumulators) for the weight
+//     gradients anyway, and the thread that wrote h reads it back where tanh' needs it.
+//     Frames past B carry zero pre-activation gradients and finite activations; padded units carry zeros throughout.
+//   * weight-gradient kernel: one launch for the seven matrices and their biases, dW = dPre^T in over the frames on the same MFMA
+//     (k = frames), driven by a host-built table of (matrix, 64-row output group, four 64-column blocks, frame slice) items; a wave
+//     keeps a 64 x 64 block of dW in sixteen accumulators.  x and y are read from the caller's memory (through the gather table when
+//     there is one); the bias is the product with a column of ones.  Every item writes its blocks of its slice's slab: no atomics,
+//     and the same inputs give the same bits.
+//   * apply kernel: one thread per parameter: slab sum in slab order, adam_element (apply_common.hpp), both packed copies refreshed,
+//     loss scalars finalised from the rows kernel's per-workgroup sums (and added to the optional float64 accumulator).
+//   * 64-bit indexing throughout; a gather index outside [0, row_count) is never dereferenced (row 0 instead, counted).
+#include <math.h>
+#include <vector>
+#include "common.hpp"
+#include "../../include/dvae_train.h"
+#include "apply_common.hpp"
+#include "train_generic.hpp"
+
+namespace dvae {
+namespace tg {
+
+using fused::ApplyArgs;
+
+static inline int up16(int v) { return (v + 15) / 16 * 16; }
+static inline int64_t al64(int64_t v) { return (v + 63) / 64 * 64; }        // floats: 256 bytes
+static inline int64_t al256(int64_t v) { return (v + 255) / 256 * 256; }
+
+static bool dims_ok(int y, int z, int h1, int h2) {
+    return y >= 0 && y <= GX && h1 >= 1 && h1 <= G_HMAX && h2 >= 1 && h2 <= G_HMAX && z >= 1 && z <= G_ZMAX;
+}
+
+static void make_gemms(const GLayout& L, GGemm* G);
+// items of one matrix and one frame slice: 64-row groups x groups of four 64-column blocks (input, labels, one block for the bias)
+static int gemm_col_groups(const GGemm& m) { return ((m.in_w + 63) / 64 + (m.y_w + 63) / 64 + 1 + 3) / 4; }
+static int gemm_items(const GGemm& m) { return (m.nrt + 3) / 4 * gemm_col_groups(m); }
+
+static GLayout make_layout(int y, int z, int h1, int h2, int64_t B, int ksplit_hint) {
+    GLayout L;
+    memset(&L, 0, sizeof(L));
+    L.y = y; L.z = z; L.h1 = h1; L.h2 = h2;
+    L.yp = y ? up16(y) : 0; L.zp = up16(z); L.h1p = up16(h1); L.h2p = up16(h2);
+    L.hm = L.h1p > L.h2p ? L.h1p : L.h2p;
+    if (L.zp > L.hm) L.hm = L.zp;
+    // parameters: state_dict order, 256-byte aligned
+    const int rows[G_NT] = {h1, h1, h2, h2, z, z, z, z, h2, h2, h1, h1, GX, GX};
+    const int cols[G_NT] = {GX + y, 1, h1, 1, h2, 1, h2, 1, z + y, 1, h2, 1, h1, 1};
+    int64_t o = 0;
+    for (int t = 0; t < G_NT; ++t) {
+        L.toff[t] = o; L.trows[t] = rows[t]; L.tcols[t] = cols[t];
+        o = al64(o + (int64_t)rows[t] * cols[t]);
+    }
+    L.n_params = o;
+    // packed copies
+    o = 0;
+    auto take = [&](int64_t n) { const int64_t at = o; o = al64(o + n); return at; };
+    L.W1x = take((int64_t)L.h1p * GXP); L.W1y = take((int64_t)L.h1p * L.yp);
+    L.W2 = take((int64_t)L.h2p * L.h1p); L.Wh = take((int64_t)2 * L.zp * L.h2p);
+    L.D1z = take((int64_t)L.h2p * L.zp); L.D1y = take((int64_t)L.h2p * L.yp);
+    L.D2 = take((int64_t)L.h1p * L.h2p); L.D3 = take((int64_t)GXP * L.h1p);
+    L.D3T = take((int64_t)L.h1p * GXP); L.D2T = take((int64_t)L.h2p * L.h1p); L.D1zT = take((int64_t)L.zp * L.h2p);
+    L.WhT = take((int64_t)L.h2p * 2 * L.zp); L.W2T = take((int64_t)L.h1p * L.h2p);
+    L.b1 = take(L.h1p); L.b2 = take(L.h2p); L.bh = take(2 * L.zp); L.bd1 = take(L.h2p); L.bd2 = take(L.h1p); L.bd3 = take(GXP);
+    L.wpack_elems = o;
+    // the stash of a frame
+    int s = 0;
+    auto col = [&](int n) { const int at = s; s += n; return at; };
+    L.s_h1e = col(L.h1p); L.s_h2e = col(L.h2p); L.s_z = col(L.zp); L.s_d1 = col(L.h2p); L.s_d2 = col(L.h1p);
+    L.s_pe1 = col(L.h1p); L.s_pe2 = col(L.h2p); L.s_ph = col(2 * L.zp); L.s_pd1 = col(L.h2p); L.s_pd2 = col(L.h1p); L.s_da = col(GXP);
+    L.S = s;
+    // frames, tiles, slices
+    L.B = B;
+    L.tiles = (B + GT - 1) / GT;
+    L.Bp = L.tiles * GT;
+    L.rows_grid = L.tiles < G_ROWS_GRID ? L.tiles : G_ROWS_GRID;
+    GGemm gm[G_NG];
+    make_gemms(L, gm);
+    int row_tiles = 0;                                    // weight-gradient items of one frame slice
+    for (int i = 0; i < G_NG; ++i) row_tiles += gemm_items(gm[i]);
+    int64_t ks = ksplit_hint;
+    if (ks <= 0) {                                        // about three workgroups a compute unit, at least 64 frames a slice
+        ks = (768 + row_tiles - 1) / row_tiles;
+        if (ks > B / 64) ks = B / 64;
+    }
+    if (ks > G_MAX_SLICES) ks = G_MAX_SLICES;
+    if (ks < 1) ks = 1;
+    L.slice_frames = ((B + ks - 1) / ks + 15) / 16 * 16;
+    L.nslices = (int)((B + L.slice_frames - 1) / L.slice_frames);
+    L.n_items = row_tiles * L.nslices;
+    // workspace
+    int64_t w = al256(L.wpack_elems * 4);
+    L.o_items = w; w = al256(w + (int64_t)L.n_items * sizeof(GItem));
+    L.o_partials = w; w = al256(w + L.rows_grid * 4 * sizeof(double));
+    L.o_stash = w; w = al256(w + L.Bp * (int64_t)L.S * 4);
+    L.o_grads = w; w = al256(w + (int64_t)L.nslices * L.n_params * 4);
+    L.ws_bytes = w;
+    L.lds_bytes = (int64_t)GT * (GXP + L.yp + 2 * L.hm + 3 * L.zp) * 4 + GT * sizeof(int64_t);
+    return L;
+}
+
+static void make_tensors(const GLayout& L, GTensor* T) {
+    for (int t = 0; t < G_NT; ++t) {
+        GTensor& d = T[t];
+        memset(&d, 0, sizeof(d));
+        d.off = L.toff[t]; d.rows = L.trows[t]; d.cols = L.tcols[t];
+        d.f0 = d.f1 = 0; d.t0 = -1; d.split = d.cols; d.bias = t & 1;
+    }
+    const int k1 = L.h1p / 16, k2 = L.h2p / 16, kz = L.zp / 16, ky = L.yp / 16;
+    T[0].f0 = L.W1x; T[0].kb0 = GKX; T[0].split = GX; T[0].f1 = L.W1y; T[0].kb1 = ky;
+    T[1].f0 = L.b1;
+    T[2].f0 = L.W2; T[2].kb0 = k1; T[2].t0 = L.W2T; T[2].tkb = k2; T[2].tcmax = L.h1;
+    T[3].f0 = L.b2;
+    T[4].f0 = L.Wh; T[4].kb0 = k2; T[4].t0 = L.WhT; T[4].tkb = 2 * kz; T[4].tcmax = L.h2;
+    T[5].f0 = L.bh;
+    T[6].f0 = L.Wh; T[6].kb0 = k2; T[6].roff = L.zp; T[6].t0 = L.WhT; T[6].tkb = 2 * kz; T[6].tkoff = L.zp; T[6].tcmax = L.h2;
+    T[7].f0 = L.bh; T[7].roff = L.zp;
+    T[8].f0 = L.D1z; T[8].kb0 = kz; T[8].split = L.z; T[8].f1 = L.D1y; T[8].kb1 = ky; T[8].t0 = L.D1zT; T[8].tkb = k2; T[8].tcmax = L.z;
+    T[9].f0 = L.bd1;
+    T[10].f0 = L.D2; T[10].kb0 = k2; T[10].t0 = L.D2T; T[10].tkb = k1; T[10].tcmax = L.h2;
+    T[11].f0 = L.bd2;
+    T[12].f0 = L.D3; T[12].kb0 = k1; T[12].t0 = L.D3T; T[12].tkb = GKX; T[12].tcmax = L.h1;
+    T[13].f0 = L.bd3;
+}
+
+static void make_gemms(const GLayout& L, GGemm* G) {
+    auto set = [&](int i, int dpre, int nrt, int rows, int wt, int kind, int in_off, int in_w, int y_w) {
+        GGemm& m = G[i];
+        memset(&m, 0, sizeof(m));
+        m.dpre = dpre; m.nrt = nrt; m.rows = rows; m.wt = wt; m.bt = wt + 1; m.in_kind = kind; m.in_off = in_off; m.in_w = in_w; m.y_w = y_w;
+        m.cols = in_w + y_w;
+    };
+    set(0, L.s_pe1, L.h1p / 16, L.h1, 0, 0, 0, GX, L.y);
+    set(1, L.s_pe2, L.h2p / 16, L.h2, 2, 1, L.s_h1e, L.h1, 0);
+    set(2, L.s_ph, L.zp / 16, L.z, 4, 1, L.s_h2e, L.h2, 0);
+    set(3, L.s_ph + L.zp, L.zp / 16, L.z, 6, 1, L.s_h2e, L.h2, 0);
+    set(4, L.s_pd1, L.h2p / 16, L.h2, 8, 1, L.s_z, L.z, L.y);
+    set(5, L.s_pd2, L.h1p / 16, L.h1, 10, 1, L.s_d1, L.h2, 0);
+    set(6, L.s_da, GKX, GX, 12, 1, L.s_d2, L.h1, 0);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// rows kernel
+struct GRowsArgs {
+    const float* x; int64_t ldx;
+    const float* y; int64_t ldy;
+    const float* eps;                 // [B][z]
+    const int64_t* row_index; int64_t row_count; int* bad;
+    float* ws;                        // the packed copies start the workspace
+    float* stash; double* partials;
+    float elbo_eps, invB;
+    int fwd_only;
+};
+
+// acc += W[row tile] (16 x 16 kb) * act (16 kb x 16 frames): W in fragment order, act in LDS as [k][16]
+__device__ __forceinline__ f32x4 tg_gemm(f32x4 acc, const float* __restrict__ wt, int kb, const float* act, int lane) {
+    // k ascending, four k blocks a round with the next round's fragments requested before this round's MFMAs: the loads are L2 hits of
+    // several hundred cycles and a workgroup may be alone on its CU
+    const f32x4* w = reinterpret_cast<const f32x4*>(wt) + lane;
+    auto step = [&](const f32x4& a, int b) __attribute__((always_inline)) {
+        const float* bp = act + b * 256 + lane;
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], bp[0], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], bp[64], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], bp[128], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], bp[192], acc, 0, 0, 0);
+    };
+    const int kb4 = kb & ~3;
+    if (kb4) {
+        f32x4 c0 = w[0], c1 = w[64], c2 = w[128], c3 = w[192];
+        for (int b = 0; b < kb4; b += 4) {
+            f32x4 n0 = c0, n1 = c1, n2 = c2, n3 = c3;
+            if (b + 4 < kb4) {
+                const f32x4* wn = w + (int64_t)(b + 4) * 64;
+                n0 = wn[0]; n1 = wn[64]; n2 = wn[128]; n3 = wn[192];
+            }
+            step(c0, b); step(c1, b + 1); step(c2, b + 2); step(c3, b + 3);
+            c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        }
+    }
+    for (int b = kb4; b < kb; ++b) step(w[(int64_t)b * 64], b);
+    return acc;
+}
+
+__global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L, const GRowsArgs g) {
+    extern __shared__ __attribute__((aligned(16))) float gsm[];
+    float* X = gsm;                                     // [528][16] x, then d loss / d a
+    float* Y = X + GT * GXP;                            // [yp][16]
+    float* A = Y + GT * L.yp;                           // [hm][16] h1e, d1, dpre_d1
+    float* Bf = A + GT * L.hm;                          // [hm][16] h2e, z, d2, dpre_d2, dpre_e2
+    float* C = Bf + GT * L.hm;                          // [3 zp][16] heads; then mu / B | KL part of d log_var | eps std / 2; then d mu | d log_var
+    int64_t* srow = reinterpret_cast<int64_t*>(C + GT * 3 * L.zp);     // [16] the frame's row of x / y, -1: past B
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int col = lane & 15, quad = lane >> 4;
+    const int ky = L.yp >> 4, k1 = L.h1p >> 4, k2 = L.h2p >> 4, kz = L.zp >> 4;
+    const float* wp = g.ws;
+    const bool bwd = !g.fwd_only;
+    double sum_is = 0.0, sum_kl = 0.0;
+
+    for (int64_t tile = blockIdx.x; tile < L.tiles; tile += gridDim.x) {
+        const int64_t r0 = tile * GT;
+        __syncthreads();                                // the previous tile's readers of srow, X and C are done
+        if (tid < GT) {
+            const int64_t r = r0 + tid;
+            int64_t s = -1;
+            if (r < L.B) {
+                s = r;
+                if (g.row_index) {
+                    s = g.row_index[r];
+                    if (s < 0 || s >= g.row_count) {
+                        s = 0;
+                        if (g.bad) atomicAdd(g.bad, 1);
+                    }
+                }
+            }
+            srow[tid] = s;
+        }
+        __syncthreads();
+        const bool fok = srow[col] >= 0;                // this lane's frame of the accumulator tiles
+        float* const sfr = g.stash + (r0 + col) * (int64_t)L.S + 4 * quad;
+        auto st4 = [&](int off, int t, const f32x4& v) { if (bwd) *reinterpret_cast<f32x4*>(sfr + off + 16 * t) = v; };
+        auto ld4 = [&](int off, int t) { return *reinterpret_cast<const f32x4*>(sfr + off + 16 * t); };
+
+        // ---- the input tile: a quarter wave reads 16 consecutive inputs of one frame ----
+        for (int b = wave; b < GKX; b += 4) {
+#pragma unroll
+            for (int cq = 0; cq < 4; ++cq) {
+                const int k = 16 * b + col, c = 4 * cq + quad;
+                const int64_t s = srow[c];
+                X[k * GT + c] = (k < GX && s >= 0) ? g.x[s * g.ldx + k] : 0.f;
+            }
+        }
+        for (int b = wave; b < ky; b += 4) {
+#pragma unroll
+            for (int cq = 0; cq < 4; ++cq) {
+                const int k = 16 * b + col, c = 4 * cq + quad;
+                const int64_t s = srow[c];
+                Y[k * GT + c] = (k < L.y && s >= 0) ? g.y[s * g.ldy + k] : 0.f;
+            }
+        }
+        __syncthreads();
+
+        // ---- encoder layer 1: h1e = tanh([x | y] W1^T + b1) -> A ----
+        for (int t = wave; t < k1; t += 4) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            acc = tg_gemm(acc, wp + L.W1x + (int64_t)t * GKX * 256, GKX, X, lane);
+            acc = tg_gemm(acc, wp + L.W1y + (int64_t)t * ky * 256, ky, Y, lane);
+            f32x4 h;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 16 * t + 4 * quad + r;
+                h[r] = tanhf(acc[r] + wp[L.b1 + row]);
+                A[row * GT + col] = h[r];
+            }
+            st4(L.s_h1e, t, h);
+        }
+        __syncthreads();
+        // ---- encoder layer 2: h2e = tanh(h1e W2^T + b2) -> Bf ----
+        for (int t = wave; t < k2; t += 4) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            acc = tg_gemm(acc, wp + L.W2 + (int64_t)t * k1 * 256, k1, A, lane);
+            f32x4 h;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 16 * t + 4 * quad + r;
+                h[r] = tanhf(acc[r] + wp[L.b2 + row]);
+                Bf[row * GT + col] = h[r];
+            }
+            st4(L.s_h2e, t, h);
+        }
+        __syncthreads();
+        // ---- heads: [mu | log_var] -> C rows 0 .. 2 zp - 1 ----
+        for (int t = wave; t < 2 * kz; t += 4) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            acc = tg_gemm(acc, wp + L.Wh + (int64_t)t * k2 * 256, k2, Bf, lane);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 16 * t + 4 * quad + r;
+                C[row * GT + col] = acc[r] + wp[L.bh + row];
+            }
+        }
+        __syncthreads();
+        // ---- z = mu + exp(log_var / 2) eps -> Bf; the KL terms; what the backward pass needs of the heads -> C ----
+        for (int i = tid; i < GT * L.zp; i += 256) {
+            const int c = i & 15, j = i >> 4;
+            const bool ok = srow[c] >= 0 && j < L.z;
+            const float mu = C[j * GT + c], lv = C[(L.zp + j) * GT + c];
+            const float e = ok ? g.eps[(r0 + c) * L.z + j] : 0.f;
+            const float sd = expf(0.5f * lv), ev = expf(lv);
+            const float zv = mu + sd * e;
+            Bf[j * GT + c] = zv;
+            C[j * GT + c] = ok ? mu * g.invB : 0.f;
+            C[(L.zp + j) * GT + c] = ok ? -0.5f * (1.f - ev) * g.invB : 0.f;
+            C[(2 * L.zp + j) * GT + c] = 0.5f * sd * e;
+            if (ok) sum_kl += (double)(-0.5f * (lv - mu * mu - ev));
+            if (bwd) g.stash[(r0 + c) * (int64_t)L.S + L.s_z + j] = zv;
+        }
+        __syncthreads();
+        // ---- decoder layer 1: d1 = tanh([z | y] D1^T + b) -> A ----
+        for (int t = wave; t < k2; t += 4) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            acc = tg_gemm(acc, wp + L.D1z + (int64_t)t * kz * 256, kz, Bf, lane);
+            acc = tg_gemm(acc, wp + L.D1y + (int64_t)t * ky * 256, ky, Y, lane);
+            f32x4 h;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 16 * t + 4 * quad + r;
+                h[r] = tanhf(acc[r] + wp[L.bd1 + row]);
+                A[row * GT + col] = h[r];
+            }
+            st4(L.s_d1, t, h);
+        }
+        __syncthreads();
+        // ---- decoder layer 2: d2 = tanh(d1 D2^T + b) -> Bf ----
+        for (int t = wave; t < k1; t += 4) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            acc = tg_gemm(acc, wp + L.D2 + (int64_t)t * k2 * 256, k2, A, lane);
+            f32x4 h;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 16 * t + 4 * quad + r;
+                h[r] = tanhf(acc[r] + wp[L.bd2 + row]);
+                Bf[row * GT + col] = h[r];
+            }
+            st4(L.s_d2, t, h);
+        }
+        __syncthreads();
+        // ---- output layer: a = d2 D3^T + b, r = exp(a); Itakura-Saito x / r - log(x + eps) + a - 1; d loss / d a = (1 - x / r) / B -> X ----
+        for (int t = wave; t < GKX; t += 4) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            acc = tg_gemm(acc, wp + L.D3 + (int64_t)t * k1 * 256, k1, Bf, lane);
+            f32x4 da;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 16 * t + 4 * quad + r;
+                const bool ok = fok && row < GX;
+                const float a = acc[r] + wp[L.bd3 + row];
+                const float xv = X[row * GT + col];
+                const float q = xv * expf(-a);
+                if (ok) sum_is += (double)(q - logf(xv + g.elbo_eps) + a - 1.f);
+                da[r] = ok ? (1.f - q) * g.invB : 0.f;
+                if (bwd) X[row * GT + col] = da[r];
+            }
+            st4(L.s_da, t, da);
+        }
+        if (!bwd) continue;
+        __syncthreads();
+        // ---- d d2 = da D3; dpre_d2 = d d2 (1 - d2^2) -> Bf ----
+        for (int t = wave; t < k1; t += 4) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            acc = tg_gemm(acc, wp + L.D3T + (int64_t)t * GKX * 256, GKX, X, lane);
+            f32x4 d;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 16 * t + 4 * quad + r;
+                const float o = Bf[row * GT + col];
+                d[r] = acc[r] * (1.f - o * o);
+                Bf[row * GT + col] = d[r];
+            }
+            st4(L.s_pd2, t, d);
+        }
+        __syncthreads();
+        // ---- d d1 = dpre_d2 D2; dpre_d1 = d d1 (1 - d1^2) -> A ----
+        for (int t = wave; t < k2; t += 4) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            acc = tg_gemm(acc, wp + L.D2T + (int64_t)t * k1 * 256, k1, Bf, lane);
+            f32x4 d;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 16 * t + 4 * quad + r;
+                const float o = A[row * GT + col];
+                d[r] = acc[r] * (1.f - o * o);
+                A[row * GT + col] = d[r];
+            }
+            st4(L.s_pd1, t, d);
+        }
+        __syncthreads();
+        // ---- dz = dpre_d1 D1[:, :z]; d mu = dz + mu / B; d log_var = dz eps std / 2 + its KL part -> C rows 0 .. 2 zp - 1 ----
+        for (int t = wave; t < kz; t += 4) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            acc = tg_gemm(acc, wp + L.D1zT + (int64_t)t * k2 * 256, k2, A, lane);
+            f32x4 dm, dl;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 16 * t + 4 * quad + r;
+                dm[r] = acc[r] + C[row * GT + col];
+                dl[r] = acc[r] * C[(2 * L.zp + row) * GT + col] + C[(L.zp + row) * GT + col];
+                C[row * GT + col] = dm[r];
+                C[(L.zp + row) * GT + col] = dl[r];
+            }
+            st4(L.s_ph, t, dm);
+            st4(L.s_ph + L.zp, t, dl);
+        }
+        __syncthreads();
+        // ---- d h2e = [d mu | d log_var] [Wmu; Wlv]; dpre_e2 = d h2e (1 - h2e^2) -> Bf (h2e: this thread's own stash entry) ----
+        for (int t = wave; t < k2; t += 4) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            acc = tg_gemm(acc, wp + L.WhT + (int64_t)t * 2 * kz * 256, 2 * kz, C, lane);
+            const f32x4 o = ld4(L.s_h2e, t);
+            f32x4 d;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 16 * t + 4 * quad + r;
+                d[r] = acc[r] * (1.f - o[r] * o[r]);
+                Bf[row * GT + col] = d[r];
+            }
+            st4(L.s_pe2, t, d);
+        }
+        __syncthreads();
+        // ---- d h1e = dpre_e2 W2; dpre_e1 = d h1e (1 - h1e^2): only the stash needs it ----
+        for (int t = wave; t < k1; t += 4) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            acc = tg_gemm(acc, wp + L.W2T + (int64_t)t * k2 * 256, k2, Bf, lane);
+            const f32x4 o = ld4(L.s_h1e, t);
+            f32x4 d;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) d[r] = acc[r] * (1.f - o[r] * o[r]);
+            st4(L.s_pe1, t, d);
+        }
+    }
+    // the workgroup's loss sums: waves in order
+    sum_is = wave_sum(sum_is); sum_kl = wave_sum(sum_kl);
+    __syncthreads();                                    // the last tile's readers of X are done: its first bytes hold the sums
+    double (*red)[2] = reinterpret_cast<double (*)[2]>(gsm);
+    if (lane == 0) { red[wave][0] = sum_is; red[wave][1] = sum_kl; }
+    __syncthreads();
+    if (tid == 0) {
+        double* p = g.partials + 4 * (int64_t)blockIdx.x;
+        p[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+        p[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+        p[2] = 0.0; p[3] = 0.0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// weight-gradient kernel
+struct GWgradArgs {
+    const float* x; int64_t ldx;
+    const float* y; int64_t ldy;
+    const int64_t* row_index; int64_t row_count;
+    const float* stash; float* slabs; int64_t slab_stride;
+    int64_t B, slice_frames;
+    const GItem* items;
+    int S;
+    GGemm gm[G_NG];
+    int64_t toff[G_NT];
+};
+
+struct __attribute__((packed, aligned(4))) G4U { f32x4 v; };      // 16 bytes at dword alignment (rows of 513 floats)
+
+// One item = 64 rows of one matrix (four 16-row tiles of dPre) x four 64-column blocks of its input (the bias is one more block behind
+// them), one block a wave, x one frame slice.  A wave keeps a 64 x 64 block of dW in 16 accumulators: per four frames it loads one dPre value
+// per row tile (a quarter wave reads 16 consecutive floats of a frame) and ONE 16-byte piece of the input row -- columns 4 j .. 4 j + 3 of
+// the block, so column tile c holds the block's columns 4 j + c, j = 0 .. 15 -- for sixteen MFMAs.
+__global__ __launch_bounds__(256) void train_generic_wgrad_kernel(const GWgradArgs g) {
+    const GItem it = g.items[blockIdx.x];
+    const GGemm m = g.gm[it.gemm];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int j = lane & 15, quad = lane >> 4;
+    const int64_t f0 = (int64_t)it.slice * g.slice_frames;
+    const int64_t f1 = f0 + g.slice_frames < g.B ? f0 + g.slice_frames : g.B;
+    const int nb0 = (m.in_w + 63) >> 6, nb1 = (m.y_w + 63) >> 6, nb = nb0 + nb1 + 1;
+    const int nrt = m.nrt - 4 * it.rt < 4 ? m.nrt - 4 * it.rt : 4;           // row tiles of this item (it.rt counts 64-row groups)
+    const float* dp = g.stash + m.dpre + 64 * it.rt + j;
+    float* slab = g.slabs + (int64_t)it.slice * g.slab_stride;
+    const int cb = it.cb0 + wave;                       // the wave's 64-column block
+    if (cb < nb) {
+        // the block's source: rows of `ld` floats at `base` with `w` valid columns, this lane's four from c4; output columns from ocol
+        const bool bias = cb == nb0 + nb1, lab = !bias && cb >= nb0;
+        const bool gather = g.row_index && (lab || m.in_kind == 0);
+        const float* base = lab ? g.y : (m.in_kind == 0 ? g.x : g.stash + m.in_off);
+        const int64_t ld = lab ? g.ldy : (m.in_kind == 0 ? g.ldx : (int64_t)g.S);
+        const int w = bias ? 1 : (lab ? m.y_w : m.in_w), ocol = lab ? m.in_w : 0;
+        const int c4 = 64 * (lab ? cb - nb0 : (bias ? 0 : cb)) + 4 * j;
+        const int ntc = w - (c4 - 4 * j) < 4 ? w - (c4 - 4 * j) : 4;          // column tiles with a valid column
+        const int nv = w - c4 < 0 ? 0 : (w - c4 > 4 ? 4 : w - c4);            // this lane's valid columns
+        f32x4 acc[4][4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) acc[r][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // the operands of the four frames from f: frame f + quad; past the slice: zeros
+        auto load = [&](int64_t f, float (&a)[4], f32x4& b) __attribute__((always_inline)) {
+            const int64_t fr = f + quad;
+            const bool ok = fr < f1;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) a[r] = (ok && r < nrt) ? dp[fr * g.S + 16 * r] : 0.f;
+            b = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (bias) {
+                b[0] = 1.f;
+            } else if (ok && nv > 0) {
+                int64_t s = fr;
+                if (gather) {
+                    s = g.row_index[fr];
+                    if (s < 0 || s >= g.row_count) s = 0;
+                }
+                const float* p = base + s * ld + c4;
+                if (nv == 4) b = reinterpret_cast<const G4U*>(p)->v;
+                else { b[0] = p[0]; if (nv > 1) b[1] = p[1]; if (nv > 2) b[2] = p[2]; }
+            }
+        };
+        float a[4], an[4];
+        f32x4 b, bn;
+        load(f0, a, b);
+        for (int64_t f = f0; f < f1; f += 4) {
+            load(f + 4, an, bn);                        // requested before this round's MFMAs (all zeros past the slice)
+            if (nrt == 4 && ntc == 4) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) acc[r][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], b[c], acc[r][c], 0, 0, 0);
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        if (r < nrt && c < ntc) acc[r][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], b[c], acc[r][c], 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) a[r] = an[r];
+            b = bn;
+        }
+#pragma unroll
+        for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = 64 * it.rt + 16 * rt + 4 * quad + r;
+                    if (rt >= nrt || row >= m.rows || c >= nv) continue;
+                    if (bias) {
+                        if (j == 0) slab[g.toff[m.bt] + row] = acc[rt][c][r];
+                    } else {
+                        slab[g.toff[m.wt] + (int64_t)row * m.cols + ocol + c4 + c] = acc[rt][c][r];
+                    }
+                }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// apply kernel: optimizer step, both packed copies, loss scalars
+struct GApplyArgs {
+    ApplyArgs a;
+    GTensor t[G_NT];
+    float* ws;
+    int adam, finalize;
+};
+
+__global__ __launch_bounds__(256) void train_generic_apply_kernel(const GApplyArgs g) {
+    __shared__ double red[4][4];
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx < g.a.n_params) {
+        int t = -1;
+#pragma unroll
+        for (int k = 0; k < G_NT; ++k)
+            if (idx >= g.t[k].off && idx < g.t[k].off + (int64_t)g.t[k].rows * g.t[k].cols) t = k;
+        if (t >= 0) {
+            const GTensor d = g.t[t];
+            float pi = g.a.p[idx];
+            if (g.adam) {
+                const float gi = fused::slab_sum_at(g.a, idx);
+                float mi, vi;
+                fused::adam_element(g.a, pi, g.a.m[idx], g.a.v[idx], gi, mi, vi);
+                g.a.p[idx] = pi; g.a.m[idx] = mi; g.a.v[idx] = vi;
+            }
+            const int i = (int)(idx - d.off);
+            const int r = i / d.cols, c = i - r * d.cols;
+            if (d.bias) {
+                g.ws[d.f0 + d.roff + r] = pi;
+            } else {
+                if (c < d.split) g.ws[d.f0 + frag_pos(r + d.roff, c, d.kb0)] = pi;
+                else g.ws[d.f1 + frag_pos(r + d.roff, c - d.split, d.kb1)] = pi;
+                if (d.t0 >= 0 && c < d.tcmax) g.ws[d.t0 + frag_pos(c, r + d.tkoff, d.tkb)] = pi;
+            }
+        }
+    }
+    if (g.finalize && blockIdx.x == 0) fused::finalize_losses(g.a, red);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// host
+static int plan_layout(const char* who, const dvae_train_generic_plan_t* plan, GLayout& L) {
+    DVAE_CHECK_ARG(plan, "%s: null plan", who);
+    DVAE_CHECK_ARG((plan->model == DVAE_MODEL_M1 || plan->model == DVAE_MODEL_M2) && plan->precision == DVAE_PREC_F32 &&
+                   dims_ok(plan->y_dim, plan->z_dim, plan->h1, plan->h2) && (plan->model == DVAE_MODEL_M1) == (plan->y_dim == 0) && plan->B >= 1,
+                   "%s: not a plan of dvae_train_generic_plan", who);
+    L = make_layout(plan->y_dim, plan->z_dim, plan->h1, plan->h2, plan->B, plan->ksplit);
+    DVAE_CHECK_ARG(L.ws_bytes == plan->workspace_bytes && L.nslices == plan->ksplit && L.n_params == plan->n_params &&
+                   L.slice_frames == plan->slice_frames, "%s: the plan was changed after dvae_train_generic_plan", who);
+    return 0;
+}
+
+static int check_inputs(const char* who, const dvae_train_generic_plan_t* plan, const void* ws, const float* x, int64_t ldx, const float* y,
+                        int64_t ldy, const float* eps) {
+    DVAE_CHECK_ARG(ws && x && eps, "%s: null pointer", who);
+    DVAE_CHECK_ARG(ldx >= GX && ldx < ((int64_t)1 << 20), "%s: leading dimension of x %lld (at least 513)", who, (long long)ldx);
+    DVAE_CHECK_ARG((plan->y_dim > 0) == (y != nullptr), "%s: y must be given exactly when y_dim > 0 (y_dim %d)", who, plan->y_dim);
+    DVAE_CHECK_ARG(!y || (ldy >= plan->y_dim && ldy < ((int64_t)1 << 20)), "%s: leading dimension of y %lld for y_dim %d", who, (long long)ldy, plan->y_dim);
+    DVAE_CHECK_ARG(!plan->row_index || plan->row_count >= 1, "%s: a gather table needs row_count >= 1 (got %lld)", who, (long long)plan->row_count);
+    return 0;
+}
+
+static ApplyArgs apply_args(const dvae_train_generic_plan_t* plan, const GLayout& L, float* params, float* m, float* v, char* ws, bool adam, int step,
+                            double lr, double beta1, double beta2, double adam_eps, double grad_scale, float* losses3) {
+    ApplyArgs a;
+    memset(&a, 0, sizeof(a));
+    a.p = params; a.m = m; a.v = v;
+    a.slabs = (const float*)(ws + L.o_grads); a.slab_stride = L.n_params; a.nslabs = L.nslices;
+    a.n_params = L.n_params;
+    if (adam) {
+        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+        a.one_minus_b1 = (float)(1.0 - beta1); a.b2 = (float)beta2; a.one_minus_b2 = (float)(1.0 - beta2);
+        a.step_size = (float)(lr / bc1); a.bc2_sqrt = (float)sqrt(bc2); a.eps = (float)adam_eps; a.gscale = (float)grad_scale;
+    }
+    a.partials = (const double*)(ws + L.o_partials); a.npartials = (int)L.rows_grid; a.B = L.B; a.losses3 = losses3;
+    a.accum = (double*)(uintptr_t)plan->loss_accum;
+    return a;
+}
+
+// adam: the optimizer step on every parameter; otherwise only the packed copies are rewritten (params != null) and / or the losses finalised
+static int launch_apply(const GLayout& L, const ApplyArgs& a, char* ws, bool adam, bool elements, bool finalize, hipStream_t s) {
+    GApplyArgs g;
+    memset(&g, 0, sizeof(g));
+    g.a = a;
+    if (!elements) g.a.n_params = 0;
+    make_tensors(L, g.t);
+    g.ws = (float*)ws; g.adam = adam ? 1 : 0; g.finalize = finalize ? 1 : 0;
+    const int64_t blocks = elements ? (L.n_params + 255) / 256 : 1;
+    hipLaunchKernelGGL(train_generic_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g);
+    DVAE_LAUNCH_OK("train_generic_apply_kernel");
+    return 0;
+}
+
+static int launch_rows(const dvae_train_generic_plan_t* plan, const GLayout& L, char* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
+                       const float* eps, float elbo_eps, bool fwd_only, hipStream_t s) {
+    constexpr int64_t LDS_MAX = 160 * 1024;
+    if (L.lds_bytes > LDS_MAX) { set_error("train_generic_rows_kernel: %lld B of LDS needed, %lld available", (long long)L.lds_bytes, (long long)LDS_MAX); return DVAE_E_UNSUPPORTED; }
+    if (L.lds_bytes > 64 * 1024) {                      // past the default limit of dynamic LDS: raised once per device
+        static bool attr_done[64] = {};
+        int dev = 0;
+        DVAE_HIP(hipGetDevice(&dev));
+        if (dev < 0 || dev >= 64 || !attr_done[dev]) {
+            hipError_t e = hipFuncSetAttribute((const void*)train_generic_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();                // reported here, not left for the caller's next runtime call
+                set_error("hipFuncSetAttribute(train_generic_rows_kernel, %lld B LDS): %s", (long long)LDS_MAX, hipGetErrorString(e));
+                return (int)e;
+            }
+            if (dev >= 0 && dev < 64) attr_done[dev] = true;
+        }
+    }
+    GRowsArgs g;
+    memset(&g, 0, sizeof(g));
+    g.x = x; g.ldx = ldx; g.y = y; g.ldy = ldy; g.eps = eps;
+    g.row_index = (const int64_t*)(uintptr_t)plan->row_index; g.row_count = plan->row_count; g.bad = (int*)(uintptr_t)plan->bad_row_counter;
+    g.ws = (float*)ws; g.stash = (float*)(ws + L.o_stash); g.partials = (double*)(ws + L.o_partials);
+    g.elbo_eps = elbo_eps; g.invB = (float)(1.0 / (double)L.B); g.fwd_only = fwd_only ? 1 : 0;
+    hipLaunchKernelGGL(train_generic_rows_kernel, dim3((unsigned)L.rows_grid), dim3(256), (size_t)L.lds_bytes, s, L, g);
+    DVAE_LAUNCH_OK("train_generic_rows_kernel");
+    return 0;
+}
+
+static int launch_wgrad(const dvae_train_generic_plan_t* plan, const GLayout& L, char* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
+                        hipStream_t s) {
+    GWgradArgs g;
+    memset(&g, 0, sizeof(g));
+    g.x = x; g.ldx = ldx; g.y = y; g.ldy = ldy;
+    g.row_index = (const int64_t*)(uintptr_t)plan->row_index; g.row_count = plan->row_count;
+    g.stash = (const float*)(ws + L.o_stash); g.slabs = (float*)(ws + L.o_grads); g.slab_stride = L.n_params;
+    g.B = L.B; g.slice_frames = L.slice_frames; g.items = (const GItem*)(ws + L.o_items); g.S = L.S;
+    make_gemms(L, g.gm);
+    for (int t = 0; t < G_NT; ++t) g.toff[t] = L.toff[t];
+    hipLaunchKernelGGL(train_generic_wgrad_kernel, dim3((unsigned)L.n_items), dim3(256), 0, s, g);
+    DVAE_LAUNCH_OK("train_generic_wgrad_kernel");
+    return 0;
+}
+
+}  // namespace tg
+}  // namespace dvae
+
+using namespace dvae;
+using namespace dvae::tg;
+
+extern "C" int dvae_train_generic_plan(int model, int y_dim, int z_dim, int h1, int h2, int precision, int64_t B, int ksplit_hint,
+                                       dvae_train_generic_plan_t* plan) {
+    DVAE_CHECK_ARG(plan, "train_generic_plan: null plan");
+    const char* limits = "the generic train step covers M1 (y_dim 0) and M2 (y_dim 1..513) at x 513, hidden widths 1..512, z_dim 1..128, exact fp32";
+    if (model != DVAE_MODEL_M1 && model != DVAE_MODEL_M2) {
+        set_error("train_generic_plan: model %d (M2_info and M2_DEC exist at the reference geometry only: dvae_train_plan); %s", model, limits);
+        return DVAE_E_UNSUPPORTED;
+    }
+    if (precision != DVAE_PREC_F32) {
+        set_error("train_generic_plan: operand policy %d (the bf16 policies exist at the reference geometry only: dvae_train_plan); %s", precision, limits);
+        return DVAE_E_UNSUPPORTED;
+    }
+    DVAE_CHECK_ARG(dims_ok(y_dim, z_dim, h1, h2), "train_generic_plan: y_dim %d, hidden %d / %d, z_dim %d; %s", y_dim, h1, h2, z_dim, limits);
+    DVAE_CHECK_ARG((model == DVAE_MODEL_M1) == (y_dim == 0), "train_generic_plan: model M%d with y_dim %d; %s", model, y_dim, limits);
+    DVAE_CHECK_ARG(B >= 1 && B < ((int64_t)1 << 31), "train_generic_plan: %lld frames", (long long)B);
+    DVAE_CHECK_ARG(ksplit_hint >= 0 && ksplit_hint <= G_MAX_SLICES, "train_generic_plan: %d frame slices (0 = choose, at most %d)", ksplit_hint, G_MAX_SLICES);
+    const GLayout L = make_layout(y_dim, z_dim, h1, h2, B, ksplit_hint);
+    memset(plan, 0, sizeof(*plan));
+    plan->model = model; plan->y_dim = y_dim; plan->z_dim = z_dim; plan->h1 = h1; plan->h2 = h2; plan->precision = precision;
+    plan->ksplit = L.nslices; plan->n_tensors = G_NT; plan->B = B; plan->n_params = L.n_params;
+    for (int t = 0; t < G_NT; ++t) { plan->tensor_offset[t] = L.toff[t]; plan->tensor_rows[t] = L.trows[t]; plan->tensor_cols[t] = L.tcols[t]; }
+    plan->workspace_bytes = L.ws_bytes; plan->grad_offset_bytes = L.o_grads; plan->Bp = L.Bp; plan->rows_grid = L.rows_grid;
+    plan->slice_frames = L.slice_frames; plan->wgrad_items = L.n_items; plan->lds_bytes = L.lds_bytes;
+    return 0;
+}
+
+extern "C" int dvae_train_generic_repack(const dvae_train_generic_plan_t* plan, const float* params, void* ws, void* stream) {
+    GLayout L;
+    if (int rc = plan_layout("train_generic_repack", plan, L)) return rc;
+    DVAE_CHECK_ARG(params && ws, "train_generic_repack: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    DVAE_HIP(hipMemsetAsync(ws, 0, (size_t)L.wpack_elems * 4, s));          // the padding of the packed copies
+    const ApplyArgs a = apply_args(plan, L, (float*)params, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, nullptr);
+    return launch_apply(L, a, (char*)ws, false, true, false, s);
+}
+
+extern "C" int dvae_train_generic_init(const dvae_train_generic_plan_t* plan, const float* params, void* ws, void* stream) {
+    GLayout L;
+    if (int rc = plan_layout("train_generic_init", plan, L)) return rc;
+    DVAE_CHECK_ARG(params && ws, "train_generic_init: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    GGemm gm[G_NG];
+    make_gemms(L, gm);
+    const int order[G_NG] = {0, 6, 4, 1, 5, 2, 3};                         // the widest inputs first: their items run longest
+    std::vector<GItem> items;
+    for (int sl = 0; sl < L.nslices; ++sl)
+        for (int gi = 0; gi < G_NG; ++gi)
+            for (int rt = 0; rt < (gm[order[gi]].nrt + 3) / 4; ++rt)
+                for (int cg = 0; cg < gemm_col_groups(gm[order[gi]]); ++cg) items.push_back(GItem{order[gi], rt, sl, 4 * cg});
+    DVAE_CHECK_ARG((int)items.size() == L.n_items, "train_generic_init: %d items for a table of %d", (int)items.size(), L.n_items);
+    DVAE_HIP(hipMemcpyAsync((char*)ws + L.o_items, items.data(), items.size() * sizeof(GItem), hipMemcpyHostToDevice, s));
+    DVAE_HIP(hipMemsetAsync((char*)ws + L.o_partials, 0, (size_t)L.rows_grid * 4 * sizeof(double), s));
+    DVAE_HIP(hipStreamSynchronize(s));                                      // the table leaves host memory that ends with this call
+    return dvae_train_generic_repack(plan, params, ws, stream);
+}
+
+extern "C" int dvae_train_generic_grads(const dvae_train_generic_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
+                                        const float* eps_noise, float elbo_eps, void* stream) {
+    GLayout L;
+    if (int rc = plan_layout("train_generic_grads", plan, L)) return rc;
+    if (int rc = check_inputs("train_generic_grads", plan, ws, x, ldx, y, ldy, eps_noise)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = launch_rows(plan, L, (char*)ws, x, ldx, y, ldy, eps_noise, elbo_eps, false, s)) return rc;
+    return launch_wgrad(plan, L, (char*)ws, x, ldx, y, ldy, s);
+}
+
+extern "C" int dvae_train_generic_apply(const dvae_train_generic_plan_t* plan, float* params, float* m, float* v, void* ws, int step, double lr,
+                                        double beta1, double beta2, double adam_eps, double grad_scale, float* losses3, void* stream) {
+    GLayout L;
+    if (int rc = plan_layout("train_generic_apply", plan, L)) return rc;
+    DVAE_CHECK_ARG(params && m && v && ws && losses3, "train_generic_apply: null pointer");
+    DVAE_CHECK_ARG(step >= 1, "train_generic_apply: step %d (1-based)", step);
+    const ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, losses3);
+    return launch_apply(L, a, (char*)ws, true, true, true, (hipStream_t)stream);
+}
+
+extern "C" int dvae_train_generic_step(const dvae_train_generic_plan_t* plan, float* params, float* m, float* v, void* ws, const float* x, int64_t ldx,
+                                       const float* y, int64_t ldy, const float* eps_noise, float elbo_eps, int step, double lr, double beta1,
+                                       double beta2, double adam_eps, float* losses3, void* stream) {
+    DVAE_CHECK_ARG(params && m && v && losses3, "train_generic_step: null pointer");
+    DVAE_CHECK_ARG(step >= 1, "train_generic_step: step %d (1-based)", step);
+    if (int rc = dvae_train_generic_grads(plan, ws, x, ldx, y, ldy, eps_noise, elbo_eps, stream)) return rc;
+    return dvae_train_generic_apply(plan, params, m, v, ws, step, lr, beta1, beta2, adam_eps, 1.0, losses3, stream);
+}
+
+extern "C" int dvae_train_generic_eval(const dvae_train_generic_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
+                                       const float* eps_noise, float elbo_eps, float* losses3, void* stream) {
+    GLayout L;
+    if (int rc = plan_layout("train_generic_eval", plan, L)) return rc;
+    if (int rc = check_inputs("train_generic_eval", plan, ws, x, ldx, y, ldy, eps_noise)) return rc;
+    DVAE_CHECK_ARG(losses3, "train_generic_eval: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = launch_rows(plan, L, (char*)ws, x, ldx, y, ldy, eps_noise, elbo_eps, true, s)) return rc;
+    const ApplyArgs a = apply_args(plan, L, nullptr, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, losses3);
+    return launch_apply(L, a, (char*)ws, false, false, true, s);
+}

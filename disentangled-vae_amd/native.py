@@ -107,6 +107,13 @@ SIGNATURES = {
     "dvae_train_noise": (c_i, [c_vp, ctypes.c_uint64, c_vp, c_vp]),
     "dvae_module_forward": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_i, c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_i, c_vp]),
     "dvae_module_backward": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_i, c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_i, c_vp]),
+    "dvae_train_generic_plan": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, c_i64, c_i, c_vp]),
+    "dvae_train_generic_init": (c_i, [c_vp, c_vp, c_vp, c_vp]),
+    "dvae_train_generic_repack": (c_i, [c_vp, c_vp, c_vp, c_vp]),
+    "dvae_train_generic_grads": (c_i, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_f, c_vp]),
+    "dvae_train_generic_apply": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_d, c_d, c_d, c_d, c_vp, c_vp]),
+    "dvae_train_generic_step": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_f, c_i, c_d, c_d, c_d, c_d, c_vp, c_vp]),
+    "dvae_train_generic_eval": (c_i, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_f, c_vp, c_vp]),
     "dvae_train_profile": (c_i, [c_i]),
     "dvae_train_debug_stamps": (c_i, [c_vp]),
     "dvae_mcem_debug_stamps": (c_i, [c_vp]),

@@ -495,6 +495,37 @@ class Trainer:
         return {n: (ms[i], calls[i]) for i, n in enumerate(names)}
 
 
+def trainer_kind(model, dims):
+    """Which fused train step serves (model, dims): "resident" (the hand-tuned kernels of the reference's geometry, supported()),
+    "generic" (csrc/train_generic.hip: M1 / M2, x 513, y_dim 0 / 1..513, two hidden widths 1..512, z_dim 1..128, fp32) or None.
+    Host logic only."""
+    from . import trainer_generic as G
+    try:
+        if supported(model, dims):
+            return "resident"
+    except KeyError:                    # a dims dict without one of the keys names no geometry of the resident step
+        pass
+    return "generic" if G.covered(model, dims) else None
+
+
+def make_trainer(model, dims, generic=False, **kw):
+    """A Trainer where supported() holds (the default there: it is the faster step), otherwise a GenericTrainer; raises with the limits
+    named when neither covers (model, dims).  generic=True puts the reference geometry on the generic step too."""
+    from . import trainer_generic as G
+    kind = trainer_kind(model, dims)
+    if kind is None:
+        raise NotImplementedError(f"no fused train step for {model} {dims}: the resident step covers M1 / M2 (y 1 or 513) / M2_info (y 1) at "
+                                  f"x 513, z 16, h [128, 128]; {G.LIMITS}")
+    if kind == "resident" and not (generic and G.covered(model, dims)):
+        if generic:
+            raise NotImplementedError(f"generic=True: {G.LIMITS}; got {model} {dims}")
+        return Trainer(model, dims, **kw)
+    if kw.get("precision", "fp32") != "fp32":
+        raise NotImplementedError(f"precision {kw['precision']!r} exists on the resident step only; {G.LIMITS}")
+    kw.pop("precision", None)
+    return G.GenericTrainer(model, dims, **kw)
+
+
 class BenchImpl:
     """bench.py adapter: the fused path."""
 

@@ -173,6 +173,65 @@ int dvae_train_noise(const dvae_train_plan_t* plan, uint64_t step, float* eps_ou
 /* Rebuild the kernel-layout weight copies after `params` was written from outside (load_state_dict). */
 int dvae_train_repack(const dvae_train_plan_t* plan, const float* params, void* ws, void* stream);
 
+/* ---- the fused train step for M1 / M2 of ANY covered size (csrc/train_generic.hip): x 513, y_dim 0 (M1) or 1..513 (M2: encoder on
+ * [x | y], decoder on [z | y]), hidden widths h1 / h2 1..512, z_dim 1..128 -- the limits of dvae_mcem_plan_dims -- two tanh layers a side,
+ * loss elbo, exact fp32.  Three launches per step whatever the geometry: rows kernel (forward, loss terms, backward-data chain; layer inputs
+ * and pre-activation gradients to a stash), weight-gradient kernel (all seven matrices and biases, one partial slab per frame slice, no
+ * atomics), apply kernel (slab sums in slab order, the Adam element of dvae_train_apply, both packed weight copies, the loss scalars).
+ * The resident step above stays the default at z 16 / h (128, 128); this one also runs there when asked.  Same conventions: caller-owned
+ * flat buffers laid out per the plan (state_dict order, 256-byte aligned tensors), scratch in `ws`, results stream-ordered. */
+typedef struct {
+    /* inputs (echoed) */
+    int32_t model;            /* DVAE_MODEL_M1 or DVAE_MODEL_M2 */
+    int32_t y_dim, z_dim, h1, h2;
+    int32_t precision;        /* DVAE_PREC_F32 */
+    int32_t ksplit;           /* frame slices of the weight-gradient reduction = slabs the apply kernel sums (at most 16) */
+    int32_t n_tensors;        /* 14 */
+    int64_t B;                /* frames per step */
+    int64_t n_params;         /* flat length in floats (with alignment gaps) */
+    int64_t tensor_offset[DVAE_TRAIN_MAX_TENSORS];      /* in floats */
+    int32_t tensor_rows[DVAE_TRAIN_MAX_TENSORS];
+    int32_t tensor_cols[DVAE_TRAIN_MAX_TENSORS];        /* 1 for biases */
+    int64_t workspace_bytes;
+    int64_t grad_offset_bytes;   /* ws + this = ksplit slabs of n_params floats */
+    int64_t Bp;                  /* frames padded to whole 16-frame tiles */
+    int64_t rows_grid;           /* workgroups of the rows kernel (tiles beyond it are strided over) */
+    int64_t slice_frames;        /* frames of a slice (a multiple of 16; the last slice may be shorter) */
+    int64_t wgrad_items;         /* workgroups of the weight-gradient launch */
+    int64_t lds_bytes;           /* dynamic LDS of the rows kernel */
+    /* set by the caller between calls, as in dvae_train_plan_t: float64 running sums (8 doubles) or 0; the gather table (B int64 row
+       numbers of the frame store x / y) or 0, the rows of that store, and the int32 counter of refused indices or 0.  An index outside
+       [0, row_count) is never dereferenced: row 0 is read instead and the counter incremented. */
+    uint64_t loss_accum;
+    uint64_t row_index;
+    int64_t  row_count;
+    uint64_t bad_row_counter;
+} dvae_train_generic_plan_t;
+
+/* Host only.  ksplit_hint 0 = choose.  DVAE_E_UNSUPPORTED for M2_info / M2_DEC and the bf16 policies (they exist at the reference geometry
+ * only), DVAE_E_BADARG naming the limits for a size outside them. */
+int dvae_train_generic_plan(int model, int y_dim, int z_dim, int h1, int h2, int precision, int64_t B, int ksplit_hint,
+                            dvae_train_generic_plan_t* plan);
+/* One-time setup of `ws` (item table, packed weight copies from `params`); synchronises the stream once. */
+int dvae_train_generic_init(const dvae_train_generic_plan_t* plan, const float* params, void* ws, void* stream);
+/* Rebuild both packed weight copies after `params` was written from outside. */
+int dvae_train_generic_repack(const dvae_train_generic_plan_t* plan, const float* params, void* ws, void* stream);
+/* rows kernel + weight-gradient kernel: x [B, 513] (ldx), y [B, y_dim] (ldy; NULL for M1) -- or the frame stores under a gather table --,
+ * eps_noise [B, z_dim] (required).  The gradient of the mean loss over the B frames is left as plan->ksplit slabs. */
+int dvae_train_generic_grads(const dvae_train_generic_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
+                             const float* eps_noise, float elbo_eps, void* stream);
+/* apply kernel: g = grad_scale * (slabs summed in slab order); Adam at `step` (1-based); packed copies; losses3 = {recon + KL, recon, KL}.
+ * Separate from _grads so that a gradient exchange can sit between them. */
+int dvae_train_generic_apply(const dvae_train_generic_plan_t* plan, float* params, float* m, float* v, void* ws, int step, double lr,
+                             double beta1, double beta2, double adam_eps, double grad_scale, float* losses3, void* stream);
+/* dvae_train_generic_grads + dvae_train_generic_apply with grad_scale 1. */
+int dvae_train_generic_step(const dvae_train_generic_plan_t* plan, float* params, float* m, float* v, void* ws, const float* x, int64_t ldx,
+                            const float* y, int64_t ldy, const float* eps_noise, float elbo_eps, int step, double lr, double beta1,
+                            double beta2, double adam_eps, float* losses3, void* stream);
+/* Forward and loss only (two launches): parameters, moments and gradient slabs are left alone. */
+int dvae_train_generic_eval(const dvae_train_generic_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
+                            const float* eps_noise, float elbo_eps, float* losses3, void* stream);
+
 /* Per-kernel device time of the last `dvae_train_*` calls made with profiling enabled:
  * enable != 0 brackets each launch with hipEvents on its stream (a few us of host cost each).
  * dvae_train_profile_read synchronises and returns accumulated ms and launch counts
