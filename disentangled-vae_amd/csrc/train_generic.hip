@@ -33,19 +33,11 @@ namespace dvae {
 namespace tg {
 
 using fused::ApplyArgs;
-
-static inline int up16(int v) { return (v + 15) / 16 * 16; }
-static inline int64_t al64(int64_t v) { return (v + 63) / 64 * 64; }        // floats: 256 bytes
-static inline int64_t al256(int64_t v) { return (v + 255) / 256 * 256; }
+static void make_gemms(const GLayout& L, GGemm* G);
 
 static bool dims_ok(int y, int z, int h1, int h2) {
     return y >= 0 && y <= GX && h1 >= 1 && h1 <= G_HMAX && h2 >= 1 && h2 <= G_HMAX && z >= 1 && z <= G_ZMAX;
 }
-
-static void make_gemms(const GLayout& L, GGemm* G);
-// items of one matrix and one frame slice: 64-row groups x groups of four 64-column blocks (input, labels, one block for the bias)
-static int gemm_col_groups(const GGemm& m) { return ((m.in_w + 63) / 64 + (m.y_w + 63) / 64 + 1 + 3) / 4; }
-static int gemm_items(const GGemm& m) { return (m.nrt + 3) / 4 * gemm_col_groups(m); }
 
 static GLayout make_layout(int y, int z, int h1, int h2, int64_t B, int ksplit_hint) {
     GLayout L;
@@ -89,15 +81,7 @@ static GLayout make_layout(int y, int z, int h1, int h2, int64_t B, int ksplit_h
     make_gemms(L, gm);
     int row_tiles = 0;                                    // weight-gradient items of one frame slice
     for (int i = 0; i < G_NG; ++i) row_tiles += gemm_items(gm[i]);
-    int64_t ks = ksplit_hint;
-    if (ks <= 0) {                                        // about three workgroups a compute unit, at least 64 frames a slice
-        ks = (768 + row_tiles - 1) / row_tiles;
-        if (ks > B / 64) ks = B / 64;
-    }
-    if (ks > G_MAX_SLICES) ks = G_MAX_SLICES;
-    if (ks < 1) ks = 1;
-    L.slice_frames = ((B + ks - 1) / ks + 15) / 16 * 16;
-    L.nslices = (int)((B + L.slice_frames - 1) / L.slice_frames);
+    choose_slices(B, row_tiles, ksplit_hint, L.slice_frames, L.nslices);
     L.n_items = row_tiles * L.nslices;
     // workspace
     int64_t w = al256(L.wpack_elems * 4);
@@ -162,35 +146,6 @@ struct GRowsArgs {
     float elbo_eps, invB;
     int fwd_only;
 };
-
-// acc += W[row tile] (16 x 16 kb) * act (16 kb x 16 frames): W in fragment order, act in LDS as [k][16]
-__device__ __forceinline__ f32x4 tg_gemm(f32x4 acc, const float* __restrict__ wt, int kb, const float* act, int lane) {
-    // k ascending, four k blocks a round with the next round's fragments requested before this round's MFMAs: the loads are L2 hits of
-    // several hundred cycles and a workgroup may be alone on its CU
-    const f32x4* w = reinterpret_cast<const f32x4*>(wt) + lane;
-    auto step = [&](const f32x4& a, int b) __attribute__((always_inline)) {
-        const float* bp = act + b * 256 + lane;
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], bp[0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], bp[64], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], bp[128], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], bp[192], acc, 0, 0, 0);
-    };
-    const int kb4 = kb & ~3;
-    if (kb4) {
-        f32x4 c0 = w[0], c1 = w[64], c2 = w[128], c3 = w[192];
-        for (int b = 0; b < kb4; b += 4) {
-            f32x4 n0 = c0, n1 = c1, n2 = c2, n3 = c3;
-            if (b + 4 < kb4) {
-                const f32x4* wn = w + (int64_t)(b + 4) * 64;
-                n0 = wn[0]; n1 = wn[64]; n2 = wn[128]; n3 = wn[192];
-            }
-            step(c0, b); step(c1, b + 1); step(c2, b + 2); step(c3, b + 3);
-            c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        }
-    }
-    for (int b = kb4; b < kb; ++b) step(w[(int64_t)b * 64], b);
-    return acc;
-}
 
 __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L, const GRowsArgs g) {
     extern __shared__ __attribute__((aligned(16))) float gsm[];
@@ -444,19 +399,7 @@ __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// weight-gradient kernel
-struct GWgradArgs {
-    const float* x; int64_t ldx;
-    const float* y; int64_t ldy;
-    const int64_t* row_index; int64_t row_count;
-    const float* stash; float* slabs; int64_t slab_stride;
-    int64_t B, slice_frames;
-    const GItem* items;
-    int S;
-    GGemm gm[G_NG];
-    int64_t toff[G_NT];
-};
-
+// weight-gradient kernel (GWgradArgs: train_generic.hpp; the classifier step launches it too)
 struct __attribute__((packed, aligned(4))) G4U { f32x4 v; };      // 16 bytes at dword alignment (rows of 513 floats)
 
 // One item = 64 rows of one matrix (four 16-row tiles of dPre) x four 64-column blocks of its input (the bias is one more block behind
@@ -549,14 +492,8 @@ __global__ __launch_bounds__(256) void train_generic_wgrad_kernel(const GWgradAr
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// apply kernel: optimizer step, both packed copies, loss scalars
-struct GApplyArgs {
-    ApplyArgs a;
-    GTensor t[G_NT];
-    float* ws;
-    int adam, finalize;
-};
-
+// apply kernel: optimizer step, both packed copies, loss scalars (GApplyArgs: train_generic.hpp; the classifier step launches it too,
+// with its confusion counts to finalise)
 __global__ __launch_bounds__(256) void train_generic_apply_kernel(const GApplyArgs g) {
     __shared__ double red[4][4];
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -585,7 +522,45 @@ __global__ __launch_bounds__(256) void train_generic_apply_kernel(const GApplyAr
             }
         }
     }
-    if (g.finalize && blockIdx.x == 0) fused::finalize_losses(g.a, red);
+    if (g.finalize && blockIdx.x == 0) {
+        fused::finalize_losses(g.a, red);
+        if (g.cnt_partials && threadIdx.x < 4) {            // integers, workgroup order
+            long long c = 0;
+            for (int i = 0; i < g.cnt_wgs; ++i) c += g.cnt_partials[4 * (int64_t)i + threadIdx.x];
+            g.counts4[threadIdx.x] = c;
+            if (g.cnt_accum) g.cnt_accum[threadIdx.x] += c;
+        }
+    }
+}
+
+int launch_wgrad_table(const GWgradArgs& g, int n_items, hipStream_t s) {
+    hipLaunchKernelGGL(train_generic_wgrad_kernel, dim3((unsigned)n_items), dim3(256), 0, s, g);
+    DVAE_LAUNCH_OK("train_generic_wgrad_kernel");
+    return 0;
+}
+
+int launch_apply_table(const GApplyArgs& g, hipStream_t s) {
+    const int64_t blocks = g.a.n_params > 0 ? (g.a.n_params + 255) / 256 : 1;
+    hipLaunchKernelGGL(train_generic_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g);
+    DVAE_LAUNCH_OK("train_generic_apply_kernel");
+    return 0;
+}
+
+int raise_lds_limit(const void* kernel, const char* name, int64_t lds_bytes, bool (&done)[64]) {
+    if (lds_bytes > G_LDS_MAX) { set_error("%s: %lld B of LDS needed, %lld available", name, (long long)lds_bytes, (long long)G_LDS_MAX); return DVAE_E_UNSUPPORTED; }
+    if (lds_bytes <= 64 * 1024) return 0;
+    int dev = 0;
+    DVAE_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !done[dev]) {
+        hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G_LDS_MAX);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();                    // reported here, not left for the caller's next runtime call
+            set_error("hipFuncSetAttribute(%s, %lld B LDS): %s", name, (long long)G_LDS_MAX, hipGetErrorString(e));
+            return (int)e;
+        }
+        if (dev >= 0 && dev < 64) done[dev] = true;
+    }
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -636,30 +611,13 @@ static int launch_apply(const GLayout& L, const ApplyArgs& a, char* ws, bool ada
     if (!elements) g.a.n_params = 0;
     make_tensors(L, g.t);
     g.ws = (float*)ws; g.adam = adam ? 1 : 0; g.finalize = finalize ? 1 : 0;
-    const int64_t blocks = elements ? (L.n_params + 255) / 256 : 1;
-    hipLaunchKernelGGL(train_generic_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g);
-    DVAE_LAUNCH_OK("train_generic_apply_kernel");
-    return 0;
+    return launch_apply_table(g, s);
 }
 
 static int launch_rows(const dvae_train_generic_plan_t* plan, const GLayout& L, char* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
                        const float* eps, float elbo_eps, bool fwd_only, hipStream_t s) {
-    constexpr int64_t LDS_MAX = 160 * 1024;
-    if (L.lds_bytes > LDS_MAX) { set_error("train_generic_rows_kernel: %lld B of LDS needed, %lld available", (long long)L.lds_bytes, (long long)LDS_MAX); return DVAE_E_UNSUPPORTED; }
-    if (L.lds_bytes > 64 * 1024) {                      // past the default limit of dynamic LDS: raised once per device
-        static bool attr_done[64] = {};
-        int dev = 0;
-        DVAE_HIP(hipGetDevice(&dev));
-        if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-            hipError_t e = hipFuncSetAttribute((const void*)train_generic_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();                // reported here, not left for the caller's next runtime call
-                set_error("hipFuncSetAttribute(train_generic_rows_kernel, %lld B LDS): %s", (long long)LDS_MAX, hipGetErrorString(e));
-                return (int)e;
-            }
-            if (dev >= 0 && dev < 64) attr_done[dev] = true;
-        }
-    }
+    static bool attr_done[64] = {};
+    if (int rc = raise_lds_limit((const void*)train_generic_rows_kernel, "train_generic_rows_kernel", L.lds_bytes, attr_done)) return rc;
     GRowsArgs g;
     memset(&g, 0, sizeof(g));
     g.x = x; g.ldx = ldx; g.y = y; g.ldy = ldy; g.eps = eps;
@@ -681,9 +639,7 @@ static int launch_wgrad(const dvae_train_generic_plan_t* plan, const GLayout& L,
     g.B = L.B; g.slice_frames = L.slice_frames; g.items = (const GItem*)(ws + L.o_items); g.S = L.S;
     make_gemms(L, g.gm);
     for (int t = 0; t < G_NT; ++t) g.toff[t] = L.toff[t];
-    hipLaunchKernelGGL(train_generic_wgrad_kernel, dim3((unsigned)L.n_items), dim3(256), 0, s, g);
-    DVAE_LAUNCH_OK("train_generic_wgrad_kernel");
-    return 0;
+    return launch_wgrad_table(g, L.n_items, s);
 }
 
 }  // namespace tg
@@ -736,11 +692,7 @@ extern "C" int dvae_train_generic_init(const dvae_train_generic_plan_t* plan, co
     GGemm gm[G_NG];
     make_gemms(L, gm);
     const int order[G_NG] = {0, 6, 4, 1, 5, 2, 3};                         // the widest inputs first: their items run longest
-    std::vector<GItem> items;
-    for (int sl = 0; sl < L.nslices; ++sl)
-        for (int gi = 0; gi < G_NG; ++gi)
-            for (int rt = 0; rt < (gm[order[gi]].nrt + 3) / 4; ++rt)
-                for (int cg = 0; cg < gemm_col_groups(gm[order[gi]]); ++cg) items.push_back(GItem{order[gi], rt, sl, 4 * cg});
+    const std::vector<GItem> items = make_items(gm, order, G_NG, L.nslices);
     DVAE_CHECK_ARG((int)items.size() == L.n_items, "train_generic_init: %d items for a table of %d", (int)items.size(), L.n_items);
     DVAE_HIP(hipMemcpyAsync((char*)ws + L.o_items, items.data(), items.size() * sizeof(GItem), hipMemcpyHostToDevice, s));
     DVAE_HIP(hipMemsetAsync((char*)ws + L.o_partials, 0, (size_t)L.rows_grid * 4 * sizeof(double), s));

@@ -1,7 +1,12 @@
-// Plain structs of the generic fused train step (train_generic.hip; include/dvae_train.h: dvae_train_generic_*): the packed weight
-// copies, the stash of one frame, the workspace, and the tables the weight-gradient and optimizer launches read.
+// What the fused train steps of any covered size share (train_generic.hip: the M1 / M2 step, dvae_train_generic_*; train_classifier.hip:
+// the label classifier's step, dvae_train_clf_*; include/dvae_train.h): the packed weight copies in fragment order and the product that
+// reads them, the tables the weight-gradient and optimizer launches read, and the launches of those two kernels, which live in
+// train_generic.hip and serve both steps.  Below them: the plain structs of the M1 / M2 step alone.
 #pragma once
 #include <stdint.h>
+#include <vector>
+#include "common.hpp"
+#include "apply_types.hpp"
 
 namespace dvae {
 namespace tg {
@@ -9,8 +14,12 @@ namespace tg {
 constexpr int GT = 16;                          // frames per tile
 constexpr int GX = 513, GXP = 528, GKX = GXP / 16;
 constexpr int G_HMAX = 512, G_ZMAX = 128;       // the limits of dvae_mcem_plan_dims / mlp_generic.hip
-constexpr int G_NT = 14, G_NG = 7;              // tensors (state_dict order), weight matrices
+constexpr int G_NT = 14, G_NG = 7;              // tensors (state_dict order), weight matrices: the sizes of the tables (a step may use fewer)
 constexpr int G_ROWS_GRID = 256, G_MAX_SLICES = 16;   // one rows workgroup per compute unit, the other tiles strided over; slabs the apply kernel sums
+
+inline int up16(int v) { return (v + 15) / 16 * 16; }
+inline int64_t al64(int64_t v) { return (v + 63) / 64 * 64; }        // floats: 256 bytes
+inline int64_t al256(int64_t v) { return (v + 255) / 256 * 256; }
 
 // element (row, k) of a matrix packed in fragment order [row tile][k block of 16][lane][4] with kb k blocks (mlp_generic.hip: lane l
 // holds row l & 15, inputs 16 b + 4 i + (l >> 4))
@@ -18,24 +27,34 @@ __host__ __device__ inline int64_t frag_pos(int row, int k, int kb) {
     return ((((int64_t)(row >> 4) * kb + (k >> 4)) * 64 + (((k & 3) << 4) | (row & 15))) << 2) + ((k & 15) >> 2);
 }
 
-struct GLayout {
-    int y, z, h1, h2, yp, zp, h1p, h2p, hm;     // sizes and their multiples of 16 (yp 0 without labels); hm = max(h1p, h2p, zp)
-    // packed copies, float offsets from the start of the workspace: forward [out tile][k block], x / z block and label block apart;
-    // the heads are one matrix (mu rows 0 .. z - 1, log_var rows zp .. zp + z - 1)
-    int64_t W1x, W1y, W2, Wh, D1z, D1y, D2, D3;
-    int64_t D3T, D2T, D1zT, WhT, W2T;           // the transposed copies of the backward-data products
-    int64_t b1, b2, bh, bd1, bd2, bd3;          // zero-padded biases
-    int64_t wpack_elems;
-    // the stash of one frame (floats): layer inputs, then the pre-activation gradients
-    int S, s_h1e, s_h2e, s_z, s_d1, s_d2, s_pe1, s_pe2, s_ph, s_pd1, s_pd2, s_da;
-    // workspace (bytes)
-    int64_t o_items, o_partials, o_stash, o_grads, ws_bytes;
-    int64_t B, Bp, tiles, rows_grid, slice_frames, n_params;
-    int nslices, n_items;
-    int64_t lds_bytes;
-    int64_t toff[G_NT];
-    int trows[G_NT], tcols[G_NT];
-};
+// acc += W[row tile] (16 x 16 kb) * act (16 kb x 16 frames): W in fragment order, act in LDS as [k][16]
+__device__ __forceinline__ f32x4 tg_gemm(f32x4 acc, const float* __restrict__ wt, int kb, const float* act, int lane) {
+    // k ascending, four k blocks a round with the next round's fragments requested before this round's MFMAs: the loads are L2 hits of
+    // several hundred cycles and a workgroup may be alone on its CU
+    const f32x4* w = reinterpret_cast<const f32x4*>(wt) + lane;
+    auto step = [&](const f32x4& a, int b) __attribute__((always_inline)) {
+        const float* bp = act + b * 256 + lane;
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], bp[0], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], bp[64], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], bp[128], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], bp[192], acc, 0, 0, 0);
+    };
+    const int kb4 = kb & ~3;
+    if (kb4) {
+        f32x4 c0 = w[0], c1 = w[64], c2 = w[128], c3 = w[192];
+        for (int b = 0; b < kb4; b += 4) {
+            f32x4 n0 = c0, n1 = c1, n2 = c2, n3 = c3;
+            if (b + 4 < kb4) {
+                const f32x4* wn = w + (int64_t)(b + 4) * 64;
+                n0 = wn[0]; n1 = wn[64]; n2 = wn[128]; n3 = wn[192];
+            }
+            step(c0, b); step(c1, b + 1); step(c2, b + 2); step(c3, b + 3);
+            c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        }
+    }
+    for (int b = kb4; b < kb; ++b) step(w[(int64_t)b * 64], b);
+    return acc;
+}
 
 // where a parameter lives in the packed copies
 struct GTensor {
@@ -56,6 +75,87 @@ struct GGemm {
 };
 
 struct GItem { int32_t gemm, rt, slice, cb0; };      // rt: the 64-row group of the matrix; cb0: the first of its four 64-column blocks
+
+// items of one matrix and one frame slice: 64-row groups x groups of four 64-column blocks (input, labels, one block for the bias)
+inline int gemm_col_groups(const GGemm& m) { return ((m.in_w + 63) / 64 + (m.y_w + 63) / 64 + 1 + 3) / 4; }
+inline int gemm_items(const GGemm& m) { return (m.nrt + 3) / 4 * gemm_col_groups(m); }
+
+// the item table of a weight-gradient launch: per frame slice, the matrices in `order` (the widest inputs first: their items run longest)
+inline std::vector<GItem> make_items(const GGemm* gm, const int* order, int ng, int nslices) {
+    std::vector<GItem> items;
+    for (int sl = 0; sl < nslices; ++sl)
+        for (int gi = 0; gi < ng; ++gi)
+            for (int rt = 0; rt < (gm[order[gi]].nrt + 3) / 4; ++rt)
+                for (int cg = 0; cg < gemm_col_groups(gm[order[gi]]); ++cg) items.push_back(GItem{order[gi], rt, sl, 4 * cg});
+    return items;
+}
+
+// frame slices of the weight-gradient reduction for `row_tiles` items a slice: about three workgroups a compute unit, at least 64 frames
+// a slice (hint > 0: as asked); -> frames of a slice (a multiple of 16), slices
+inline void choose_slices(int64_t B, int row_tiles, int ksplit_hint, int64_t& slice_frames, int& nslices) {
+    int64_t ks = ksplit_hint;
+    if (ks <= 0) {
+        ks = (768 + row_tiles - 1) / row_tiles;
+        if (ks > B / 64) ks = B / 64;
+    }
+    if (ks > G_MAX_SLICES) ks = G_MAX_SLICES;
+    if (ks < 1) ks = 1;
+    slice_frames = ((B + ks - 1) / ks + 15) / 16 * 16;
+    nslices = (int)((B + slice_frames - 1) / slice_frames);
+}
+
+// weight-gradient kernel (train_generic.hip: train_generic_wgrad_kernel)
+struct GWgradArgs {
+    const float* x; int64_t ldx;
+    const float* y; int64_t ldy;
+    const int64_t* row_index; int64_t row_count;
+    const float* stash; float* slabs; int64_t slab_stride;
+    int64_t B, slice_frames;
+    const GItem* items;
+    int S;
+    GGemm gm[G_NG];
+    int64_t toff[G_NT];
+};
+
+// apply kernel (train_generic.hip: train_generic_apply_kernel): optimizer step, both packed copies, loss scalars; with `cnt_partials`
+// also the confusion counts of the classifier step: [cnt_wgs][4] integers summed in workgroup order into counts4 (and added to cnt_accum)
+struct GApplyArgs {
+    fused::ApplyArgs a;
+    GTensor t[G_NT];
+    float* ws;
+    int adam, finalize;
+    const long long* cnt_partials; int cnt_wgs;
+    long long* counts4; long long* cnt_accum;
+};
+
+// the two launches, for a caller that has filled the tables (unused entries zeroed): n_items workgroups; one thread a parameter of
+// g.a.n_params (0: one workgroup that only finalises)
+int launch_wgrad_table(const GWgradArgs& g, int n_items, hipStream_t s);
+int launch_apply_table(const GApplyArgs& g, hipStream_t s);
+// dynamic LDS past the default 64 KB limit for a rows kernel: raised once per device (done: the caller's flags, one per device)
+int raise_lds_limit(const void* kernel, const char* name, int64_t lds_bytes, bool (&done)[64]);
+constexpr int64_t G_LDS_MAX = 160 * 1024;
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// the M1 / M2 step
+struct GLayout {
+    int y, z, h1, h2, yp, zp, h1p, h2p, hm;     // sizes and their multiples of 16 (yp 0 without labels); hm = max(h1p, h2p, zp)
+    // packed copies, float offsets from the start of the workspace: forward [out tile][k block], x / z block and label block apart;
+    // the heads are one matrix (mu rows 0 .. z - 1, log_var rows zp .. zp + z - 1)
+    int64_t W1x, W1y, W2, Wh, D1z, D1y, D2, D3;
+    int64_t D3T, D2T, D1zT, WhT, W2T;           // the transposed copies of the backward-data products
+    int64_t b1, b2, bh, bd1, bd2, bd3;          // zero-padded biases
+    int64_t wpack_elems;
+    // the stash of one frame (floats): layer inputs, then the pre-activation gradients
+    int S, s_h1e, s_h2e, s_z, s_d1, s_d2, s_pe1, s_pe2, s_ph, s_pd1, s_pd2, s_da;
+    // workspace (bytes)
+    int64_t o_items, o_partials, o_stash, o_grads, ws_bytes;
+    int64_t B, Bp, tiles, rows_grid, slice_frames, n_params;
+    int nslices, n_items;
+    int64_t lds_bytes;
+    int64_t toff[G_NT];
+    int trows[G_NT], tcols[G_NT];
+};
 
 }  // namespace tg
 }  // namespace dvae

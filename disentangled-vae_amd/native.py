@@ -114,6 +114,13 @@ SIGNATURES = {
     "dvae_train_generic_apply": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_d, c_d, c_d, c_d, c_vp, c_vp]),
     "dvae_train_generic_step": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_f, c_i, c_d, c_d, c_d, c_d, c_vp, c_vp]),
     "dvae_train_generic_eval": (c_i, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_f, c_vp, c_vp]),
+    "dvae_train_clf_plan": (c_i, [c_i, c_i, c_i, c_i, c_i64, c_i, c_vp]),
+    "dvae_train_clf_init": (c_i, [c_vp, c_vp, c_vp, c_vp]),
+    "dvae_train_clf_repack": (c_i, [c_vp, c_vp, c_vp, c_vp]),
+    "dvae_train_clf_grads": (c_i, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_f, c_vp]),
+    "dvae_train_clf_apply": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_d, c_d, c_d, c_d, c_vp, c_vp, c_vp]),
+    "dvae_train_clf_step": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_f, c_i, c_d, c_d, c_d, c_d, c_vp, c_vp, c_vp]),
+    "dvae_train_clf_eval": (c_i, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_f, c_vp, c_vp, c_vp]),
     "dvae_train_profile": (c_i, [c_i]),
     "dvae_train_debug_stamps": (c_i, [c_vp]),
     "dvae_mcem_debug_stamps": (c_i, [c_vp]),

@@ -232,6 +232,69 @@ int dvae_train_generic_step(const dvae_train_generic_plan_t* plan, float* params
 int dvae_train_generic_eval(const dvae_train_generic_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
                             const float* eps_noise, float elbo_eps, float* losses3, void* stream);
 
+/* ---- the fused train step for the label classifier alone (csrc/train_classifier.hip): Classifier([513, [h1, h2], y_dim]) of
+ * packages/models/models.py -- relu, relu, sigmoid -- under binary_cross_entropy (packages/models/utils.py:55-56) and Adam: the loop body
+ * the reference sketches in scripts/train_audio_net.py, and the net it otherwise trains only as a side net of M2_info
+ * (scripts/training_M2_info_vad_pretrain.py).  x 513, h1 / h2 1..512, y_dim 1..513 (the limits of dvae_classify_generic_batch, which runs
+ * the result), exact fp32, one GPU.  Three launches per step: rows kernel (forward, BCE, confusion counts, backward-data chain, stash),
+ * the weight-gradient and apply kernels of the generic step above on this step's tables.  Contract:
+ *   loss      mean over the B frames of -sum_j [y_j log(p_j + eps) + (1 - y_j) log(1 - p_j + eps)], p = sigmoid(a); labels are floats,
+ *             soft labels in [0, 1] go through the same formulas; summed per workgroup in double, workgroups in order;
+ *   backward  d loss / d p = -(1 / B) (y / (p + eps) - (1 - y) / (1 - p + eps)) with the eps terms kept, then p (1 - p) and the relu masks;
+ *   counts    tp, tn, fp, fn over all B * y_dim elements (prediction p > 0.5, truth y != 0; the order of dvae_label_counts_batch), integers;
+ *   the same inputs give the same bits (no atomics on floats; slabs and partial sums in a fixed order);
+ *   six tensors in Classifier.state_dict() order: hidden.0.weight, hidden.0.bias, hidden.1.weight, hidden.1.bias, output_layer.weight,
+ *   output_layer.bias, each at a 256-byte aligned offset of the flat buffers. */
+typedef struct {
+    /* inputs (echoed) */
+    int32_t h1, h2, y_dim;
+    int32_t precision;        /* DVAE_PREC_F32 */
+    int32_t ksplit;           /* frame slices of the weight-gradient reduction = slabs the apply kernel sums (at most 16) */
+    int32_t n_tensors;        /* 6 */
+    int64_t B;                /* frames per step */
+    int64_t n_params;         /* flat length in floats (with alignment gaps) */
+    int64_t tensor_offset[DVAE_TRAIN_MAX_TENSORS];      /* in floats */
+    int32_t tensor_rows[DVAE_TRAIN_MAX_TENSORS];
+    int32_t tensor_cols[DVAE_TRAIN_MAX_TENSORS];        /* 1 for biases */
+    int64_t workspace_bytes;
+    int64_t grad_offset_bytes;   /* ws + this = ksplit slabs of n_params floats */
+    int64_t Bp;                  /* frames padded to whole 16-frame tiles */
+    int64_t rows_grid;           /* workgroups of the rows kernel (tiles beyond it are strided over) */
+    int64_t slice_frames;        /* frames of a slice (a multiple of 16; the last slice may be shorter) */
+    int64_t wgrad_items;         /* workgroups of the weight-gradient launch */
+    int64_t lds_bytes;           /* dynamic LDS of the rows kernel */
+    /* set by the caller between calls: float64 running sums (8 doubles; the loss is added to the first two) or 0; int64 running counts
+       (4) or 0; the gather table, the rows of the frame store and the counter of refused indices as in dvae_train_generic_plan_t */
+    uint64_t loss_accum;
+    uint64_t count_accum;
+    uint64_t row_index;
+    int64_t  row_count;
+    uint64_t bad_row_counter;
+} dvae_train_clf_plan_t;
+
+/* Host only.  ksplit_hint 0 = choose.  DVAE_E_UNSUPPORTED naming the limits for a width outside them or another operand policy;
+ * DVAE_E_BADARG for B < 1. */
+int dvae_train_clf_plan(int h1, int h2, int y_dim, int precision, int64_t B, int ksplit_hint, dvae_train_clf_plan_t* plan);
+/* One-time setup of `ws` (item table, packed weight copies from `params`); synchronises the stream once. */
+int dvae_train_clf_init(const dvae_train_clf_plan_t* plan, const float* params, void* ws, void* stream);
+/* Rebuild both packed weight copies after `params` was written from outside. */
+int dvae_train_clf_repack(const dvae_train_clf_plan_t* plan, const float* params, void* ws, void* stream);
+/* rows kernel + weight-gradient kernel: x [B, 513] (ldx), y [B, y_dim] (ldy) -- or the frame stores under a gather table.  The gradient
+ * of the mean loss is left as plan->ksplit slabs. */
+int dvae_train_clf_grads(const dvae_train_clf_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy, float bce_eps,
+                         void* stream);
+/* apply kernel: g = grad_scale * (slabs summed in slab order); Adam at `step` (1-based); packed copies; losses3 = {BCE, BCE, 0} (the
+ * generic step's three scalars with no second term); counts4 = {tp, tn, fp, fn} of the step's batch. */
+int dvae_train_clf_apply(const dvae_train_clf_plan_t* plan, float* params, float* m, float* v, void* ws, int step, double lr, double beta1,
+                         double beta2, double adam_eps, double grad_scale, float* losses3, int64_t* counts4, void* stream);
+/* dvae_train_clf_grads + dvae_train_clf_apply with grad_scale 1. */
+int dvae_train_clf_step(const dvae_train_clf_plan_t* plan, float* params, float* m, float* v, void* ws, const float* x, int64_t ldx,
+                        const float* y, int64_t ldy, float bce_eps, int step, double lr, double beta1, double beta2, double adam_eps,
+                        float* losses3, int64_t* counts4, void* stream);
+/* Forward, loss and counts only (two launches): parameters, moments and gradient slabs are left alone. */
+int dvae_train_clf_eval(const dvae_train_clf_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy, float bce_eps,
+                        float* losses3, int64_t* counts4, void* stream);
+
 /* Per-kernel device time of the last `dvae_train_*` calls made with profiling enabled:
  * enable != 0 brackets each launch with hipEvents on its stream (a few us of host cost each).
  * dvae_train_profile_read synchronises and returns accumulated ms and launch counts
