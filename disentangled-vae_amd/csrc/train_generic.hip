@@ -34,6 +34,7 @@ namespace tg {
 
 using fused::ApplyArgs;
 static void make_gemms(const GLayout& L, GGemm* G);
+constexpr int M_NT = 14, M_NG = 7;               // this step's share of the tables (G_NT / G_NG entries: train_generic.hpp)
 
 static bool dims_ok(int y, int z, int h1, int h2) {
     return y >= 0 && y <= GX && h1 >= 1 && h1 <= G_HMAX && h2 >= 1 && h2 <= G_HMAX && z >= 1 && z <= G_ZMAX;
@@ -47,10 +48,10 @@ static GLayout make_layout(int y, int z, int h1, int h2, int64_t B, int ksplit_h
     L.hm = L.h1p > L.h2p ? L.h1p : L.h2p;
     if (L.zp > L.hm) L.hm = L.zp;
     // parameters: state_dict order, 256-byte aligned
-    const int rows[G_NT] = {h1, h1, h2, h2, z, z, z, z, h2, h2, h1, h1, GX, GX};
-    const int cols[G_NT] = {GX + y, 1, h1, 1, h2, 1, h2, 1, z + y, 1, h2, 1, h1, 1};
+    const int rows[M_NT] = {h1, h1, h2, h2, z, z, z, z, h2, h2, h1, h1, GX, GX};
+    const int cols[M_NT] = {GX + y, 1, h1, 1, h2, 1, h2, 1, z + y, 1, h2, 1, h1, 1};
     int64_t o = 0;
-    for (int t = 0; t < G_NT; ++t) {
+    for (int t = 0; t < M_NT; ++t) {
         L.toff[t] = o; L.trows[t] = rows[t]; L.tcols[t] = cols[t];
         o = al64(o + (int64_t)rows[t] * cols[t]);
     }
@@ -77,10 +78,10 @@ static GLayout make_layout(int y, int z, int h1, int h2, int64_t B, int ksplit_h
     L.tiles = (B + GT - 1) / GT;
     L.Bp = L.tiles * GT;
     L.rows_grid = L.tiles < G_ROWS_GRID ? L.tiles : G_ROWS_GRID;
-    GGemm gm[G_NG];
+    GGemm gm[M_NG];
     make_gemms(L, gm);
     int row_tiles = 0;                                    // weight-gradient items of one frame slice
-    for (int i = 0; i < G_NG; ++i) row_tiles += gemm_items(gm[i]);
+    for (int i = 0; i < M_NG; ++i) row_tiles += gemm_items(gm[i]);
     choose_slices(B, row_tiles, ksplit_hint, L.slice_frames, L.nslices);
     L.n_items = row_tiles * L.nslices;
     // workspace
@@ -667,8 +668,8 @@ extern "C" int dvae_train_generic_plan(int model, int y_dim, int z_dim, int h1, 
     const GLayout L = make_layout(y_dim, z_dim, h1, h2, B, ksplit_hint);
     memset(plan, 0, sizeof(*plan));
     plan->model = model; plan->y_dim = y_dim; plan->z_dim = z_dim; plan->h1 = h1; plan->h2 = h2; plan->precision = precision;
-    plan->ksplit = L.nslices; plan->n_tensors = G_NT; plan->B = B; plan->n_params = L.n_params;
-    for (int t = 0; t < G_NT; ++t) { plan->tensor_offset[t] = L.toff[t]; plan->tensor_rows[t] = L.trows[t]; plan->tensor_cols[t] = L.tcols[t]; }
+    plan->ksplit = L.nslices; plan->n_tensors = M_NT; plan->B = B; plan->n_params = L.n_params;
+    for (int t = 0; t < M_NT; ++t) { plan->tensor_offset[t] = L.toff[t]; plan->tensor_rows[t] = L.trows[t]; plan->tensor_cols[t] = L.tcols[t]; }
     plan->workspace_bytes = L.ws_bytes; plan->grad_offset_bytes = L.o_grads; plan->Bp = L.Bp; plan->rows_grid = L.rows_grid;
     plan->slice_frames = L.slice_frames; plan->wgrad_items = L.n_items; plan->lds_bytes = L.lds_bytes;
     return 0;
@@ -689,10 +690,10 @@ extern "C" int dvae_train_generic_init(const dvae_train_generic_plan_t* plan, co
     if (int rc = plan_layout("train_generic_init", plan, L)) return rc;
     DVAE_CHECK_ARG(params && ws, "train_generic_init: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    GGemm gm[G_NG];
+    GGemm gm[M_NG];
     make_gemms(L, gm);
-    const int order[G_NG] = {0, 6, 4, 1, 5, 2, 3};                         // the widest inputs first: their items run longest
-    const std::vector<GItem> items = make_items(gm, order, G_NG, L.nslices);
+    const int order[M_NG] = {0, 6, 4, 1, 5, 2, 3};                         // the widest inputs first: their items run longest
+    const std::vector<GItem> items = make_items(gm, order, M_NG, L.nslices);
     DVAE_CHECK_ARG((int)items.size() == L.n_items, "train_generic_init: %d items for a table of %d", (int)items.size(), L.n_items);
     DVAE_HIP(hipMemcpyAsync((char*)ws + L.o_items, items.data(), items.size() * sizeof(GItem), hipMemcpyHostToDevice, s));
     DVAE_HIP(hipMemsetAsync((char*)ws + L.o_partials, 0, (size_t)L.rows_grid * 4 * sizeof(double), s));

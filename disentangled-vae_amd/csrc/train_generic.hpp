@@ -1,7 +1,8 @@
 // What the fused train steps of any covered size share (train_generic.hip: the M1 / M2 step, dvae_train_generic_*; train_classifier.hip:
-// the label classifier's step, dvae_train_clf_*; include/dvae_train.h): the packed weight copies in fragment order and the product that
-// reads them, the tables the weight-gradient and optimizer launches read, and the launches of those two kernels, which live in
-// train_generic.hip and serve both steps.  Below them: the plain structs of the M1 / M2 step alone.
+// the label classifier's step, dvae_train_clf_*; train_info.hip: the M2_info step, dvae_train_info_*; include/dvae_train.h): the packed
+// weight copies in fragment order and the product that reads them, the tables the weight-gradient and optimizer launches read, and the
+// launches of those two kernels, which live in train_generic.hip and serve all three steps.  Below them: the plain structs of the
+// M1 / M2 step alone.
 #pragma once
 #include <stdint.h>
 #include <vector>
@@ -14,7 +15,8 @@ namespace tg {
 constexpr int GT = 16;                          // frames per tile
 constexpr int GX = 513, GXP = 528, GKX = GXP / 16;
 constexpr int G_HMAX = 512, G_ZMAX = 128;       // the limits of dvae_mcem_plan_dims / mlp_generic.hip
-constexpr int G_NT = 14, G_NG = 7;              // tensors (state_dict order), weight matrices: the sizes of the tables (a step may use fewer)
+constexpr int G_NT = 26, G_NG = 13;             // tensors (state_dict order), weight matrices: the sizes of the tables (M2_info fills them: train_info.hip; M1 / M2 use 14 / 7, the classifier 6 / 3)
+constexpr int G_KERNARG_MAX = 4096;             // bytes the runtime takes as the arguments of one kernel
 constexpr int G_ROWS_GRID = 256, G_MAX_SLICES = 16;   // one rows workgroup per compute unit, the other tiles strided over; slabs the apply kernel sums
 
 inline int up16(int v) { return (v + 15) / 16 * 16; }
@@ -127,6 +129,8 @@ struct GApplyArgs {
     const long long* cnt_partials; int cnt_wgs;
     long long* counts4; long long* cnt_accum;
 };
+
+static_assert(sizeof(GWgradArgs) <= G_KERNARG_MAX && sizeof(GApplyArgs) <= G_KERNARG_MAX, "the tables travel as kernel arguments");
 
 // the two launches, for a caller that has filled the tables (unused entries zeroed): n_items workgroups; one thread a parameter of
 // g.a.n_params (0: one workgroup that only finalises)

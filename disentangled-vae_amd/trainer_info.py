@@ -1,0 +1,305 @@
+"""Fused train step for M2_info models of any covered size (include/dvae_train.h: dvae_train_info_*; csrc/train_info.hip): the loop
+body of scripts/training_M2_info_vad.py:159-198 on DeepGenerativeModel_v5 -- encoder on x, decoder on [z | y], a relu classifier on x, an
+adversarial auxiliary relu classifier on z; enc_loss = ELBO + alpha BCE(clf(x), y) - beta BCE(aux(z), y), aux_loss = gamma BCE(aux(z), y),
+the auxiliary net stepped with (gamma - beta) dBCE, one Adam update over all 26 tensors -- in three HIP launches per step whatever the
+geometry: x 513, y_dim 1..513, hidden widths 1..512, z_dim 1..128, exact fp32, one GPU.
+
+`InfoTrainer` offers the surface of `trainer_generic.GenericTrainer` where it has meaning here; `make_info_trainer` chooses between it and
+the resident `trainer.Trainer("M2_info", ...)`, which stays the default at the reference geometry and is the only home of the 16-bit
+operand policies and of data-parallel training.  PyTorch is plumbing: it owns the buffers and the stream, and draws the reparametrisation
+noise when none is passed.  No fallback: a geometry outside the limits raises with the limits named, before anything touches the device.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import native as N
+from .trainer import INFO_NAMES, MAXT, Trainer, supported
+
+LIMITS = ("the generic M2_info train step covers DeepGenerativeModel_v5 at x_dim 513, y_dim 1..513, two hidden widths 1..512, z_dim 1..128, "
+          "precision fp32, one GPU")
+
+
+class InfoPlan(ctypes.Structure):
+    _fields_ = [("y_dim", ctypes.c_int32), ("z_dim", ctypes.c_int32), ("h1", ctypes.c_int32), ("h2", ctypes.c_int32), ("ksplit", ctypes.c_int32),
+                ("n_tensors", ctypes.c_int32), ("launches_per_step", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("B", ctypes.c_int64),
+                ("n_params", ctypes.c_int64), ("tensor_offset", ctypes.c_int64 * MAXT), ("tensor_rows", ctypes.c_int32 * MAXT),
+                ("tensor_cols", ctypes.c_int32 * MAXT), ("workspace_bytes", ctypes.c_int64), ("grad_offset_bytes", ctypes.c_int64),
+                ("Bp", ctypes.c_int64), ("rows_grid", ctypes.c_int64), ("slice_frames", ctypes.c_int64), ("wgrad_items", ctypes.c_int64),
+                ("lds_bytes", ctypes.c_int64), ("info_alpha", ctypes.c_double), ("info_beta", ctypes.c_double), ("info_gamma", ctypes.c_double),
+                ("loss_accum", ctypes.c_uint64), ("row_index", ctypes.c_uint64), ("row_count", ctypes.c_int64), ("bad_row_counter", ctypes.c_uint64)]
+
+
+def covered(dims):
+    """The geometry limits (host logic only)."""
+    try:
+        h = tuple(dims.get("h_dim", ()))
+        return (dims.get("x_dim") == 513 and len(h) == 2 and all(1 <= int(v) <= 512 for v in h) and 1 <= int(dims.get("z_dim", 0)) <= 128
+                and 1 <= int(dims.get("y_dim", 0) or 0) <= 513)
+    except (TypeError, ValueError):
+        return False
+
+
+def make_plan(dims, batch, ksplit=0):
+    """dvae_train_info_plan for (dims, batch): host only.  Raises NotImplementedError / ValueError with the library's message."""
+    lib = N.load()
+    h = tuple(dims.get("h_dim", ()))
+    if dims.get("x_dim") != 513 or len(h) != 2:
+        raise NotImplementedError(f"{LIMITS}; got {dims}")
+    plan = InfoPlan()
+    rc = lib.dvae_train_info_plan(int(dims.get("y_dim", 0) or 0), int(dims["z_dim"]), int(h[0]), int(h[1]), int(batch), int(ksplit), ctypes.byref(plan))
+    if rc != 0:
+        msg = lib.dvae_last_error().decode("utf-8", "replace")
+        raise (NotImplementedError if rc == 1003 else ValueError)(f"{msg} (got {dims})")
+    return plan
+
+
+class InfoTrainer:
+    """One object = one M2_info replica on one GPU.  step(x, y, eps_noise) enqueues one full train step and returns the device tensor
+    [ELBO, recon, KL, enc_loss, classif_loss, aux_loss, aux_enc_loss, 0] (no host sync)."""
+
+    model = "M2_info"
+
+    def __init__(self, dims, params=None, batch=128, device="cuda:0", lr=1e-4, betas=(0.9, 0.999), adam_eps=1e-8, elbo_eps=1e-8,
+                 alpha=0.0, beta=10.0, gamma=1.0, seed=None, ksplit=0, share=None):
+        self.plan = make_plan(dims, batch, ksplit)          # refuses before anything touches the device
+        self.plan.info_alpha, self.plan.info_beta, self.plan.info_gamma = float(alpha), float(beta), float(gamma)
+        if not torch.cuda.is_available():
+            raise RuntimeError("InfoTrainer needs the MI355X HIP path (no CPU fallback)")
+        self.lib = N.load()
+        self.dims, self.B = dict(dims), int(batch)
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.precision, self.world, self.ksplit = "fp32", 1, int(ksplit)
+        self.lr, self.betas, self.adam_eps, self.elbo_eps = lr, betas, adam_eps, elbo_eps
+        self.alpha, self.beta, self.gamma = float(alpha), float(beta), float(gamma)
+        self.y_dim, self.z_dim, self.h_dim = self.plan.y_dim, self.plan.z_dim, (self.plan.h1, self.plan.h2)
+        self.names = INFO_NAMES
+        P = self.plan.n_params
+        with torch.cuda.device(self.device):
+            if share is None:
+                self._params = torch.zeros(P, dtype=torch.float32, device=self.device)
+                self._m = torch.zeros(P, dtype=torch.float32, device=self.device)
+                self._v = torch.zeros(P, dtype=torch.float32, device=self.device)
+                self._shared = {"step_count": 0, "version": 0}
+            else:                       # same parameters / Adam state, another batch size (see fork())
+                self._params, self._m, self._v, self._shared = share._params, share._m, share._v, share._shared
+            self.ws = torch.empty(self.plan.workspace_bytes, dtype=torch.uint8, device=self.device)
+            self.losses = torch.zeros(8, dtype=torch.float32, device=self.device)
+            self.bad_rows = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.plan.bad_row_counter = self.bad_rows.data_ptr()
+        self.seed = int(seed) if seed is not None else (share.seed if share is not None else int(torch.initial_seed()))
+        self._copy_version = self._shared["version"]
+        if share is None:
+            if params is None:
+                params = self._reference_init(seed)
+            self._write_params(params)
+        with torch.cuda.device(self.device):
+            N.check(self.lib.dvae_train_info_init(ctypes.byref(self.plan), N.ptr(self._params), N.ptr(self.ws), N.stream()), "dvae_train_info_init")
+
+    # ---- shared state ----
+    params = property(lambda self: self._params)
+    m = property(lambda self: self._m)
+    v = property(lambda self: self._v)
+
+    @property
+    def step_count(self):
+        return self._shared["step_count"]
+
+    @step_count.setter
+    def step_count(self, v):
+        self._shared["step_count"] = v
+
+    def fork(self, batch):
+        """A trainer for another batch size over the SAME parameters and Adam moments (the last, shorter batch of an epoch, the
+        validation batch size).  Each trainer has its own packed weight copies; they are rebuilt when the other one has stepped."""
+        return InfoTrainer(self.dims, batch=batch, device=self.device, lr=self.lr, betas=self.betas, adam_eps=self.adam_eps,
+                           elbo_eps=self.elbo_eps, alpha=self.alpha, beta=self.beta, gamma=self.gamma, ksplit=self.ksplit, share=self)
+
+    def _repack(self):
+        with torch.cuda.device(self.device):
+            N.check(self.lib.dvae_train_info_repack(ctypes.byref(self.plan), N.ptr(self._params), N.ptr(self.ws), N.stream()),
+                    "dvae_train_info_repack")
+        self._copy_version = self._shared["version"]
+
+    def _sync_copies(self):
+        if self._copy_version != self._shared["version"]:
+            self._repack()
+
+    # ---- parameters under the reference's state_dict names ----
+    def _reference_init(self, seed):
+        """xavier_normal_ weights / zero bias drawn exactly like synth.build_model("M2_info", dims) constructs them."""
+        from .synth import build_model
+        if seed is not None:
+            torch.manual_seed(seed)
+        m = build_model("M2_info", dict(self.dims, y_dim=self.y_dim))
+        return {k: v.detach() for k, v in m.state_dict().items()}
+
+    def tensor_view(self, i):
+        o, r, c = self.plan.tensor_offset[i], self.plan.tensor_rows[i], self.plan.tensor_cols[i]
+        v = self._params[o:o + r * c]
+        return v.view(r, c) if self.names[i].endswith("weight") else v
+
+    def _write_params(self, sd, strict=True):
+        unknown = [k for k in sd if k not in self.names]
+        if strict and unknown:
+            raise KeyError(f"unexpected keys in state_dict: {unknown[:4]}")
+        for i, name in enumerate(self.names):
+            if name not in sd:
+                if strict:
+                    raise KeyError(f"missing key in state_dict: {name}")
+                continue
+            t = sd[name]
+            t = torch.from_numpy(np.array(t)) if isinstance(t, np.ndarray) else t.detach()      # (a copy: the caller's array may be read-only)
+            view = self.tensor_view(i)
+            if tuple(t.shape) != tuple(view.shape):
+                raise ValueError(f"{name}: shape {tuple(t.shape)} != {tuple(view.shape)}")
+            view.copy_(t.to(torch.float32))
+
+    def load_state_dict(self, sd, strict=True):
+        """strict=False overwrites only the tensors present (the pretrain flow of scripts/training_M2_info_vad_pretrain.py:102-112, e.g.
+        ClassifierTrainer.state_dict(prefix="enc_dec_clf.classifier."))."""
+        self._write_params(sd, strict)
+        self._shared["version"] += 1
+        self._repack()
+
+    def state_dict(self):
+        return {name: self.tensor_view(i).clone() for i, name in enumerate(self.names)}
+
+    def state_dict_numpy(self):
+        return {k: v.cpu().numpy() for k, v in self.state_dict().items()}
+
+    def losses_host(self):
+        """The last step's eight loss scalars on the host (synchronises)."""
+        return self.losses.cpu().numpy().copy()
+
+    def grads_numpy(self):
+        """Gradient of the last step per tensor, as numpy: the frame-slice slabs summed in slab order, as the apply kernel sums them.
+        The auxiliary tensors hold (gamma - beta) dBCE, what the script's second optimizer steps with, as on the resident trainer."""
+        P, ks, go = self.plan.n_params, self.plan.ksplit, self.plan.grad_offset_bytes
+        slabs = self.ws[go:go + 4 * P * ks].view(torch.float32).view(ks, P)
+        flat = slabs[0].clone()
+        for k in range(1, ks):
+            flat += slabs[k]
+        flat = flat.cpu().numpy()
+        out = {}
+        for i, name in enumerate(self.names):
+            o, r, c = self.plan.tensor_offset[i], self.plan.tensor_rows[i], self.plan.tensor_cols[i]
+            g = flat[o:o + r * c].copy()
+            out[name] = g.reshape(r, c) if name.endswith("weight") else g
+        return out
+
+    # ---- one train step ----
+    def _check_inputs(self, x, y, rows, eps_noise):
+        """rows=None: x [B, 513], y [B, y_dim] are the batch.  rows = int64 CUDA tensor [B]: x / y are a whole frame store and frame b
+        of the step is row rows[b], gathered inside the kernels: no copy."""
+        B = self.B
+        n = B if rows is None else x.shape[0]
+        if x.ndim != 2 or x.shape != (n, 513) or x.dtype != torch.float32 or x.device != self.device or n < 1:
+            raise ValueError(f"x must be a float32 tensor [{n if rows is not None else B}, 513] on {self.device}")
+        if y is None or y.shape != (n, self.y_dim) or y.dtype != torch.float32 or y.device != self.device:
+            raise ValueError(f"y must be a float32 tensor [{n}, {self.y_dim}] on {self.device}")
+        if eps_noise is not None and (eps_noise.shape != (B, self.z_dim) or eps_noise.dtype != torch.float32 or eps_noise.device != self.device):
+            raise ValueError(f"eps_noise must be a float32 tensor [{B}, {self.z_dim}] on {self.device}")
+        if rows is not None and not (rows.device == self.device and rows.dtype == torch.int64 and rows.shape == (B,) and rows.is_contiguous()):
+            raise ValueError(f"rows must be a contiguous int64 tensor [{B}] on {self.device}")
+        self.plan.row_index = 0 if rows is None else rows.data_ptr()
+        self.plan.row_count = 0 if rows is None else n
+
+    def bad_row_count(self):
+        """Gather indices outside the frame store seen since the last call (synchronises); the affected frames were trained on row 0
+        instead.  No kernel reads memory through such an index."""
+        n = int(self.bad_rows.item())
+        if n:
+            self.bad_rows.zero_()
+        return n
+
+    def noise(self, step):
+        """The [B, z_dim] noise step() / evaluate() use when none is passed: torch.randn on the device from a generator seeded with
+        (seed, step); the k-th evaluate() without noise draws noise(2**40 + k)."""
+        g = torch.Generator(device=self.device).manual_seed((self.seed * 0x9E3779B97F4A7C15 + int(step)) & 0x7FFFFFFFFFFFFFFF)
+        return torch.randn((self.B, self.z_dim), generator=g, device=self.device, dtype=torch.float32)
+
+    @staticmethod
+    def _inputs(x, y, eps_noise):
+        return (x if x.stride(1) == 1 else x.contiguous()), (y if y.stride(1) == 1 else y.contiguous()), eps_noise.contiguous()
+
+    def step(self, x, y, eps_noise=None, rows=None):
+        self._check_inputs(x, y, rows, eps_noise)
+        self._sync_copies()
+        self.step_count += 1
+        if eps_noise is None:
+            eps_noise = self.noise(self.step_count)
+        x, y, eps_noise = self._inputs(x, y, eps_noise)
+        self._shared["version"] += 1
+        self._copy_version = self._shared["version"]
+        with torch.cuda.device(self.device):
+            N.check(self.lib.dvae_train_info_step(ctypes.byref(self.plan), N.ptr(self._params), N.ptr(self._m), N.ptr(self._v), N.ptr(self.ws),
+                                                  N.ptr(x), N.ld(x), N.ptr(y), N.ld(y), N.ptr(eps_noise), self.elbo_eps, self.step_count, self.lr,
+                                                  self.betas[0], self.betas[1], self.adam_eps, N.ptr(self.losses), N.stream()),
+                    "dvae_train_info_step")
+        return self.losses
+
+    def evaluate(self, x, y, eps_noise=None, rows=None):
+        """Validation pass: the forward passes and the losses on a batch of the trainer's size, no backward, no update.  Returns a NEW
+        device tensor of the eight loss scalars."""
+        self._check_inputs(x, y, rows, eps_noise)
+        self._sync_copies()
+        if eps_noise is None:
+            self._shared["eval_count"] = self._shared.get("eval_count", 0) + 1
+            eps_noise = self.noise((1 << 40) + self._shared["eval_count"])
+        x, y, eps_noise = self._inputs(x, y, eps_noise)
+        out = torch.zeros_like(self.losses)
+        with torch.cuda.device(self.device):
+            N.check(self.lib.dvae_train_info_eval(ctypes.byref(self.plan), N.ptr(self.ws), N.ptr(x), N.ld(x), N.ptr(y), N.ld(y), N.ptr(eps_noise),
+                                                  self.elbo_eps, N.ptr(out), N.stream()), "dvae_train_info_eval")
+        return out
+
+    def grads_only(self, x, y, eps_noise, reduce=False):
+        """rows + weight-gradient kernels without the optimizer (tests / gradient inspection; read them with grads_numpy()).
+        `reduce` is accepted for the signature of Trainer.grads_only: the slabs are summed on reading either way."""
+        self._check_inputs(x, y, None, eps_noise)
+        self._sync_copies()
+        x, y, eps_noise = self._inputs(x, y, eps_noise)
+        with torch.cuda.device(self.device):
+            N.check(self.lib.dvae_train_info_grads(ctypes.byref(self.plan), N.ptr(self.ws), N.ptr(x), N.ld(x), N.ptr(y), N.ld(y), N.ptr(eps_noise),
+                                                   self.elbo_eps, N.stream()), "dvae_train_info_grads")
+
+    def accumulate_losses(self, buf):
+        """Running sums for epoch logging without a host sync per step: `buf` is a float64 CUDA tensor of 8 elements (or None to stop);
+        every step() / evaluate() adds its loss scalars to its first seven on the device."""
+        if buf is not None and not (buf.is_cuda and buf.dtype == torch.float64 and buf.numel() >= 8 and buf.is_contiguous()):
+            raise ValueError("accumulate_losses: need a contiguous float64 CUDA tensor with >= 8 elements")
+        self._accum = buf
+        self.plan.loss_accum = 0 if buf is None else buf.data_ptr()
+
+
+def info_trainer_kind(dims):
+    """Which fused train step serves M2_info at `dims`: "resident" (the hand-tuned kernels of the reference's geometry,
+    trainer.supported), "generic" (csrc/train_info.hip) or None.  Host logic only."""
+    try:
+        if supported("M2_info", dims):
+            return "resident"
+    except (KeyError, TypeError):       # a dims dict without one of the keys names no geometry of the resident step
+        pass
+    return "generic" if covered(dims) else None
+
+
+def make_info_trainer(dims, generic=False, **kw):
+    """The resident Trainer("M2_info", ...) where trainer.supported holds (the default there: the faster step, the 16-bit operand policies,
+    data-parallel training), otherwise an InfoTrainer; generic=True puts the reference geometry on the generic step too.  Raises with the
+    limits named when neither covers `dims`, and for a 16-bit policy or world != 1 on the generic step."""
+    kind = info_trainer_kind(dims)
+    if kind is None or (generic and not covered(dims)):
+        raise NotImplementedError(f"no fused M2_info train step for {dims}: the resident step covers x 513, z 16, h [128, 128], y 1; {LIMITS}")
+    if kind == "resident" and not generic:
+        return Trainer("M2_info", dims, **kw)
+    if kw.get("precision", "fp32") != "fp32":
+        raise NotImplementedError(f"precision {kw['precision']!r} exists on the resident step only; {LIMITS}")
+    if int(kw.get("world", 1)) != 1 or kw.get("process_group") is not None:
+        raise NotImplementedError(f"data-parallel training is not built on the generic step (got world={kw.get('world', 1)}); {LIMITS}")
+    for k in ("precision", "world", "process_group"):
+        kw.pop(k, None)
+    return InfoTrainer(dims, **kw)

@@ -85,18 +85,19 @@ def main():
     ap.add_argument("--score", action="store_true", help="with --synthetic (whose speech is known): SI-SDR and ESTOI of mixture and estimate per utterance")
     ap.add_argument("--snr", type=float, nargs="+", default=None, help="with --synthetic: mix every utterance with synthetic noise at each of "
                     "these SNRs (dB) on the device instead of adding a fixed 0.2 * randn on the host")
-    ap.add_argument("--z-dim", type=int, default=16, help="latent size of the random-weight model (any 1..128: sizes other than the "
+    ap.add_argument("--z-dim", type=int, default=16, help="latent size of the model, random-weight or --checkpoint (any 1..128: sizes other than the "
                     "reference's 16 / 128 / 128 run the generic fp32 kernels -- chain, encoder of --fused-start, classifier of --labels classifier)")
-    ap.add_argument("--h-dim", type=int, nargs=2, default=[128, 128], metavar=("H1", "H2"), help="hidden widths of the random-weight model (1..512 each)")
+    ap.add_argument("--h-dim", type=int, nargs=2, default=[128, 128], metavar=("H1", "H2"), help="hidden widths of the model (1..512 each); examples/train_fused.py "
+                    "--z-dim / --h-dim trains and saves such a model")
     ap.add_argument("--trim", type=int, default=800, help="samples cut at both ends before scoring (run_metrics.py:117-121: 0.05 s)")
     a = ap.parse_args()
     if a.score and (a.wav or not a.synthetic):
         ap.error("--score needs the clean speech, which only --synthetic mixtures come with")
     if a.snr is not None and (a.wav or not a.synthetic):
         ap.error("--snr mixes the --synthetic utterances")
-    if (a.z_dim, list(a.h_dim)) != (16, [128, 128]) and (a.checkpoint or a.precision != "fp32"):
-        ap.error("--z-dim / --h-dim size the random-weight model: fp32 and no --checkpoint (other sizes run the generic fp32 kernels: "
-                 "mcem.chain_kind, encode.encoder_kind, classify.classifier_kind)")
+    if (a.z_dim, list(a.h_dim)) != (16, [128, 128]) and a.precision != "fp32":
+        ap.error("--z-dim / --h-dim: sizes other than 16 / 128 128 run the generic kernels, which are fp32 (mcem.chain_kind, "
+                 "encode.encoder_kind, classify.classifier_kind)")
     names, waves, clean = [], [], []
     for p in a.wav:
         fs, w = wavfile.read(p)

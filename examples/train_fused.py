@@ -1,11 +1,13 @@
 """The reference's training loop (scripts/training_M1.py / training_M2.py / training_M2_info_vad.py: epochs of train batches, a validation pass,
 one checkpoint per epoch named `<M>_epoch_{:03d}_vloss_{:.2f}.pt`, the same two log files) on the MI355X-native path:
 GPU-resident frame store (disentangled-vae_amd/frames.py) + fused train step (disentangled-vae_amd/trainer.py: make_trainer -- the resident
-step at the reference's z 16 / h 128 128, the generic step of trainer_generic.py at any other covered size).
+step at the reference's z 16 / h 128 128, the generic step of trainer_generic.py at any other covered size; M2_info through
+trainer_info.py: make_info_trainer, the same choice for DeepGenerativeModel_v5).
 
     python examples/train_fused.py --model M2 --labels ibm_labels --h5 data/complete/processed/ntcd_timit/Clean_ibm_labels_upsampled.h5
     python examples/train_fused.py --model M2 --synthetic 200000            # no dataset at hand
     python examples/train_fused.py --model M2 --synthetic 200000 --y-dim 1 --z-dim 32 --h-dim 256 64      # the model examples/enhance_mcem.py takes
+    python examples/train_fused.py --model M2_info --synthetic 200000 --z-dim 32 --h-dim 256 64            # ... with --labels classifier
 
 Checkpoints are plain state_dicts with the reference's keys: the reference's evaluate / reconstruct scripts load them.
 Differences from the scripts, all deliberate: the batch size is a flag (the fused step is meant for thousands of
@@ -22,6 +24,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 make_trainer = importlib.import_module("disentangled-vae_amd.trainer").make_trainer
+make_info_trainer = importlib.import_module("disentangled-vae_amd.trainer_info").make_info_trainer
 DeviceFrames = importlib.import_module("disentangled-vae_amd.frames").DeviceFrames
 
 
@@ -64,14 +67,17 @@ def main():
     ap.add_argument("--precision", choices=["fp32", "bf16"], default="fp32")
     ap.add_argument("--z-dim", type=int, default=16, help="latent width (1..128)")
     ap.add_argument("--h-dim", type=int, nargs=2, default=[128, 128], metavar=("H1", "H2"), help="hidden widths (1..512)")
-    ap.add_argument("--y-dim", type=int, default=None, help="label width of M2 on synthetic data (1..513; default: what --labels gives)")
+    ap.add_argument("--y-dim", type=int, default=None, help="label width of M2 / M2_info on synthetic data (1..513; default: what --labels gives)")
+    ap.add_argument("--alpha", type=float, default=0.0, help="M2_info: weight of BCE(classifier(x), y) in enc_loss")
+    ap.add_argument("--beta", type=float, default=10.0, help="M2_info: weight of the adversarial -BCE(auxiliary(z), y) in enc_loss")
+    ap.add_argument("--gamma", type=float, default=1.0, help="M2_info: weight of aux_loss = BCE(auxiliary(z.detach()), y)")
     ap.add_argument("--out", default="models/fused_run")
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
     if a.model == "M2_info":
         a.labels = "vad_labels"                     # scripts/training_M2_info_vad.py: VAD labels, alpha 0 / beta 10 / gamma 1
     y_dim = 0 if a.model == "M1" else (1 if a.labels == "vad_labels" else 513)
-    if a.y_dim is not None and a.model == "M2":
+    if a.y_dim is not None and a.model != "M1":
         if a.h5:
             ap.error("--y-dim applies to --synthetic data; with --h5 the label file decides")
         y_dim = a.y_dim
@@ -83,7 +89,11 @@ def main():
     if a.model == "M1":
         train.y = valid.y = None
     dims = dict(x_dim=513, y_dim=y_dim, z_dim=a.z_dim, h_dim=tuple(a.h_dim))
-    tr = make_trainer(a.model, dims, batch=min(a.batch, len(train)), precision=a.precision, lr=a.lr, seed=a.seed)
+    kw = dict(batch=min(a.batch, len(train)), precision=a.precision, lr=a.lr, seed=a.seed)
+    if a.model == "M2_info":                        # the resident step at the reference geometry, csrc/train_info.hip at any other covered size
+        tr = make_info_trainer(dims, alpha=a.alpha, beta=a.beta, gamma=a.gamma, **kw)
+    else:
+        tr = make_trainer(a.model, dims, **kw)
     tv = tr.fork(min(a.batch, len(valid)))
     train_trainers, valid_trainers = [tr], [tv]
     os.makedirs(a.out, exist_ok=True)

@@ -295,6 +295,70 @@ int dvae_train_clf_step(const dvae_train_clf_plan_t* plan, float* params, float*
 int dvae_train_clf_eval(const dvae_train_clf_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy, float bce_eps,
                         float* losses3, int64_t* counts4, void* stream);
 
+/* ---- the fused train step for M2_info of ANY covered size (csrc/train_info.hip): DeepGenerativeModel_v5 of packages/models/models.py:390-444
+ * -- encoder on x alone, decoder on [z | y], a relu classifier on x, an adversarial auxiliary relu classifier on z -- under the loop body of
+ * scripts/training_M2_info_vad.py:159-198.  x 513, y_dim 1..513, hidden widths h1 / h2 1..512, z_dim 1..128, exact fp32, one GPU.  THREE
+ * launches per step whatever the geometry and the batch: rows kernel (the four forward passes, the loss terms, every backward-data chain,
+ * the stash), then the weight-gradient and apply kernels of the generic step above on this step's tables (thirteen matrices, 26 tensors).
+ * Contract:
+ *   enc_loss = ELBO + alpha BCE(clf(x), y) - beta BCE(aux(z), y): its gradient goes into every enc_dec_clf tensor, the -beta term through
+ *              z into the encoder; aux_loss = gamma BCE(aux(z.detach()), y); the auxiliary tensors receive (gamma - beta) dBCE (the
+ *              script never zeroes what enc_loss.backward() leaves in them); the auxiliary pre-activation gradients are formed once at
+ *              unit weight, so beta = 0 divides nothing; the eps inside the BCE logs is elbo_eps, as in the script;
+ *   one Adam update over all 26 tensors at the same step count (the script's two optimizers share their hyper-parameters);
+ *   losses8 = {ELBO, recon, KL, enc_loss, classif_loss, aux_loss, aux_enc_loss, 0}, means over the B frames (the order of dvae_train_apply);
+ *   the same inputs give the same bits (no atomics on floats; slabs and partial sums in a fixed order);
+ *   26 tensors in DeepGenerativeModel_v5.state_dict() order, each at a 256-byte aligned offset of the flat buffers. */
+typedef struct {
+    /* inputs (echoed) */
+    int32_t y_dim, z_dim, h1, h2;
+    int32_t ksplit;              /* frame slices of the weight-gradient reduction = slabs the apply kernel sums (at most 16) */
+    int32_t n_tensors;           /* 26 */
+    int32_t launches_per_step;   /* 3, whatever the geometry and B */
+    int32_t reserved0;
+    int64_t B;                   /* frames per step */
+    int64_t n_params;            /* flat length in floats (with alignment gaps) */
+    int64_t tensor_offset[DVAE_TRAIN_MAX_TENSORS];      /* in floats */
+    int32_t tensor_rows[DVAE_TRAIN_MAX_TENSORS];
+    int32_t tensor_cols[DVAE_TRAIN_MAX_TENSORS];        /* 1 for biases */
+    int64_t workspace_bytes;
+    int64_t grad_offset_bytes;   /* ws + this = ksplit slabs of n_params floats; the auxiliary tensors hold (gamma - beta) dBCE */
+    int64_t Bp;                  /* frames padded to whole 16-frame tiles */
+    int64_t rows_grid;           /* workgroups of the rows kernel (tiles beyond it are strided over) */
+    int64_t slice_frames;        /* frames of a slice (a multiple of 16; the last slice may be shorter) */
+    int64_t wgrad_items;         /* workgroups of the weight-gradient launch */
+    int64_t lds_bytes;           /* dynamic LDS of the rows kernel (at most 160 KB at every geometry within the limits) */
+    /* loss weights: dvae_train_info_plan sets the script's defaults (0, 10, 1); the caller may overwrite them before dvae_train_info_init */
+    double  info_alpha, info_beta, info_gamma;
+    /* set by the caller between calls, as in dvae_train_generic_plan_t: float64 running sums (8 doubles) or 0; the gather table, the rows
+       of the frame store and the int32 counter of refused indices or 0 */
+    uint64_t loss_accum;
+    uint64_t row_index;
+    int64_t  row_count;
+    uint64_t bad_row_counter;
+} dvae_train_info_plan_t;
+
+/* Host only (callable without a GPU).  ksplit_hint 0 = choose.  DVAE_E_BADARG naming the limits for a size outside them. */
+int dvae_train_info_plan(int y_dim, int z_dim, int h1, int h2, int64_t B, int ksplit_hint, dvae_train_info_plan_t* plan);
+/* One-time setup of `ws` (item table, packed weight copies from `params`); synchronises the stream once. */
+int dvae_train_info_init(const dvae_train_info_plan_t* plan, const float* params, void* ws, void* stream);
+/* Rebuild both packed weight copies after `params` was written from outside. */
+int dvae_train_info_repack(const dvae_train_info_plan_t* plan, const float* params, void* ws, void* stream);
+/* rows kernel + weight-gradient kernel: x [B, 513] (ldx), y [B, y_dim] (ldy) -- or the frame stores under a gather table --, eps_noise
+ * [B, z_dim] (required).  The gradients are left as plan->ksplit slabs. */
+int dvae_train_info_grads(const dvae_train_info_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
+                          const float* eps_noise, float elbo_eps, void* stream);
+/* apply kernel: g = grad_scale * (slabs summed in slab order); Adam at `step` (1-based); packed copies; losses8. */
+int dvae_train_info_apply(const dvae_train_info_plan_t* plan, float* params, float* m, float* v, void* ws, int step, double lr, double beta1,
+                          double beta2, double adam_eps, double grad_scale, float* losses8, void* stream);
+/* dvae_train_info_grads + dvae_train_info_apply with grad_scale 1. */
+int dvae_train_info_step(const dvae_train_info_plan_t* plan, float* params, float* m, float* v, void* ws, const float* x, int64_t ldx,
+                         const float* y, int64_t ldy, const float* eps_noise, float elbo_eps, int step, double lr, double beta1, double beta2,
+                         double adam_eps, float* losses8, void* stream);
+/* Forward and losses only (two launches): parameters, moments and gradient slabs are left alone. */
+int dvae_train_info_eval(const dvae_train_info_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
+                         const float* eps_noise, float elbo_eps, float* losses8, void* stream);
+
 /* Per-kernel device time of the last `dvae_train_*` calls made with profiling enabled:
  * enable != 0 brackets each launch with hipEvents on its stream (a few us of host cost each).
  * dvae_train_profile_read synchronises and returns accumulated ms and launch counts
