@@ -520,6 +520,7 @@ __global__ __launch_bounds__(256) void train_generic_apply_kernel(const GApplyAr
                 if (c < d.split) g.ws[d.f0 + frag_pos(r + d.roff, c, d.kb0)] = pi;
                 else g.ws[d.f1 + frag_pos(r + d.roff, c - d.split, d.kb1)] = pi;
                 if (d.t0 >= 0 && c < d.tcmax) g.ws[d.t0 + frag_pos(c, r + d.tkoff, d.tkb)] = pi;
+                if (d.tkb1 > 0 && c >= d.split) g.ws[d.t1 + frag_pos(c - d.split, r, d.tkb1)] = pi;
             }
         }
     }
@@ -530,6 +531,21 @@ __global__ __launch_bounds__(256) void train_generic_apply_kernel(const GApplyAr
             for (int i = 0; i < g.cnt_wgs; ++i) c += g.cnt_partials[4 * (int64_t)i + threadIdx.x];
             g.counts4[threadIdx.x] = c;
             if (g.cnt_accum) g.cnt_accum[threadIdx.x] += c;
+        }
+        if (g.v_partials) {                                 // one partial a thread: workgroup order within a wave's sum, waves in order
+            static_assert(G_ROWS_GRID <= 256, "one thread of the finalising workgroup per rows workgroup");
+            __syncthreads();                                // write_losses has read `red`
+            double v = (int)threadIdx.x < g.a.npartials ? g.v_partials[threadIdx.x] : 0.0;
+            v = wave_sum(v);
+            if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][0] = v;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                const float bv = (float)((red[0][0] + red[1][0] + red[2][0] + red[3][0]) / (double)g.a.B);
+                const float aux_enc = g.a.beta * bv;
+                g.a.losses3[3] = g.a.losses3[0] + g.a.losses3[4] - aux_enc;      // enc_loss = ELBO + classif_loss - beta V
+                g.a.losses3[6] = aux_enc;
+                if (g.v_accum) for (int q = 0; q < 8; ++q) g.v_accum[q] += (double)g.a.losses3[q];
+            }
         }
     }
 }

@@ -66,6 +66,8 @@ struct GTensor {
     int32_t kb0, kb1, split, roff;  // row r -> r + roff
     int64_t t0;                     // transposed copy, -1 = none: element (r, c < tcmax) -> row c, input r + tkoff
     int32_t tkb, tkoff, tcmax, bias;
+    int64_t t1;                     // transposed copy of the columns >= split, tkb1 = 0: none: element (r, c) -> row c - split, input r
+    int32_t tkb1, pad1;
 };
 
 // one weight matrix of the weight-gradient launch: dW = dPre^T [in | y] and db = dPre^T 1 over the frames
@@ -120,7 +122,10 @@ struct GWgradArgs {
 };
 
 // apply kernel (train_generic.hip: train_generic_apply_kernel): optimizer step, both packed copies, loss scalars; with `cnt_partials`
-// also the confusion counts of the classifier step: [cnt_wgs][4] integers summed in workgroup order into counts4 (and added to cnt_accum)
+// also the confusion counts of the classifier step: [cnt_wgs][4] integers summed in workgroup order into counts4 (and added to cnt_accum);
+// with `v_partials` (the M2_info step whose adversarial term is not a cross entropy, train_info.hip) a fifth loss sum per rows workgroup
+// (a.npartials <= G_ROWS_GRID of them): aux_enc_loss = beta V replaces beta BCE in the loss scalars, and the running sums go to v_accum
+// (a.accum is then null)
 struct GApplyArgs {
     fused::ApplyArgs a;
     GTensor t[G_NT];
@@ -128,6 +133,7 @@ struct GApplyArgs {
     int adam, finalize;
     const long long* cnt_partials; int cnt_wgs;
     long long* counts4; long long* cnt_accum;
+    const double* v_partials; double* v_accum;
 };
 
 static_assert(sizeof(GWgradArgs) <= G_KERNARG_MAX && sizeof(GApplyArgs) <= G_KERNARG_MAX, "the tables travel as kernel arguments");

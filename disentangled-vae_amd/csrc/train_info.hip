@@ -33,6 +33,12 @@
 //   * apply kernel: slab sums in slab order, adam_element, both packed copies, the eight loss scalars of the resident step
 //     (apply_common.hpp: write_losses with `info`).
 //   * 64-bit indexing throughout; a gather index outside [0, row_count) is never dereferenced (row 0 instead, counted).
+// Two options (dvae_train_info_plan_mode, known at plan time: stash and workspace depend on them) give the loop body of
+// scripts/training_M2_info_vad_pretrain.py:162-200: the decoder fed [z | clf(x)], and binary_cross_entropy_v2 / _v3 of aux(z) as the
+// encoder's adversarial term.  They are template parameters of the rows kernel (see there); the instantiation <false, 0> is the step
+// above, statement for statement.  LDS is the same at every mode: p_c lives in the label tile Y, and the labels are read again through
+// the gather table where a later phase needs them.  The weight-gradient launch reads [z | p_c] of decoder layer 1 from the stash, where
+// the rows kernel lays them side by side; the apply kernel keeps one more packed copy, the label block of that layer transposed.
 #include <math.h>
 #include <vector>
 #include "common.hpp"
@@ -56,10 +62,13 @@ struct ILayout {
     int64_t C1, C2, Co, CoT, C2T;                                        // classifier on x
     int64_t A1, A2, Ao, AoT, A2T, A1T;                                   // auxiliary net on z
     int64_t b1, b2, bh, bd1, bd2, bd3, bc1, bc2, bco, ba1, ba2, bao;     // zero-padded biases
+    int64_t D1yT;                                                        // the label block of decoder layer 1, transposed (dec_label "classifier" only)
     int64_t wpack_elems;
     // the stash of one frame (floats): layer inputs, then the pre-activation gradients
     int S, s_h1e, s_h2e, s_z, s_d1, s_d2, s_pe1, s_pe2, s_ph, s_pd1, s_pd2, s_da;
     int s_c1, s_c2, s_pc1, s_pc2, s_pco, s_a1, s_a2, s_pa1, s_pa2, s_pao;
+    int s_zc;                                                            // [z | p_c], the input of decoder layer 1 (dec_label "classifier" only)
+    int mode;                                                            // DVAE_INFO_* bits
     int64_t o_items, o_partials, o_stash, o_grads, ws_bytes;             // workspace (bytes)
     int64_t B, Bp, tiles, rows_grid, slice_frames, n_params;
     int nslices, n_items;
@@ -67,6 +76,9 @@ struct ILayout {
     int64_t toff[I_NT];
     int trows[I_NT], tcols[I_NT];
 };
+
+constexpr int MODE_AUX = DVAE_INFO_AUX_UNIFORM | DVAE_INFO_AUX_ENTROPY, MODE_ALL = DVAE_INFO_DEC_CLASSIFIER | MODE_AUX;
+static bool mode_ok(int mode) { return (mode & ~MODE_ALL) == 0 && (mode & MODE_AUX) != MODE_AUX; }
 
 static bool dims_ok(int y, int z, int h1, int h2) {
     return y >= 1 && y <= GX && h1 >= 1 && h1 <= G_HMAX && h2 >= 1 && h2 <= G_HMAX && z >= 1 && z <= G_ZMAX;
@@ -83,7 +95,8 @@ static void make_gemms(const ILayout& L, GGemm* G) {
     set(1, L.s_pe2, L.h2p / 16, L.h2, 1, L.s_h1e, L.h1, 0);
     set(2, L.s_ph, L.zp / 16, L.z, 1, L.s_h2e, L.h2, 0);
     set(3, L.s_ph + L.zp, L.zp / 16, L.z, 1, L.s_h2e, L.h2, 0);
-    set(4, L.s_pd1, L.h2p / 16, L.h2, 1, L.s_z, L.z, L.y);
+    if (L.mode & DVAE_INFO_DEC_CLASSIFIER) set(4, L.s_pd1, L.h2p / 16, L.h2, 1, L.s_zc, L.z + L.y, 0);      // [z | p_c] lies in the stash
+    else set(4, L.s_pd1, L.h2p / 16, L.h2, 1, L.s_z, L.z, L.y);
     set(5, L.s_pd2, L.h1p / 16, L.h1, 1, L.s_d1, L.h2, 0);
     set(6, L.s_da, GKX, GX, 1, L.s_d2, L.h1, 0);
     set(7, L.s_pc1, L.h1p / 16, L.h1, 0, 0, GX, 0);
@@ -94,9 +107,11 @@ static void make_gemms(const ILayout& L, GGemm* G) {
     set(12, L.s_pao, L.yp / 16, L.y, 1, L.s_a2, L.h2, 0);
 }
 
-static ILayout make_layout(int y, int z, int h1, int h2, int64_t B, int ksplit_hint) {
+static ILayout make_layout(int y, int z, int h1, int h2, int64_t B, int ksplit_hint, int mode) {
     ILayout L;
     memset(&L, 0, sizeof(L));
+    L.mode = mode;
+    const bool dec_clf = (mode & DVAE_INFO_DEC_CLASSIFIER) != 0, aux_v = (mode & MODE_AUX) != 0;
     L.y = y; L.z = z; L.h1 = h1; L.h2 = h2;
     L.yp = up16(y); L.zp = up16(z); L.h1p = up16(h1); L.h2p = up16(h2);
     L.hm = L.h1p > L.h2p ? L.h1p : L.h2p;
@@ -124,6 +139,7 @@ static ILayout make_layout(int y, int z, int h1, int h2, int64_t B, int ksplit_h
     L.AoT = take((int64_t)L.h2p * L.yp); L.A2T = take((int64_t)L.h1p * L.h2p); L.A1T = take((int64_t)L.zp * L.h1p);
     L.b1 = take(L.h1p); L.b2 = take(L.h2p); L.bh = take(2 * L.zp); L.bd1 = take(L.h2p); L.bd2 = take(L.h1p); L.bd3 = take(GXP);
     L.bc1 = take(L.h1p); L.bc2 = take(L.h2p); L.bco = take(L.yp); L.ba1 = take(L.h1p); L.ba2 = take(L.h2p); L.bao = take(L.yp);
+    if (dec_clf) L.D1yT = take((int64_t)L.yp * L.h2p);
     L.wpack_elems = o;
     // the stash of a frame
     int s = 0;
@@ -132,6 +148,7 @@ static ILayout make_layout(int y, int z, int h1, int h2, int64_t B, int ksplit_h
     L.s_pe1 = col(L.h1p); L.s_pe2 = col(L.h2p); L.s_ph = col(2 * L.zp); L.s_pd1 = col(L.h2p); L.s_pd2 = col(L.h1p); L.s_da = col(GXP);
     L.s_c1 = col(L.h1p); L.s_c2 = col(L.h2p); L.s_pc1 = col(L.h1p); L.s_pc2 = col(L.h2p); L.s_pco = col(L.yp);
     L.s_a1 = col(L.h1p); L.s_a2 = col(L.h2p); L.s_pa1 = col(L.h1p); L.s_pa2 = col(L.h2p); L.s_pao = col(L.yp);
+    if (dec_clf) L.s_zc = col((L.z + L.y + 3) / 4 * 4);                   // (a multiple of 4: the 16-byte stores of the next frame stay aligned)
     L.S = s;
     // frames, tiles, slices
     L.B = B;
@@ -147,7 +164,7 @@ static ILayout make_layout(int y, int z, int h1, int h2, int64_t B, int ksplit_h
     // workspace
     int64_t w = al256(L.wpack_elems * 4);
     L.o_items = w; w = al256(w + (int64_t)L.n_items * sizeof(GItem));
-    L.o_partials = w; w = al256(w + L.rows_grid * 4 * sizeof(double));
+    L.o_partials = w; w = al256(w + L.rows_grid * (aux_v ? 5 : 4) * sizeof(double));      // the fifth sum (V) behind the [rows_grid][4]
     L.o_stash = w; w = al256(w + L.Bp * (int64_t)L.S * 4);
     L.o_grads = w; w = al256(w + (int64_t)L.nslices * L.n_params * 4);
     L.ws_bytes = w;
@@ -173,6 +190,7 @@ static void make_tensors(const ILayout& L, GTensor* T) {
     T[6].f0 = L.Wh; T[6].kb0 = k2; T[6].roff = L.zp; T[6].t0 = L.WhT; T[6].tkb = 2 * kz; T[6].tkoff = L.zp; T[6].tcmax = L.h2;
     T[7].f0 = L.bh; T[7].roff = L.zp;
     T[8].f0 = L.D1z; T[8].kb0 = kz; T[8].split = L.z; T[8].f1 = L.D1y; T[8].kb1 = ky; T[8].t0 = L.D1zT; T[8].tkb = k2; T[8].tcmax = L.z;
+    if (L.mode & DVAE_INFO_DEC_CLASSIFIER) { T[8].t1 = L.D1yT; T[8].tkb1 = k2; }
     T[9].f0 = L.bd1;
     T[10].f0 = L.D2; T[10].kb0 = k2; T[10].t0 = L.D2T; T[10].tkb = k1; T[10].tcmax = L.h2;
     T[11].f0 = L.bd2;
@@ -205,10 +223,23 @@ struct IRowsArgs {
     float clf_scale;                  // alpha / B: the weight of d BCE(clf(x), y)
     float aux_z_scale;                // -beta: the unit auxiliary gradients where they flow to z
     float aux_w_scale;                // gamma - beta: ... where they are stashed for the weight gradients
+    float aux_gamma;                  // gamma: the weight of d BCE in the auxiliary tensors when the adversarial term is not a cross entropy
+    double* partials_v;               // [rows_grid] the sums of V (then only)
     int fwd_only;
 };
 static_assert(sizeof(ILayout) + sizeof(IRowsArgs) <= G_KERNARG_MAX, "layout and arguments travel as kernel arguments");
 
+// DC: the decoder is fed the classifier's output p_c instead of the label (dec_label "classifier"); AV: the adversarial term V on the
+// encoder is 0 the cross entropy, 1 binary_cross_entropy_v2 (targets 0.5), 2 binary_cross_entropy_v3 (the entropy of aux(z)).  <false, 0>
+// is the step described at the top of the file.  What the other instantiations change:
+//   DC  phase 1 ends with p_c in Y (the labels are done with until the classifier's backward pass) and in the stash behind z; phase 3 runs
+//       as it is, on p_c; behind it, with dpre_d1 in A: d p_c = alpha dBCE / d p_c + dpre_d1 D1[:, z:] (the transposed label block D1yT),
+//       dpre_o -> X, and the thread puts the label it read for this -- again through the frame's row of the gather table, so a refused
+//       index stays counted once -- back into Y; dpre_c2 -> Bf and dpre_c1 with the relu masks from the stash.
+//   AV  the output layer of the auxiliary net forms two gradients: gamma dBCE - beta dV at weight 1 / B -> X (towards the weights: the
+//       chain that is stashed) and dV at weight 1 / B -> Y (towards z; the labels are done with for this tile).  The weight chain runs
+//       first, then the z chain through the same relu masks, read from the stash; dpre_a1 of the z chain -> X for phase 5.
+template <bool DC, int AV>
 __global__ __launch_bounds__(256) void train_info_rows_kernel(const ILayout L, const IRowsArgs g) {
     extern __shared__ __attribute__((aligned(16))) float ism[];
     float* X = ism;                                     // [528][16] x; dpre_o of the classifier; x again; d loss / d a; a1, dpre_ao, dpre_a1
@@ -224,6 +255,7 @@ __global__ __launch_bounds__(256) void train_info_rows_kernel(const ILayout L, c
     const float* wp = g.ws;
     const bool bwd = !g.fwd_only;
     double sum_is = 0.0, sum_kl = 0.0, sum_bc = 0.0, sum_ba = 0.0;
+    [[maybe_unused]] double sum_bv = 0.0;                // V, where it is not the cross entropy
 
     for (int64_t tile = blockIdx.x; tile < L.tiles; tile += gridDim.x) {
         const int64_t r0 = tile * GT;
@@ -318,6 +350,20 @@ __global__ __launch_bounds__(256) void train_info_rows_kernel(const ILayout L, c
         for (int t = wave; t < ky; t += 4) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
             acc = tg_gemm(acc, wp + L.Co + (int64_t)t * k2 * 256, k2, Bf, lane);
+            if constexpr (DC) {
+                // p_c takes the label's place in Y (zero in padded columns and frames past B) and lies behind z in the stash
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = 16 * t + 4 * quad + r;
+                    const bool ok = fok && row < L.y;
+                    const float p = 1.f / (1.f + expf(-(acc[r] + wp[L.bco + row])));
+                    const float q = 1.f - p, yv = Y[row * GT + col];
+                    if (ok) sum_bc -= (double)(yv * logf(p + g.elbo_eps) + (1.f - yv) * logf(q + g.elbo_eps));
+                    Y[row * GT + col] = ok ? p : 0.f;
+                    if (bwd && ok) g.stash[(r0 + col) * (int64_t)L.S + L.s_zc + L.z + row] = p;
+                }
+                continue;
+            }
             f32x4 da;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -327,7 +373,7 @@ __global__ __launch_bounds__(256) void train_info_rows_kernel(const ILayout L, c
             }
             st4(L.s_pco, t, da);
         }
-        if (bwd) {
+        if (!DC && bwd) {
             __syncthreads();
             // ---- d c2 = dpre_o Co; dpre_c2 = d c2 [c2 > 0] -> Bf (c2: this thread's own entry) ----
             for (int t = wave; t < k2; t += 4) {
@@ -411,6 +457,9 @@ __global__ __launch_bounds__(256) void train_info_rows_kernel(const ILayout L, c
             C[(2 * L.zp + j) * GT + c] = 0.5f * sd * e;
             if (ok) sum_kl += (double)(-0.5f * (lv - mu * mu - ev));
             g.stash[(r0 + c) * (int64_t)L.S + L.s_z + j] = zv;
+            if constexpr (DC) {
+                if (bwd && j < L.z) g.stash[(r0 + c) * (int64_t)L.S + L.s_zc + j] = zv;     // [z | p_c] for the weight gradient of decoder layer 1
+            }
         }
         __syncthreads();
 
@@ -494,6 +543,53 @@ __global__ __launch_bounds__(256) void train_info_rows_kernel(const ILayout L, c
                 st4(L.s_pd1, t, d);
             }
             __syncthreads();
+            if constexpr (DC) {
+                // ---- the classifier's backward pass: d p_c = alpha d BCE / d p_c + dpre_d1 D1[:, z:]; dpre_o -> X rows 0 .. yp - 1 (d loss / d a
+                // is done with); the label, read again through the frame's row, returns to Y ----
+                for (int t = wave; t < ky; t += 4) {
+                    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                    acc = tg_gemm(acc, wp + L.D1yT + (int64_t)t * k2 * 256, k2, A, lane);
+                    f32x4 da;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int row = 16 * t + 4 * quad + r;
+                        const bool ok = fok && row < L.y;
+                        const float yv = ok ? g.y[srow[col] * g.ldy + row] : 0.f;
+                        const float p = Y[row * GT + col], q = 1.f - p;
+                        const float dp = acc[r] - g.clf_scale * (yv / (p + g.elbo_eps) - (1.f - yv) / (q + g.elbo_eps));
+                        da[r] = ok ? dp * p * q : 0.f;
+                        X[row * GT + col] = da[r];
+                        Y[row * GT + col] = yv;
+                    }
+                    st4(L.s_pco, t, da);
+                }
+                __syncthreads();
+                // ---- d c2 = dpre_o Co; dpre_c2 = d c2 [c2 > 0] -> Bf (c2: this thread's own stash entry; dpre_d2 is done with) ----
+                for (int t = wave; t < k2; t += 4) {
+                    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                    acc = tg_gemm(acc, wp + L.CoT + (int64_t)t * ky * 256, ky, X, lane);
+                    const f32x4 o = ld4(L.s_c2, t);
+                    f32x4 d;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        d[r] = o[r] > 0.f ? acc[r] : 0.f;
+                        Bf[(16 * t + 4 * quad + r) * GT + col] = d[r];
+                    }
+                    st4(L.s_pc2, t, d);
+                }
+                __syncthreads();
+                // ---- d c1 = dpre_c2 C2; dpre_c1 = d c1 [c1 > 0]: only the stash needs it ----
+                for (int t = wave; t < k1; t += 4) {
+                    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                    acc = tg_gemm(acc, wp + L.C2T + (int64_t)t * k2 * 256, k2, Bf, lane);
+                    const f32x4 o = ld4(L.s_c1, t);
+                    f32x4 d;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) d[r] = o[r] > 0.f ? acc[r] : 0.f;
+                    st4(L.s_pc1, t, d);
+                }
+                __syncthreads();
+            }
         }
 
         // ================================ 4. the auxiliary net on z: X and Bf are free ================================
@@ -501,6 +597,18 @@ __global__ __launch_bounds__(256) void train_info_rows_kernel(const ILayout L, c
         for (int i = tid; i < GT * L.zp; i += 256) {
             const int c = i & 15, j = i >> 4;
             Bf[j * GT + c] = g.stash[(r0 + c) * (int64_t)L.S + L.s_z + j];
+        }
+        if constexpr (DC) {
+            if (!bwd) {                                 // no backward pass has put the labels back into Y
+                for (int b = wave; b < ky; b += 4) {
+#pragma unroll
+                    for (int cq = 0; cq < 4; ++cq) {
+                        const int k = 16 * b + col, c = 4 * cq + quad;
+                        const int64_t s = srow[c];
+                        Y[k * GT + c] = (k < L.y && s >= 0) ? g.y[s * g.ldy + k] : 0.f;
+                    }
+                }
+            }
         }
         __syncthreads();
         // ---- a1 = relu(z A1^T + b) -> X ----
@@ -538,6 +646,32 @@ __global__ __launch_bounds__(256) void train_info_rows_kernel(const ILayout L, c
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
             acc = tg_gemm(acc, wp + L.Ao + (int64_t)t * k2 * 256, k2, Bf, lane);
             f32x4 da;
+            if constexpr (AV != 0) {
+                // V and d V / d p (oracle/vae_oracle.py: bce_v2_bwd, bce_v3_bwd, the eps terms kept); towards the weights gamma dBCE - beta dV
+                // -> X and the stash, towards z dV -> Y (times -beta where dz is formed: beta = 0 divides nothing)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = 16 * t + 4 * quad + r;
+                    const bool ok = fok && row < L.y;
+                    const float p = 1.f / (1.f + expf(-(acc[r] + wp[L.bao + row])));
+                    const float q = 1.f - p, yv = Y[row * GT + col];
+                    const float lp = logf(p + g.elbo_eps), lq = logf(q + g.elbo_eps);
+                    const float ip = 1.f / (p + g.elbo_eps), iq = 1.f / (q + g.elbo_eps);
+                    if (ok) {
+                        sum_ba -= (double)(yv * lp + (1.f - yv) * lq);
+                        sum_bv -= (double)(AV == 1 ? 0.5f * lp + 0.5f * lq : p * lp + q * lq);
+                    }
+                    const float db = -g.invB * (yv * ip - (1.f - yv) * iq);
+                    const float dv = AV == 1 ? -g.invB * (0.5f * ip - 0.5f * iq) : -g.invB * (lp + p * ip - lq - q * iq);
+                    da[r] = ok ? (g.aux_gamma * db + g.aux_z_scale * dv) * p * q : 0.f;
+                    if (bwd) {
+                        X[row * GT + col] = da[r];
+                        Y[row * GT + col] = ok ? dv * p * q : 0.f;
+                    }
+                }
+                st4(L.s_pao, t, da);
+                continue;
+            }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = 16 * t + 4 * quad + r;
@@ -549,37 +683,82 @@ __global__ __launch_bounds__(256) void train_info_rows_kernel(const ILayout L, c
         }
         if (!bwd) continue;
         __syncthreads();
-        // ---- d a2 = dpre_ao Ao; dpre_a2 = d a2 [a2 > 0] -> Bf (a2: this thread's own entry) ----
-        for (int t = wave; t < k2; t += 4) {
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            acc = tg_gemm(acc, wp + L.AoT + (int64_t)t * ky * 256, ky, X, lane);
-            f32x4 d;
+        if constexpr (AV != 0) {
+            // ---- the chain towards the weights: dpre_a2 = (dpre_ao Ao) [a2 > 0] -> Bf (a2: this thread's own entry) and the stash ----
+            for (int t = wave; t < k2; t += 4) {
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                acc = tg_gemm(acc, wp + L.AoT + (int64_t)t * ky * 256, ky, X, lane);
+                f32x4 d;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = 16 * t + 4 * quad + r;
-                const float v = Bf[row * GT + col] > 0.f ? acc[r] : 0.f;
-                Bf[row * GT + col] = v;
-                d[r] = v * g.aux_w_scale;
+                for (int r = 0; r < 4; ++r) {
+                    const int row = 16 * t + 4 * quad + r;
+                    d[r] = Bf[row * GT + col] > 0.f ? acc[r] : 0.f;
+                    Bf[row * GT + col] = d[r];
+                }
+                st4(L.s_pa2, t, d);
             }
-            st4(L.s_pa2, t, d);
-        }
-        __syncthreads();
-        // ---- d a1 = dpre_a2 A2; dpre_a1 = d a1 [a1 > 0] -> X (a1: this thread's own stash entry; dpre_ao in X is done with) ----
-        for (int t = wave; t < k1; t += 4) {
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            acc = tg_gemm(acc, wp + L.A2T + (int64_t)t * k2 * 256, k2, Bf, lane);
-            const f32x4 o = ld4(L.s_a1, t);
-            f32x4 d;
+            __syncthreads();
+            // ---- dpre_a1 = (dpre_a2 A2) [a1 > 0]: only the stash needs this chain's ----
+            for (int t = wave; t < k1; t += 4) {
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                acc = tg_gemm(acc, wp + L.A2T + (int64_t)t * k2 * 256, k2, Bf, lane);
+                const f32x4 o = ld4(L.s_a1, t);
+                f32x4 d;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = 16 * t + 4 * quad + r;
-                const float v = o[r] > 0.f ? acc[r] : 0.f;
-                X[row * GT + col] = v;
-                d[r] = v * g.aux_w_scale;
+                for (int r = 0; r < 4; ++r) d[r] = o[r] > 0.f ? acc[r] : 0.f;
+                st4(L.s_pa1, t, d);
             }
-            st4(L.s_pa1, t, d);
+            __syncthreads();
+            // ---- the chain towards z, from Y: the same masks, a2 now from the stash; dpre_a2 -> Bf, dpre_a1 -> X for phase 5 ----
+            for (int t = wave; t < k2; t += 4) {
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                acc = tg_gemm(acc, wp + L.AoT + (int64_t)t * ky * 256, ky, Y, lane);
+                const f32x4 o = ld4(L.s_a2, t);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) Bf[(16 * t + 4 * quad + r) * GT + col] = o[r] > 0.f ? acc[r] : 0.f;
+            }
+            __syncthreads();
+            for (int t = wave; t < k1; t += 4) {
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                acc = tg_gemm(acc, wp + L.A2T + (int64_t)t * k2 * 256, k2, Bf, lane);
+                const f32x4 o = ld4(L.s_a1, t);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) X[(16 * t + 4 * quad + r) * GT + col] = o[r] > 0.f ? acc[r] : 0.f;
+            }
+            __syncthreads();
+        } else {
+            // ---- d a2 = dpre_ao Ao; dpre_a2 = d a2 [a2 > 0] -> Bf (a2: this thread's own entry) ----
+            for (int t = wave; t < k2; t += 4) {
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                acc = tg_gemm(acc, wp + L.AoT + (int64_t)t * ky * 256, ky, X, lane);
+                f32x4 d;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = 16 * t + 4 * quad + r;
+                    const float v = Bf[row * GT + col] > 0.f ? acc[r] : 0.f;
+                    Bf[row * GT + col] = v;
+                    d[r] = v * g.aux_w_scale;
+                }
+                st4(L.s_pa2, t, d);
+            }
+            __syncthreads();
+            // ---- d a1 = dpre_a2 A2; dpre_a1 = d a1 [a1 > 0] -> X (a1: this thread's own stash entry; dpre_ao in X is done with) ----
+            for (int t = wave; t < k1; t += 4) {
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                acc = tg_gemm(acc, wp + L.A2T + (int64_t)t * k2 * 256, k2, Bf, lane);
+                const f32x4 o = ld4(L.s_a1, t);
+                f32x4 d;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = 16 * t + 4 * quad + r;
+                    const float v = o[r] > 0.f ? acc[r] : 0.f;
+                    X[row * GT + col] = v;
+                    d[r] = v * g.aux_w_scale;
+                }
+                st4(L.s_pa1, t, d);
+            }
+            __syncthreads();
         }
-        __syncthreads();
 
         // ================================ 5. dz and the encoder's backward pass ================================
         // ---- dz = dpre_d1 D1[:, :z] - beta dpre_a1 A1; d mu = dz + mu / B; d log_var = dz eps std / 2 + its KL part -> C rows 0 .. 2 zp - 1 ----
@@ -634,6 +813,13 @@ __global__ __launch_bounds__(256) void train_info_rows_kernel(const ILayout L, c
     if (lane == 0) { red[wave][0] = sum_is; red[wave][1] = sum_kl; red[wave][2] = sum_bc; red[wave][3] = sum_ba; }
     __syncthreads();
     if (tid < 4) g.partials[4 * (int64_t)blockIdx.x + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    if constexpr (AV != 0) {
+        sum_bv = wave_sum(sum_bv);
+        double* redv = reinterpret_cast<double*>(ism) + 16;
+        if (lane == 0) redv[wave] = sum_bv;
+        __syncthreads();
+        if (tid == 0) g.partials_v[blockIdx.x] = ((redv[0] + redv[1]) + redv[2]) + redv[3];
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -642,8 +828,9 @@ static const char* LIMITS = "the M2_info train step covers DeepGenerativeModel_v
 
 static int plan_layout(const char* who, const dvae_train_info_plan_t* plan, ILayout& L) {
     DVAE_CHECK_ARG(plan, "%s: null plan", who);
-    DVAE_CHECK_ARG(dims_ok(plan->y_dim, plan->z_dim, plan->h1, plan->h2) && plan->B >= 1 && plan->n_tensors == I_NT, "%s: not a plan of dvae_train_info_plan", who);
-    L = make_layout(plan->y_dim, plan->z_dim, plan->h1, plan->h2, plan->B, plan->ksplit);
+    DVAE_CHECK_ARG(dims_ok(plan->y_dim, plan->z_dim, plan->h1, plan->h2) && plan->B >= 1 && plan->n_tensors == I_NT && mode_ok(plan->info_mode),
+                   "%s: not a plan of dvae_train_info_plan", who);
+    L = make_layout(plan->y_dim, plan->z_dim, plan->h1, plan->h2, plan->B, plan->ksplit, plan->info_mode);
     DVAE_CHECK_ARG(L.ws_bytes == plan->workspace_bytes && L.nslices == plan->ksplit && L.n_params == plan->n_params &&
                    L.slice_frames == plan->slice_frames, "%s: the plan was changed after dvae_train_info_plan", who);
     return 0;
@@ -671,26 +858,38 @@ static ApplyArgs apply_args(const dvae_train_info_plan_t* plan, const ILayout& L
         a.step_size = (float)(lr / bc1); a.bc2_sqrt = (float)sqrt(bc2); a.eps = (float)adam_eps; a.gscale = (float)grad_scale;
     }
     a.partials = (const double*)(ws + L.o_partials); a.npartials = (int)L.rows_grid; a.B = L.B; a.losses3 = losses8;
-    a.accum = (double*)(uintptr_t)plan->loss_accum;
+    a.accum = (L.mode & MODE_AUX) ? nullptr : (double*)(uintptr_t)plan->loss_accum;      // (launch_apply: the apply kernel corrects the scalars first)
     a.info = 1; a.alpha = (float)plan->info_alpha; a.beta = (float)plan->info_beta; a.gamma = (float)plan->info_gamma;
     return a;
 }
 
 // adam: the optimizer step on every parameter; otherwise only the packed copies are rewritten (elements) and / or the losses finalised
-static int launch_apply(const ILayout& L, const ApplyArgs& a, char* ws, bool adam, bool elements, bool finalize, hipStream_t s) {
+static int launch_apply(const dvae_train_info_plan_t* plan, const ILayout& L, const ApplyArgs& a, char* ws, bool adam, bool elements, bool finalize,
+                        hipStream_t s) {
     GApplyArgs g;
     memset(&g, 0, sizeof(g));
     g.a = a;
     if (!elements) g.a.n_params = 0;
     make_tensors(L, g.t);
+    if (L.mode & MODE_AUX) {
+        g.v_partials = (const double*)(ws + L.o_partials) + 4 * L.rows_grid;
+        g.v_accum = (double*)(uintptr_t)plan->loss_accum;
+    }
     g.ws = (float*)ws; g.adam = adam ? 1 : 0; g.finalize = finalize ? 1 : 0;
     return launch_apply_table(g, s);
 }
 
+template <bool DC, int AV>
+static int launch_rows_mode(const ILayout& L, const IRowsArgs& g, hipStream_t s) {
+    static bool attr_done[64] = {};                     // (one per instantiation: the limit is a property of the kernel)
+    if (int rc = raise_lds_limit((const void*)train_info_rows_kernel<DC, AV>, "train_info_rows_kernel", L.lds_bytes, attr_done)) return rc;
+    hipLaunchKernelGGL((train_info_rows_kernel<DC, AV>), dim3((unsigned)L.rows_grid), dim3(256), (size_t)L.lds_bytes, s, L, g);
+    DVAE_LAUNCH_OK("train_info_rows_kernel");
+    return 0;
+}
+
 static int launch_rows(const dvae_train_info_plan_t* plan, const ILayout& L, char* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
                        const float* eps, float elbo_eps, bool fwd_only, hipStream_t s) {
-    static bool attr_done[64] = {};
-    if (int rc = raise_lds_limit((const void*)train_info_rows_kernel, "train_info_rows_kernel", L.lds_bytes, attr_done)) return rc;
     IRowsArgs g;
     memset(&g, 0, sizeof(g));
     g.x = x; g.ldx = ldx; g.y = y; g.ldy = ldy; g.eps = eps;
@@ -700,9 +899,12 @@ static int launch_rows(const dvae_train_info_plan_t* plan, const ILayout& L, cha
     g.clf_scale = (float)(plan->info_alpha / (double)L.B);
     g.aux_z_scale = (float)(-plan->info_beta);
     g.aux_w_scale = (float)(plan->info_gamma - plan->info_beta);
-    hipLaunchKernelGGL(train_info_rows_kernel, dim3((unsigned)L.rows_grid), dim3(256), (size_t)L.lds_bytes, s, L, g);
-    DVAE_LAUNCH_OK("train_info_rows_kernel");
-    return 0;
+    g.aux_gamma = (float)plan->info_gamma;
+    g.partials_v = g.partials + 4 * L.rows_grid;
+    const bool dc = (L.mode & DVAE_INFO_DEC_CLASSIFIER) != 0;
+    const int av = (L.mode & DVAE_INFO_AUX_UNIFORM) ? 1 : ((L.mode & DVAE_INFO_AUX_ENTROPY) ? 2 : 0);
+    if (!dc) return av == 0 ? launch_rows_mode<false, 0>(L, g, s) : (av == 1 ? launch_rows_mode<false, 1>(L, g, s) : launch_rows_mode<false, 2>(L, g, s));
+    return av == 0 ? launch_rows_mode<true, 0>(L, g, s) : (av == 1 ? launch_rows_mode<true, 1>(L, g, s) : launch_rows_mode<true, 2>(L, g, s));
 }
 
 static int launch_wgrad(const dvae_train_info_plan_t* plan, const ILayout& L, char* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
@@ -725,12 +927,20 @@ using namespace dvae;
 using namespace dvae::ti;
 
 extern "C" int dvae_train_info_plan(int y_dim, int z_dim, int h1, int h2, int64_t B, int ksplit_hint, dvae_train_info_plan_t* plan) {
+    return dvae_train_info_plan_mode(y_dim, z_dim, h1, h2, B, ksplit_hint, 0, plan);
+}
+
+extern "C" int dvae_train_info_plan_mode(int y_dim, int z_dim, int h1, int h2, int64_t B, int ksplit_hint, int mode, dvae_train_info_plan_t* plan) {
     DVAE_CHECK_ARG(plan, "train_info_plan: null plan");
+    DVAE_CHECK_ARG(mode_ok(mode), "train_info_plan: mode 0x%x; the bits are DVAE_INFO_DEC_CLASSIFIER (%d: the decoder is fed the classifier's output; "
+                   "otherwise the label) and at most one of DVAE_INFO_AUX_UNIFORM (%d) and DVAE_INFO_AUX_ENTROPY (%d) (the adversarial term on the "
+                   "encoder; neither: the cross entropy)", mode, DVAE_INFO_DEC_CLASSIFIER, DVAE_INFO_AUX_UNIFORM, DVAE_INFO_AUX_ENTROPY);
     DVAE_CHECK_ARG(dims_ok(y_dim, z_dim, h1, h2), "train_info_plan: y_dim %d, hidden %d / %d, z_dim %d; %s", y_dim, h1, h2, z_dim, LIMITS);
     DVAE_CHECK_ARG(B >= 1 && B < ((int64_t)1 << 31), "train_info_plan: %lld frames", (long long)B);
     DVAE_CHECK_ARG(ksplit_hint >= 0 && ksplit_hint <= G_MAX_SLICES, "train_info_plan: %d frame slices (0 = choose, at most %d)", ksplit_hint, G_MAX_SLICES);
-    const ILayout L = make_layout(y_dim, z_dim, h1, h2, B, ksplit_hint);
+    const ILayout L = make_layout(y_dim, z_dim, h1, h2, B, ksplit_hint, mode);
     memset(plan, 0, sizeof(*plan));
+    plan->info_mode = mode;
     plan->y_dim = y_dim; plan->z_dim = z_dim; plan->h1 = h1; plan->h2 = h2;
     plan->ksplit = L.nslices; plan->n_tensors = I_NT; plan->launches_per_step = I_LAUNCHES; plan->B = B; plan->n_params = L.n_params;
     for (int t = 0; t < I_NT; ++t) { plan->tensor_offset[t] = L.toff[t]; plan->tensor_rows[t] = L.trows[t]; plan->tensor_cols[t] = L.tcols[t]; }
@@ -747,7 +957,7 @@ extern "C" int dvae_train_info_repack(const dvae_train_info_plan_t* plan, const 
     hipStream_t s = (hipStream_t)stream;
     DVAE_HIP(hipMemsetAsync(ws, 0, (size_t)L.wpack_elems * 4, s));          // the padding of the packed copies
     const ApplyArgs a = apply_args(plan, L, (float*)params, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, nullptr);
-    return launch_apply(L, a, (char*)ws, false, true, false, s);
+    return launch_apply(plan, L, a, (char*)ws, false, true, false, s);
 }
 
 extern "C" int dvae_train_info_init(const dvae_train_info_plan_t* plan, const float* params, void* ws, void* stream) {
@@ -761,7 +971,7 @@ extern "C" int dvae_train_info_init(const dvae_train_info_plan_t* plan, const fl
     const std::vector<GItem> items = make_items(gm, order, I_NG, L.nslices);
     DVAE_CHECK_ARG((int)items.size() == L.n_items, "train_info_init: %d items for a table of %d", (int)items.size(), L.n_items);
     DVAE_HIP(hipMemcpyAsync((char*)ws + L.o_items, items.data(), items.size() * sizeof(GItem), hipMemcpyHostToDevice, s));
-    DVAE_HIP(hipMemsetAsync((char*)ws + L.o_partials, 0, (size_t)L.rows_grid * 4 * sizeof(double), s));
+    DVAE_HIP(hipMemsetAsync((char*)ws + L.o_partials, 0, (size_t)L.rows_grid * ((L.mode & MODE_AUX) ? 5 : 4) * sizeof(double), s));
     DVAE_HIP(hipStreamSynchronize(s));                                      // the table leaves host memory that ends with this call
     return dvae_train_info_repack(plan, params, ws, stream);
 }
@@ -783,7 +993,7 @@ extern "C" int dvae_train_info_apply(const dvae_train_info_plan_t* plan, float* 
     DVAE_CHECK_ARG(params && m && v && ws && losses8, "train_info_apply: null pointer");
     DVAE_CHECK_ARG(step >= 1, "train_info_apply: step %d (1-based)", step);
     const ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, losses8);
-    return launch_apply(L, a, (char*)ws, true, true, true, (hipStream_t)stream);
+    return launch_apply(plan, L, a, (char*)ws, true, true, true, (hipStream_t)stream);
 }
 
 extern "C" int dvae_train_info_step(const dvae_train_info_plan_t* plan, float* params, float* m, float* v, void* ws, const float* x, int64_t ldx,
@@ -804,5 +1014,5 @@ extern "C" int dvae_train_info_eval(const dvae_train_info_plan_t* plan, void* ws
     hipStream_t s = (hipStream_t)stream;
     if (int rc = launch_rows(plan, L, (char*)ws, x, ldx, y, ldy, eps_noise, elbo_eps, true, s)) return rc;
     const ApplyArgs a = apply_args(plan, L, nullptr, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, losses8);
-    return launch_apply(L, a, (char*)ws, false, false, true, s);
+    return launch_apply(plan, L, a, (char*)ws, false, false, true, s);
 }

@@ -122,6 +122,7 @@ SIGNATURES = {
     "dvae_train_clf_step": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_f, c_i, c_d, c_d, c_d, c_d, c_vp, c_vp, c_vp]),
     "dvae_train_clf_eval": (c_i, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_f, c_vp, c_vp, c_vp]),
     "dvae_train_info_plan": (c_i, [c_i, c_i, c_i, c_i, c_i64, c_i, c_vp]),
+    "dvae_train_info_plan_mode": (c_i, [c_i, c_i, c_i, c_i, c_i64, c_i, c_i, c_vp]),
     "dvae_train_info_init": (c_i, [c_vp, c_vp, c_vp, c_vp]),
     "dvae_train_info_repack": (c_i, [c_vp, c_vp, c_vp, c_vp]),
     "dvae_train_info_grads": (c_i, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_f, c_vp]),

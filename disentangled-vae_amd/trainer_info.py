@@ -4,6 +4,12 @@ adversarial auxiliary relu classifier on z; enc_loss = ELBO + alpha BCE(clf(x), 
 the auxiliary net stepped with (gamma - beta) dBCE, one Adam update over all 26 tensors -- in three HIP launches per step whatever the
 geometry: x 513, y_dim 1..513, hidden widths 1..512, z_dim 1..128, exact fp32, one GPU.
 
+Two independent options give the other loop bodies the reference trains M2_info with (include/dvae_train.h: dvae_train_info_plan_mode):
+`dec_label="classifier"` feeds the decoder [z | clf(x)] instead of [z | y], so that the reconstruction gradient trains the classifier
+(scripts/training_M2_info_vad_pretrain.py:162-163), and `aux_enc="uniform"` / `"entropy"` replace the adversarial cross entropy on the
+encoder by binary_cross_entropy_v2 / _v3 of aux(z) (line 175; the caller passes gamma = beta for that script).  The defaults,
+"truth" and "bce", are the step described above, bit for bit.
+
 `InfoTrainer` offers the surface of `trainer_generic.GenericTrainer` where it has meaning here; `make_info_trainer` chooses between it and
 the resident `trainer.Trainer("M2_info", ...)`, which stays the default at the reference geometry and is the only home of the 16-bit
 operand policies and of data-parallel training.  PyTorch is plumbing: it owns the buffers and the stream, and draws the reparametrisation
@@ -23,7 +29,7 @@ LIMITS = ("the generic M2_info train step covers DeepGenerativeModel_v5 at x_dim
 
 class InfoPlan(ctypes.Structure):
     _fields_ = [("y_dim", ctypes.c_int32), ("z_dim", ctypes.c_int32), ("h1", ctypes.c_int32), ("h2", ctypes.c_int32), ("ksplit", ctypes.c_int32),
-                ("n_tensors", ctypes.c_int32), ("launches_per_step", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("B", ctypes.c_int64),
+                ("n_tensors", ctypes.c_int32), ("launches_per_step", ctypes.c_int32), ("info_mode", ctypes.c_int32), ("B", ctypes.c_int64),
                 ("n_params", ctypes.c_int64), ("tensor_offset", ctypes.c_int64 * MAXT), ("tensor_rows", ctypes.c_int32 * MAXT),
                 ("tensor_cols", ctypes.c_int32 * MAXT), ("workspace_bytes", ctypes.c_int64), ("grad_offset_bytes", ctypes.c_int64),
                 ("Bp", ctypes.c_int64), ("rows_grid", ctypes.c_int64), ("slice_frames", ctypes.c_int64), ("wgrad_items", ctypes.c_int64),
@@ -41,14 +47,30 @@ def covered(dims):
         return False
 
 
-def make_plan(dims, batch, ksplit=0):
-    """dvae_train_info_plan for (dims, batch): host only.  Raises NotImplementedError / ValueError with the library's message."""
+DEC_LABELS = {"truth": 0, "classifier": 1}              # the DVAE_INFO_* bits of include/dvae_train.h
+AUX_ENCS = {"bce": 0, "uniform": 2, "entropy": 4}
+
+
+def mode_bits(dec_label="truth", aux_enc="bce"):
+    """The mode of dvae_train_info_plan_mode for the two options; ValueError naming the choices for any other value (host logic only)."""
+    if dec_label not in DEC_LABELS:
+        raise ValueError(f"dec_label {dec_label!r}: the choices are {sorted(DEC_LABELS)}")
+    if aux_enc not in AUX_ENCS:
+        raise ValueError(f"aux_enc {aux_enc!r}: the choices are {sorted(AUX_ENCS)}")
+    return DEC_LABELS[dec_label] | AUX_ENCS[aux_enc]
+
+
+def make_plan(dims, batch, ksplit=0, dec_label="truth", aux_enc="bce"):
+    """dvae_train_info_plan_mode for (dims, batch) and the two options: host only.  Raises NotImplementedError / ValueError with the
+    library's message."""
+    mode = mode_bits(dec_label, aux_enc)
     lib = N.load()
     h = tuple(dims.get("h_dim", ()))
     if dims.get("x_dim") != 513 or len(h) != 2:
         raise NotImplementedError(f"{LIMITS}; got {dims}")
     plan = InfoPlan()
-    rc = lib.dvae_train_info_plan(int(dims.get("y_dim", 0) or 0), int(dims["z_dim"]), int(h[0]), int(h[1]), int(batch), int(ksplit), ctypes.byref(plan))
+    rc = lib.dvae_train_info_plan_mode(int(dims.get("y_dim", 0) or 0), int(dims["z_dim"]), int(h[0]), int(h[1]), int(batch), int(ksplit), mode,
+                                       ctypes.byref(plan))
     if rc != 0:
         msg = lib.dvae_last_error().decode("utf-8", "replace")
         raise (NotImplementedError if rc == 1003 else ValueError)(f"{msg} (got {dims})")
@@ -62,8 +84,9 @@ class InfoTrainer:
     model = "M2_info"
 
     def __init__(self, dims, params=None, batch=128, device="cuda:0", lr=1e-4, betas=(0.9, 0.999), adam_eps=1e-8, elbo_eps=1e-8,
-                 alpha=0.0, beta=10.0, gamma=1.0, seed=None, ksplit=0, share=None):
-        self.plan = make_plan(dims, batch, ksplit)          # refuses before anything touches the device
+                 alpha=0.0, beta=10.0, gamma=1.0, seed=None, ksplit=0, share=None, dec_label="truth", aux_enc="bce"):
+        self.plan = make_plan(dims, batch, ksplit, dec_label, aux_enc)      # refuses before anything touches the device
+        self.dec_label, self.aux_enc = dec_label, aux_enc
         self.plan.info_alpha, self.plan.info_beta, self.plan.info_gamma = float(alpha), float(beta), float(gamma)
         if not torch.cuda.is_available():
             raise RuntimeError("InfoTrainer needs the MI355X HIP path (no CPU fallback)")
@@ -116,7 +139,8 @@ class InfoTrainer:
         """A trainer for another batch size over the SAME parameters and Adam moments (the last, shorter batch of an epoch, the
         validation batch size).  Each trainer has its own packed weight copies; they are rebuilt when the other one has stepped."""
         return InfoTrainer(self.dims, batch=batch, device=self.device, lr=self.lr, betas=self.betas, adam_eps=self.adam_eps,
-                           elbo_eps=self.elbo_eps, alpha=self.alpha, beta=self.beta, gamma=self.gamma, ksplit=self.ksplit, share=self)
+                           elbo_eps=self.elbo_eps, alpha=self.alpha, beta=self.beta, gamma=self.gamma, ksplit=self.ksplit, share=self,
+                           dec_label=self.dec_label, aux_enc=self.aux_enc)
 
     def _repack(self):
         with torch.cuda.device(self.device):
@@ -177,7 +201,8 @@ class InfoTrainer:
 
     def grads_numpy(self):
         """Gradient of the last step per tensor, as numpy: the frame-slice slabs summed in slab order, as the apply kernel sums them.
-        The auxiliary tensors hold (gamma - beta) dBCE, what the script's second optimizer steps with, as on the resident trainer."""
+        The auxiliary tensors hold (gamma - beta) dBCE -- gamma dBCE - beta dV under aux_enc "uniform" / "entropy" --, what the script's
+        second optimizer steps with, as on the resident trainer."""
         P, ks, go = self.plan.n_params, self.plan.ksplit, self.plan.grad_offset_bytes
         slabs = self.ws[go:go + 4 * P * ks].view(torch.float32).view(ks, P)
         flat = slabs[0].clone()
@@ -276,22 +301,25 @@ class InfoTrainer:
         self.plan.loss_accum = 0 if buf is None else buf.data_ptr()
 
 
-def info_trainer_kind(dims):
+def info_trainer_kind(dims, dec_label="truth", aux_enc="bce"):
     """Which fused train step serves M2_info at `dims`: "resident" (the hand-tuned kernels of the reference's geometry,
-    trainer.supported), "generic" (csrc/train_info.hip) or None.  Host logic only."""
+    trainer.supported), "generic" (csrc/train_info.hip) or None.  The resident step has the default options only, so any other
+    goes to the generic step at the reference geometry too.  Host logic only."""
+    default = mode_bits(dec_label, aux_enc) == 0
     try:
-        if supported("M2_info", dims):
+        if default and supported("M2_info", dims):
             return "resident"
     except (KeyError, TypeError):       # a dims dict without one of the keys names no geometry of the resident step
         pass
     return "generic" if covered(dims) else None
 
 
-def make_info_trainer(dims, generic=False, **kw):
+def make_info_trainer(dims, generic=False, dec_label="truth", aux_enc="bce", **kw):
     """The resident Trainer("M2_info", ...) where trainer.supported holds (the default there: the faster step, the 16-bit operand policies,
-    data-parallel training), otherwise an InfoTrainer; generic=True puts the reference geometry on the generic step too.  Raises with the
-    limits named when neither covers `dims`, and for a 16-bit policy or world != 1 on the generic step."""
-    kind = info_trainer_kind(dims)
+    data-parallel training), otherwise an InfoTrainer; generic=True, or an option other than dec_label="truth" / aux_enc="bce", puts the
+    reference geometry on the generic step too.  Raises with the limits named when neither covers `dims`, and for a 16-bit policy or
+    world != 1 on the generic step; ValueError naming the choices for an unknown option, before anything touches the device."""
+    kind = info_trainer_kind(dims, dec_label, aux_enc)
     if kind is None or (generic and not covered(dims)):
         raise NotImplementedError(f"no fused M2_info train step for {dims}: the resident step covers x 513, z 16, h [128, 128], y 1; {LIMITS}")
     if kind == "resident" and not generic:
@@ -302,4 +330,4 @@ def make_info_trainer(dims, generic=False, **kw):
         raise NotImplementedError(f"data-parallel training is not built on the generic step (got world={kw.get('world', 1)}); {LIMITS}")
     for k in ("precision", "world", "process_group"):
         kw.pop(k, None)
-    return InfoTrainer(dims, **kw)
+    return InfoTrainer(dims, dec_label=dec_label, aux_enc=aux_enc, **kw)

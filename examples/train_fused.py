@@ -8,6 +8,13 @@ trainer_info.py: make_info_trainer, the same choice for DeepGenerativeModel_v5).
     python examples/train_fused.py --model M2 --synthetic 200000            # no dataset at hand
     python examples/train_fused.py --model M2 --synthetic 200000 --y-dim 1 --z-dim 32 --h-dim 256 64      # the model examples/enhance_mcem.py takes
     python examples/train_fused.py --model M2_info --synthetic 200000 --z-dim 32 --h-dim 256 64            # ... with --labels classifier
+    # scripts/training_M2_info_vad_pretrain.py: a classifier trained alone moves in, the decoder is fed its output, the encoder's
+    # adversarial term is the entropy of the auxiliary net (alpha 0, gamma = beta)
+    python examples/train_classifier.py --synthetic 40 --h-dim 256 64 --save models/clf.pt --prefix enc_dec_clf.classifier.
+    python examples/train_fused.py --model M2_info --synthetic 200000 --z-dim 32 --h-dim 256 64 --decoder-label classifier \
+        --aux-enc entropy --gamma 10 --init-classifier models/clf.pt
+    python examples/enhance_mcem.py --synthetic 3 --z-dim 32 --h-dim 256 64 --labels classifier --score \
+        --checkpoint models/fused_run/M2_info_epoch_001_vloss_<...>.pt
 
 Checkpoints are plain state_dicts with the reference's keys: the reference's evaluate / reconstruct scripts load them.
 Differences from the scripts, all deliberate: the batch size is a flag (the fused step is meant for thousands of
@@ -71,6 +78,12 @@ def main():
     ap.add_argument("--alpha", type=float, default=0.0, help="M2_info: weight of BCE(classifier(x), y) in enc_loss")
     ap.add_argument("--beta", type=float, default=10.0, help="M2_info: weight of the adversarial -BCE(auxiliary(z), y) in enc_loss")
     ap.add_argument("--gamma", type=float, default=1.0, help="M2_info: weight of aux_loss = BCE(auxiliary(z.detach()), y)")
+    ap.add_argument("--decoder-label", choices=["truth", "classifier"], default="truth",
+                    help="M2_info: what the decoder is conditioned on, the true label or the classifier's soft output (training_M2_info_vad_pretrain.py:162-163)")
+    ap.add_argument("--aux-enc", choices=["bce", "uniform", "entropy"], default="bce",
+                    help="M2_info: the adversarial term on the encoder, binary_cross_entropy against the label, _v2 (targets 0.5) or _v3 (the entropy)")
+    ap.add_argument("--init-classifier", default=None, metavar="CKPT",
+                    help="M2_info: load the keys containing enc_dec_clf.classifier from this state_dict, strict=False (training_M2_info_vad_pretrain.py:102-113)")
     ap.add_argument("--out", default="models/fused_run")
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
@@ -91,8 +104,17 @@ def main():
     dims = dict(x_dim=513, y_dim=y_dim, z_dim=a.z_dim, h_dim=tuple(a.h_dim))
     kw = dict(batch=min(a.batch, len(train)), precision=a.precision, lr=a.lr, seed=a.seed)
     if a.model == "M2_info":                        # the resident step at the reference geometry, csrc/train_info.hip at any other covered size
-        tr = make_info_trainer(dims, alpha=a.alpha, beta=a.beta, gamma=a.gamma, **kw)
+        tr = make_info_trainer(dims, alpha=a.alpha, beta=a.beta, gamma=a.gamma, dec_label=a.decoder_label, aux_enc=a.aux_enc, **kw)
+        if a.init_classifier:
+            sd = torch.load(a.init_classifier, map_location="cpu")
+            sd = {k: v for k, v in sd.items() if "enc_dec_clf.classifier" in k}
+            if not sd:
+                ap.error(f"--init-classifier: no key of {a.init_classifier} contains enc_dec_clf.classifier")
+            tr.load_state_dict(sd, strict=False)
+            print(f"classifier initialised from {a.init_classifier}: {len(sd)} tensors")
     else:
+        if a.decoder_label != "truth" or a.aux_enc != "bce" or a.init_classifier:
+            ap.error("--decoder-label, --aux-enc and --init-classifier apply to --model M2_info")
         tr = make_trainer(a.model, dims, **kw)
     tv = tr.fork(min(a.batch, len(valid)))
     train_trainers, valid_trainers = [tr], [tv]

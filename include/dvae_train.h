@@ -308,14 +308,29 @@ int dvae_train_clf_eval(const dvae_train_clf_plan_t* plan, void* ws, const float
  *   one Adam update over all 26 tensors at the same step count (the script's two optimizers share their hyper-parameters);
  *   losses8 = {ELBO, recon, KL, enc_loss, classif_loss, aux_loss, aux_enc_loss, 0}, means over the B frames (the order of dvae_train_apply);
  *   the same inputs give the same bits (no atomics on floats; slabs and partial sums in a fixed order);
- *   26 tensors in DeepGenerativeModel_v5.state_dict() order, each at a 256-byte aligned offset of the flat buffers. */
+ *   26 tensors in DeepGenerativeModel_v5.state_dict() order, each at a 256-byte aligned offset of the flat buffers.
+ * Two independent options (dvae_train_info_plan_mode; mode 0 is the contract above) give the loop body of
+ * scripts/training_M2_info_vad_pretrain.py:162-200 and its kin.  With p_c = clf(x), p_a = aux(z):
+ *   DVAE_INFO_DEC_CLASSIFIER  the decoder input is [z | p_c] instead of [z | y]: decoder layer 1 has dW = dpre_d1^T [z | p_c], and the
+ *              reconstruction gradient reaches the classifier through its label columns: d enc_loss / d p_c = alpha dBCE / d p_c +
+ *              dpre_d1 D1[:, z : z + y], then p_c (1 - p_c) and the relu masks.  With alpha = 0 that is the classifier's only gradient;
+ *   DVAE_INFO_AUX_UNIFORM / DVAE_INFO_AUX_ENTROPY  the adversarial term of enc_loss is V(p_a) instead of BCE(p_a, y):
+ *              enc_loss = ELBO + alpha BCE(p_c, y) - beta V, aux_loss = gamma BCE(p_a, y), losses8[6] = beta V, with
+ *              V = binary_cross_entropy_v2 (targets 0.5; d V / d p = -0.5 / (p + eps) + 0.5 / (1 - p + eps)) or binary_cross_entropy_v3
+ *              (targets p_a, the entropy; d V / d p = -[log(p + eps) + p / (p + eps) - log(1 - p + eps) - (1 - p) / (1 - p + eps)]), each a
+ *              mean over the B frames of a sum over the y_dim columns, eps = elbo_eps.  dz = dpre_d1 D1[:, :z] - beta dV / dz; the auxiliary
+ *              tensors receive gamma dBCE - beta dV: two output gradients through the same relu masks; beta = 0 still divides nothing.
+ *   One Adam update, three launches and the same bits from the same inputs, as in mode 0. */
+#define DVAE_INFO_DEC_CLASSIFIER 1
+#define DVAE_INFO_AUX_UNIFORM    2
+#define DVAE_INFO_AUX_ENTROPY    4
 typedef struct {
     /* inputs (echoed) */
     int32_t y_dim, z_dim, h1, h2;
     int32_t ksplit;              /* frame slices of the weight-gradient reduction = slabs the apply kernel sums (at most 16) */
     int32_t n_tensors;           /* 26 */
-    int32_t launches_per_step;   /* 3, whatever the geometry and B */
-    int32_t reserved0;
+    int32_t launches_per_step;   /* 3, whatever the geometry, B and the mode */
+    int32_t info_mode;           /* DVAE_INFO_* bits; 0 from dvae_train_info_plan */
     int64_t B;                   /* frames per step */
     int64_t n_params;            /* flat length in floats (with alignment gaps) */
     int64_t tensor_offset[DVAE_TRAIN_MAX_TENSORS];      /* in floats */
@@ -340,6 +355,9 @@ typedef struct {
 
 /* Host only (callable without a GPU).  ksplit_hint 0 = choose.  DVAE_E_BADARG naming the limits for a size outside them. */
 int dvae_train_info_plan(int y_dim, int z_dim, int h1, int h2, int64_t B, int ksplit_hint, dvae_train_info_plan_t* plan);
+/* The same with a mode (a set of DVAE_INFO_* bits; 0 equals dvae_train_info_plan field for field): stash and workspace depend on it.  Host
+ * only.  DVAE_E_BADARG naming the choices for an unknown bit or both DVAE_INFO_AUX_* bits at once. */
+int dvae_train_info_plan_mode(int y_dim, int z_dim, int h1, int h2, int64_t B, int ksplit_hint, int mode, dvae_train_info_plan_t* plan);
 /* One-time setup of `ws` (item table, packed weight copies from `params`); synchronises the stream once. */
 int dvae_train_info_init(const dvae_train_info_plan_t* plan, const float* params, void* ws, void* stream);
 /* Rebuild both packed weight copies after `params` was written from outside. */
