@@ -444,6 +444,33 @@ extern "C" int dvae_train_clf_apply(const dvae_train_clf_plan_t* plan, float* pa
     return launch_apply(plan, L, a, (char*)ws, true, true, true, (long long*)counts4, (hipStream_t)stream);
 }
 
+extern "C" int dvae_train_clf_reduce(const dvae_train_clf_plan_t* plan, void* ws, float* flat, int accumulate, float weight, float* losses3,
+                                     int64_t* counts4, void* stream) {
+    CLayout L;
+    if (int rc = plan_layout("train_clf_reduce", plan, L)) return rc;
+    if (int rc = check_reduce_args("train_clf_reduce", ws, flat, accumulate, weight)) return rc;
+    DVAE_CHECK_ARG(losses3 && counts4, "train_clf_reduce: null pointer");
+    GReduceArgs g;
+    memset(&g, 0, sizeof(g));
+    g.f.a = apply_args(plan, L, nullptr, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, losses3);
+    make_tensors(L, g.f.t);
+    g.f.ws = (float*)ws; g.f.finalize = 1;
+    g.f.cnt_partials = (const long long*)((char*)ws + L.o_counts); g.f.cnt_wgs = (int)L.rows_grid; g.f.counts4 = (long long*)counts4;
+    g.f.cnt_accum = (long long*)(uintptr_t)plan->count_accum;
+    g.flat = flat; g.accumulate = accumulate; g.weight = weight;
+    return launch_reduce_table(g, (hipStream_t)stream);
+}
+
+extern "C" int dvae_train_clf_apply_flat(const dvae_train_clf_plan_t* plan, float* params, float* m, float* v, void* ws, const float* flat, int step,
+                                         double lr, double beta1, double beta2, double adam_eps, double grad_scale, void* stream) {
+    CLayout L;
+    if (int rc = plan_layout("train_clf_apply_flat", plan, L)) return rc;
+    if (int rc = check_apply_flat_args("train_clf_apply_flat", params, m, v, ws, flat, step, lr, grad_scale)) return rc;
+    ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, nullptr);
+    a.slabs = flat; a.nslabs = 1;                       // the flat gradient is the one slab
+    return launch_apply(plan, L, a, (char*)ws, true, true, false, nullptr, (hipStream_t)stream);
+}
+
 extern "C" int dvae_train_clf_step(const dvae_train_clf_plan_t* plan, float* params, float* m, float* v, void* ws, const float* x, int64_t ldx,
                                    const float* y, int64_t ldy, float bce_eps, int step, double lr, double beta1, double beta2, double adam_eps,
                                    float* losses3, int64_t* counts4, void* stream) {

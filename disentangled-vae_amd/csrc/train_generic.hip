@@ -492,6 +492,33 @@ __global__ __launch_bounds__(256) void train_generic_wgrad_kernel(const GWgradAr
     }
 }
 
+// the finalising workgroup of the apply and reduce launches: loss scalars, the classifier's counts, the M2_info fifth sum (256 threads,
+// every thread calls)
+__device__ __forceinline__ void finalize_step(const GApplyArgs& g, double (*red)[4]) {
+    fused::finalize_losses(g.a, red);
+    if (g.cnt_partials && threadIdx.x < 4) {            // integers, workgroup order
+        long long c = 0;
+        for (int i = 0; i < g.cnt_wgs; ++i) c += g.cnt_partials[4 * (int64_t)i + threadIdx.x];
+        g.counts4[threadIdx.x] = c;
+        if (g.cnt_accum) g.cnt_accum[threadIdx.x] += c;
+    }
+    if (g.v_partials) {                                 // one partial a thread: workgroup order within a wave's sum, waves in order
+        static_assert(G_ROWS_GRID <= 256, "one thread of the finalising workgroup per rows workgroup");
+        __syncthreads();                                // write_losses has read `red`
+        double v = (int)threadIdx.x < g.a.npartials ? g.v_partials[threadIdx.x] : 0.0;
+        v = wave_sum(v);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][0] = v;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const float bv = (float)((red[0][0] + red[1][0] + red[2][0] + red[3][0]) / (double)g.a.B);
+            const float aux_enc = g.a.beta * bv;
+            g.a.losses3[3] = g.a.losses3[0] + g.a.losses3[4] - aux_enc;      // enc_loss = ELBO + classif_loss - beta V
+            g.a.losses3[6] = aux_enc;
+            if (g.v_accum) for (int q = 0; q < 8; ++q) g.v_accum[q] += (double)g.a.losses3[q];
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // apply kernel: optimizer step, both packed copies, loss scalars (GApplyArgs: train_generic.hpp; the classifier step launches it too,
 // with its confusion counts to finalise)
@@ -524,30 +551,67 @@ __global__ __launch_bounds__(256) void train_generic_apply_kernel(const GApplyAr
             }
         }
     }
-    if (g.finalize && blockIdx.x == 0) {
-        fused::finalize_losses(g.a, red);
-        if (g.cnt_partials && threadIdx.x < 4) {            // integers, workgroup order
-            long long c = 0;
-            for (int i = 0; i < g.cnt_wgs; ++i) c += g.cnt_partials[4 * (int64_t)i + threadIdx.x];
-            g.counts4[threadIdx.x] = c;
-            if (g.cnt_accum) g.cnt_accum[threadIdx.x] += c;
-        }
-        if (g.v_partials) {                                 // one partial a thread: workgroup order within a wave's sum, waves in order
-            static_assert(G_ROWS_GRID <= 256, "one thread of the finalising workgroup per rows workgroup");
-            __syncthreads();                                // write_losses has read `red`
-            double v = (int)threadIdx.x < g.a.npartials ? g.v_partials[threadIdx.x] : 0.0;
-            v = wave_sum(v);
-            if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][0] = v;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                const float bv = (float)((red[0][0] + red[1][0] + red[2][0] + red[3][0]) / (double)g.a.B);
-                const float aux_enc = g.a.beta * bv;
-                g.a.losses3[3] = g.a.losses3[0] + g.a.losses3[4] - aux_enc;      // enc_loss = ELBO + classif_loss - beta V
-                g.a.losses3[6] = aux_enc;
-                if (g.v_accum) for (int q = 0; q < 8; ++q) g.v_accum[q] += (double)g.a.losses3[q];
-            }
-        }
+    if (g.finalize && blockIdx.x == 0) finalize_step(g, red);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// reduce kernel (GReduceArgs: train_generic.hpp): the frame-slice slabs of one micro-batch summed into the flat gradient accumulator, for
+// gradient accumulation (reduce K times, apply once) and data parallelism (reduce, all-reduce, apply).  A thread owns four consecutive
+// floats: every 16-byte slab load (and the accumulator's, when it is read) is issued before the first addition, the additions run in
+// slab order -- fused::slab_sum_at's order, element for element --, then weight * sum (its own rounding: 1.0 leaves the bits alone),
+// then accumulator + that, one 16-byte store.  No atomics, and no LDS outside the finalising workgroup: the same inputs give the same
+// bits.  With accumulate 0 the accumulator is written and never read; the alignment gaps between tensors receive zeros in every call,
+// whatever the slabs hold there.  The workgroup behind the last block of elements finalises the micro-batch's loss scalars.
+template <int NS>
+__device__ __forceinline__ f32x4 slab_sum4(const float* slabs, int64_t stride, int64_t i4) {
+    f32x4 part[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) part[k] = *reinterpret_cast<const f32x4*>(slabs + k * stride + i4);       // independent loads
+    f32x4 t = part[0];
+#pragma unroll
+    for (int k = 1; k < NS; ++k) t += part[k];                                                              // fixed order
+    return t;
+}
+
+__global__ __launch_bounds__(256) void train_generic_reduce_kernel(const GReduceArgs g) {
+    __shared__ double red[4][4];
+    if (blockIdx.x == gridDim.x - 1) {                  // (workgroup-uniform)
+        if (g.f.finalize) finalize_step(g.f, red);
+        return;
     }
+    const int64_t i4 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i4 >= g.f.a.n_params) return;                   // (n_params is a multiple of 64)
+    int nv = 0;                                         // this thread's floats that belong to a tensor; the others are the gap behind it
+    const int i = (int)i4;                              // (the 26 tensors hold far fewer than 2^31 floats: 32-bit compares, a third of the ALU work)
+#pragma unroll
+    for (int k = 0; k < G_NT; ++k) {
+        const int off = (int)g.f.t[k].off, n = g.f.t[k].rows * g.f.t[k].cols;     // (unused entries: n = 0)
+        if ((unsigned)(i - off) < (unsigned)n) nv = off + n - i < 4 ? off + n - i : 4;
+    }
+    f32x4 old = {0.f, 0.f, 0.f, 0.f};
+    if (g.accumulate) old = *reinterpret_cast<const f32x4*>(g.flat + i4);
+    const float* sl = g.f.a.slabs;
+    const int64_t st = g.f.a.slab_stride;
+    const int ns = g.f.a.nslabs;
+    f32x4 t;
+    switch (ns) {                                       // the exact slab count (wave-uniform): no load beyond the slabs there are
+#define DVAE_SLABS(n) case n: t = slab_sum4<n>(sl, st, i4); break;
+        DVAE_SLABS(1) DVAE_SLABS(2) DVAE_SLABS(3) DVAE_SLABS(4) DVAE_SLABS(5) DVAE_SLABS(6) DVAE_SLABS(7) DVAE_SLABS(8)
+        DVAE_SLABS(9) DVAE_SLABS(10) DVAE_SLABS(11) DVAE_SLABS(12) DVAE_SLABS(13) DVAE_SLABS(14) DVAE_SLABS(15) DVAE_SLABS(16)
+#undef DVAE_SLABS
+        default:
+            t = *reinterpret_cast<const f32x4*>(sl + i4);
+            for (int k = 1; k < ns; ++k) t += *reinterpret_cast<const f32x4*>(sl + k * st + i4);
+    }
+    f32x4 out;
+    {
+#pragma clang fp contract(off)
+        const f32x4 wt = t * g.weight;
+        out = g.accumulate ? old + wt : wt;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) if (j >= nv) out[j] = 0.f;
+    *reinterpret_cast<f32x4*>(g.flat + i4) = out;
 }
 
 int launch_wgrad_table(const GWgradArgs& g, int n_items, hipStream_t s) {
@@ -560,6 +624,31 @@ int launch_apply_table(const GApplyArgs& g, hipStream_t s) {
     const int64_t blocks = g.a.n_params > 0 ? (g.a.n_params + 255) / 256 : 1;
     hipLaunchKernelGGL(train_generic_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g);
     DVAE_LAUNCH_OK("train_generic_apply_kernel");
+    return 0;
+}
+
+int launch_reduce_table(const GReduceArgs& g, hipStream_t s) {
+    DVAE_CHECK_ARG(g.f.a.n_params >= 0 && g.f.a.n_params < ((int64_t)1 << 31) && g.f.a.n_params % 64 == 0,
+                   "train_generic_reduce_kernel: %lld parameters (a multiple of 64 below 2^31: the kernel indexes tensors in 32 bits)", (long long)g.f.a.n_params);
+    const int64_t blocks = (g.f.a.n_params / 4 + 255) / 256 + 1;         // + the finalising workgroup
+    hipLaunchKernelGGL(train_generic_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g);
+    DVAE_LAUNCH_OK("train_generic_reduce_kernel");
+    return 0;
+}
+
+int check_reduce_args(const char* who, const void* ws, const float* flat, int accumulate, float weight) {
+    DVAE_CHECK_ARG(ws && flat, "%s: null pointer", who);
+    DVAE_CHECK_ARG(((uintptr_t)flat & 15) == 0, "%s: the flat gradient must be 16-byte aligned", who);
+    DVAE_CHECK_ARG(accumulate == 0 || accumulate == 1, "%s: accumulate %d (0: overwrite the flat gradient, 1: add to it)", who, accumulate);
+    DVAE_CHECK_ARG(isfinite(weight), "%s: the weight of the micro-batch is not finite", who);
+    return 0;
+}
+
+int check_apply_flat_args(const char* who, const float* params, const float* m, const float* v, const void* ws, const float* flat, int step,
+                          double lr, double grad_scale) {
+    DVAE_CHECK_ARG(params && m && v && ws && flat, "%s: null pointer", who);
+    DVAE_CHECK_ARG(step >= 1, "%s: step %d (1-based)", who, step);
+    DVAE_CHECK_ARG(isfinite(grad_scale) && isfinite(lr), "%s: grad_scale / lr is not finite", who);
     return 0;
 }
 
@@ -735,6 +824,31 @@ extern "C" int dvae_train_generic_apply(const dvae_train_generic_plan_t* plan, f
     DVAE_CHECK_ARG(step >= 1, "train_generic_apply: step %d (1-based)", step);
     const ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, losses3);
     return launch_apply(L, a, (char*)ws, true, true, true, (hipStream_t)stream);
+}
+
+extern "C" int dvae_train_generic_reduce(const dvae_train_generic_plan_t* plan, void* ws, float* flat, int accumulate, float weight, float* losses3,
+                                         void* stream) {
+    GLayout L;
+    if (int rc = plan_layout("train_generic_reduce", plan, L)) return rc;
+    if (int rc = check_reduce_args("train_generic_reduce", ws, flat, accumulate, weight)) return rc;
+    DVAE_CHECK_ARG(losses3, "train_generic_reduce: null pointer");
+    GReduceArgs g;
+    memset(&g, 0, sizeof(g));
+    g.f.a = apply_args(plan, L, nullptr, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, losses3);
+    make_tensors(L, g.f.t);
+    g.f.ws = (float*)ws; g.f.finalize = 1;
+    g.flat = flat; g.accumulate = accumulate; g.weight = weight;
+    return launch_reduce_table(g, (hipStream_t)stream);
+}
+
+extern "C" int dvae_train_generic_apply_flat(const dvae_train_generic_plan_t* plan, float* params, float* m, float* v, void* ws, const float* flat,
+                                             int step, double lr, double beta1, double beta2, double adam_eps, double grad_scale, void* stream) {
+    GLayout L;
+    if (int rc = plan_layout("train_generic_apply_flat", plan, L)) return rc;
+    if (int rc = check_apply_flat_args("train_generic_apply_flat", params, m, v, ws, flat, step, lr, grad_scale)) return rc;
+    ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, nullptr);
+    a.slabs = flat; a.nslabs = 1;                       // the flat gradient is the one slab
+    return launch_apply(L, a, (char*)ws, true, true, false, (hipStream_t)stream);
 }
 
 extern "C" int dvae_train_generic_step(const dvae_train_generic_plan_t* plan, float* params, float* m, float* v, void* ws, const float* x, int64_t ldx,

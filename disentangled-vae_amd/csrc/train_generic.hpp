@@ -136,12 +136,28 @@ struct GApplyArgs {
     const double* v_partials; double* v_accum;
 };
 
-static_assert(sizeof(GWgradArgs) <= G_KERNARG_MAX && sizeof(GApplyArgs) <= G_KERNARG_MAX, "the tables travel as kernel arguments");
+// reduce kernel (train_generic.hip: train_generic_reduce_kernel), between _grads and _apply_flat: flat = [flat +] weight * (the slabs of
+// f.a summed in slab order), zeros in the alignment gaps between the tensors of f.t; one more workgroup finalises the micro-batch's loss
+// scalars (and counts) exactly as the apply kernel's finalising workgroup does (f.adam is unused, f.finalize 1)
+struct GReduceArgs {
+    GApplyArgs f;
+    float* flat;
+    int accumulate;
+    float weight;
+};
 
-// the two launches, for a caller that has filled the tables (unused entries zeroed): n_items workgroups; one thread a parameter of
-// g.a.n_params (0: one workgroup that only finalises)
+static_assert(sizeof(GWgradArgs) <= G_KERNARG_MAX && sizeof(GApplyArgs) <= G_KERNARG_MAX && sizeof(GReduceArgs) <= G_KERNARG_MAX,
+              "the tables travel as kernel arguments");
+
+// the launches, for a caller that has filled the tables (unused entries zeroed): n_items workgroups; one thread a parameter of
+// g.a.n_params (0: one workgroup that only finalises); one thread per four floats of g.f.a.n_params and one finalising workgroup
 int launch_wgrad_table(const GWgradArgs& g, int n_items, hipStream_t s);
 int launch_apply_table(const GApplyArgs& g, hipStream_t s);
+int launch_reduce_table(const GReduceArgs& g, hipStream_t s);
+// what the _reduce / _apply_flat entry points of the three steps refuse before anything touches the device (0: fine)
+int check_reduce_args(const char* who, const void* ws, const float* flat, int accumulate, float weight);
+int check_apply_flat_args(const char* who, const float* params, const float* m, const float* v, const void* ws, const float* flat, int step,
+                          double lr, double grad_scale);
 // dynamic LDS past the default 64 KB limit for a rows kernel: raised once per device (done: the caller's flags, one per device)
 int raise_lds_limit(const void* kernel, const char* name, int64_t lds_bytes, bool (&done)[64]);
 constexpr int64_t G_LDS_MAX = 160 * 1024;

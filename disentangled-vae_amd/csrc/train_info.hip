@@ -996,6 +996,35 @@ extern "C" int dvae_train_info_apply(const dvae_train_info_plan_t* plan, float* 
     return launch_apply(plan, L, a, (char*)ws, true, true, true, (hipStream_t)stream);
 }
 
+extern "C" int dvae_train_info_reduce(const dvae_train_info_plan_t* plan, void* ws, float* flat, int accumulate, float weight, float* losses8,
+                                      void* stream) {
+    ILayout L;
+    if (int rc = plan_layout("train_info_reduce", plan, L)) return rc;
+    if (int rc = check_reduce_args("train_info_reduce", ws, flat, accumulate, weight)) return rc;
+    DVAE_CHECK_ARG(losses8, "train_info_reduce: null pointer");
+    GReduceArgs g;
+    memset(&g, 0, sizeof(g));
+    g.f.a = apply_args(plan, L, nullptr, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, losses8);
+    make_tensors(L, g.f.t);
+    if (L.mode & MODE_AUX) {                            // (as launch_apply)
+        g.f.v_partials = (const double*)((char*)ws + L.o_partials) + 4 * L.rows_grid;
+        g.f.v_accum = (double*)(uintptr_t)plan->loss_accum;
+    }
+    g.f.ws = (float*)ws; g.f.finalize = 1;
+    g.flat = flat; g.accumulate = accumulate; g.weight = weight;
+    return launch_reduce_table(g, (hipStream_t)stream);
+}
+
+extern "C" int dvae_train_info_apply_flat(const dvae_train_info_plan_t* plan, float* params, float* m, float* v, void* ws, const float* flat, int step,
+                                          double lr, double beta1, double beta2, double adam_eps, double grad_scale, void* stream) {
+    ILayout L;
+    if (int rc = plan_layout("train_info_apply_flat", plan, L)) return rc;
+    if (int rc = check_apply_flat_args("train_info_apply_flat", params, m, v, ws, flat, step, lr, grad_scale)) return rc;
+    ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, nullptr);
+    a.slabs = flat; a.nslabs = 1;                       // the flat gradient is the one slab
+    return launch_apply(plan, L, a, (char*)ws, true, true, false, (hipStream_t)stream);
+}
+
 extern "C" int dvae_train_info_step(const dvae_train_info_plan_t* plan, float* params, float* m, float* v, void* ws, const float* x, int64_t ldx,
                                     const float* y, int64_t ldy, const float* eps_noise, float elbo_eps, int step, double lr, double beta1,
                                     double beta2, double adam_eps, float* losses8, void* stream) {

@@ -277,6 +277,29 @@ class ClassifierTrainer:
             N.check(self.lib.dvae_train_clf_grads(ctypes.byref(self.plan), N.ptr(self.ws), N.ptr(x), N.ld(x), N.ptr(y), N.ld(y), self.bce_eps,
                                                   N.stream()), "dvae_train_clf_grads")
 
+    # ---- accumulate.AccumulatedStep ----
+    def _micro(self, flat, accumulate, weight, x, y, rows):
+        """One micro-batch: rows + weight-gradient + reduce launches; the slabs go into `flat` (accumulate 0: overwritten), the
+        micro-batch's BCE into self.losses and its counts into self.counts."""
+        x, y = self._check_inputs(x, y, rows)
+        self._sync_copies()
+        with torch.cuda.device(self.device):
+            N.check(self.lib.dvae_train_clf_grads(ctypes.byref(self.plan), N.ptr(self.ws), N.ptr(x), N.ld(x), N.ptr(y), N.ld(y), self.bce_eps,
+                                                  N.stream()), "dvae_train_clf_grads")
+            N.check(self.lib.dvae_train_clf_reduce(ctypes.byref(self.plan), N.ptr(self.ws), N.ptr(flat), int(accumulate), float(weight),
+                                                   N.ptr(self._losses3), N.ptr(self.counts), N.stream()), "dvae_train_clf_reduce")
+        return self.losses
+
+    def _apply_flat(self, flat, grad_scale):
+        """One Adam step on g = grad_scale * flat; counts as a step exactly as step() does."""
+        self.step_count += 1
+        self._shared["version"] += 1
+        self._copy_version = self._shared["version"]          # the apply kernel rewrites every element of this trainer's packed copies
+        with torch.cuda.device(self.device):
+            N.check(self.lib.dvae_train_clf_apply_flat(ctypes.byref(self.plan), N.ptr(self._params), N.ptr(self._m), N.ptr(self._v),
+                                                       N.ptr(self.ws), N.ptr(flat), self.step_count, self.lr, self.betas[0], self.betas[1],
+                                                       self.adam_eps, float(grad_scale), N.stream()), "dvae_train_clf_apply_flat")
+
     def accumulate_losses(self, buf):
         """Running sum for epoch logging without a host sync per step: `buf` is a float64 CUDA tensor of 8 elements (or None to stop);
         every step() / evaluate() adds its BCE to buf[0] on the device (buf[1] receives it too: the apply kernel's second scalar)."""

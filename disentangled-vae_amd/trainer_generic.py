@@ -60,7 +60,8 @@ class GenericTrainer:
     def __init__(self, model, dims, params=None, batch=128, device="cuda:0", lr=1e-4, betas=(0.9, 0.999), adam_eps=1e-8, elbo_eps=1e-8,
                  seed=None, ksplit=0, share=None, precision="fp32", world=1):
         if int(world) != 1:
-            raise NotImplementedError(f"data-parallel training is not built on the generic step ({LIMITS}); got world={world}")
+            raise NotImplementedError(f"data-parallel training is not built on the generic step ({LIMITS}); got world={world}: wrap a "
+                                      "one-GPU trainer per rank in accumulate.AccumulatedStep(trainer, process_group)")
         self.plan = make_plan(model, dims, batch, precision, ksplit)          # refuses before anything touches the device
         if not torch.cuda.is_available():
             raise RuntimeError("GenericTrainer needs the MI355X HIP path (no CPU fallback)")
@@ -266,6 +267,30 @@ class GenericTrainer:
         with torch.cuda.device(self.device):
             N.check(self.lib.dvae_train_generic_grads(ctypes.byref(self.plan), N.ptr(self.ws), N.ptr(x), N.ld(x), yp, ldy, N.ptr(eps_noise),
                                                       self.elbo_eps, N.stream()), "dvae_train_generic_grads")
+
+    # ---- accumulate.AccumulatedStep ----
+    def _micro(self, flat, accumulate, weight, x, y, eps_noise, rows):
+        """One micro-batch: rows + weight-gradient + reduce launches; the slabs go into `flat` (accumulate 0: overwritten) and the
+        micro-batch's losses into self.losses."""
+        self._check_inputs(x, y, rows, eps_noise)
+        self._sync_copies()
+        x, y, yp, ldy, eps_noise = self._inputs(x, y, eps_noise)
+        with torch.cuda.device(self.device):
+            N.check(self.lib.dvae_train_generic_grads(ctypes.byref(self.plan), N.ptr(self.ws), N.ptr(x), N.ld(x), yp, ldy, N.ptr(eps_noise),
+                                                      self.elbo_eps, N.stream()), "dvae_train_generic_grads")
+            N.check(self.lib.dvae_train_generic_reduce(ctypes.byref(self.plan), N.ptr(self.ws), N.ptr(flat), int(accumulate), float(weight),
+                                                       N.ptr(self.losses), N.stream()), "dvae_train_generic_reduce")
+        return self.losses
+
+    def _apply_flat(self, flat, grad_scale):
+        """One Adam step on g = grad_scale * flat; counts as a step exactly as step() does."""
+        self.step_count += 1
+        self._shared["version"] += 1
+        self._copy_version = self._shared["version"]          # the apply kernel rewrites every element of this trainer's packed copies
+        with torch.cuda.device(self.device):
+            N.check(self.lib.dvae_train_generic_apply_flat(ctypes.byref(self.plan), N.ptr(self._params), N.ptr(self._m), N.ptr(self._v),
+                                                           N.ptr(self.ws), N.ptr(flat), self.step_count, self.lr, self.betas[0], self.betas[1],
+                                                           self.adam_eps, float(grad_scale), N.stream()), "dvae_train_generic_apply_flat")
 
     def accumulate_losses(self, buf):
         """Running sums for epoch logging without a host sync per step: `buf` is a float64 CUDA tensor of 8 elements (or None to stop);

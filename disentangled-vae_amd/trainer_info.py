@@ -292,6 +292,30 @@ class InfoTrainer:
             N.check(self.lib.dvae_train_info_grads(ctypes.byref(self.plan), N.ptr(self.ws), N.ptr(x), N.ld(x), N.ptr(y), N.ld(y), N.ptr(eps_noise),
                                                    self.elbo_eps, N.stream()), "dvae_train_info_grads")
 
+    # ---- accumulate.AccumulatedStep ----
+    def _micro(self, flat, accumulate, weight, x, y, eps_noise, rows):
+        """One micro-batch: rows + weight-gradient + reduce launches; the slabs go into `flat` (accumulate 0: overwritten) and the
+        micro-batch's eight losses into self.losses."""
+        self._check_inputs(x, y, rows, eps_noise)
+        self._sync_copies()
+        x, y, eps_noise = self._inputs(x, y, eps_noise)
+        with torch.cuda.device(self.device):
+            N.check(self.lib.dvae_train_info_grads(ctypes.byref(self.plan), N.ptr(self.ws), N.ptr(x), N.ld(x), N.ptr(y), N.ld(y), N.ptr(eps_noise),
+                                                   self.elbo_eps, N.stream()), "dvae_train_info_grads")
+            N.check(self.lib.dvae_train_info_reduce(ctypes.byref(self.plan), N.ptr(self.ws), N.ptr(flat), int(accumulate), float(weight),
+                                                    N.ptr(self.losses), N.stream()), "dvae_train_info_reduce")
+        return self.losses
+
+    def _apply_flat(self, flat, grad_scale):
+        """One Adam step on g = grad_scale * flat; counts as a step exactly as step() does."""
+        self.step_count += 1
+        self._shared["version"] += 1
+        self._copy_version = self._shared["version"]          # the apply kernel rewrites every element of this trainer's packed copies
+        with torch.cuda.device(self.device):
+            N.check(self.lib.dvae_train_info_apply_flat(ctypes.byref(self.plan), N.ptr(self._params), N.ptr(self._m), N.ptr(self._v),
+                                                        N.ptr(self.ws), N.ptr(flat), self.step_count, self.lr, self.betas[0], self.betas[1],
+                                                        self.adam_eps, float(grad_scale), N.stream()), "dvae_train_info_apply_flat")
+
     def accumulate_losses(self, buf):
         """Running sums for epoch logging without a host sync per step: `buf` is a float64 CUDA tensor of 8 elements (or None to stop);
         every step() / evaluate() adds its loss scalars to its first seven on the device."""
@@ -327,7 +351,8 @@ def make_info_trainer(dims, generic=False, dec_label="truth", aux_enc="bce", **k
     if kw.get("precision", "fp32") != "fp32":
         raise NotImplementedError(f"precision {kw['precision']!r} exists on the resident step only; {LIMITS}")
     if int(kw.get("world", 1)) != 1 or kw.get("process_group") is not None:
-        raise NotImplementedError(f"data-parallel training is not built on the generic step (got world={kw.get('world', 1)}); {LIMITS}")
+        raise NotImplementedError(f"data-parallel training is not built on the generic step (got world={kw.get('world', 1)}); {LIMITS}: wrap a "
+                                  "one-GPU trainer per rank in accumulate.AccumulatedStep(trainer, process_group)")
     for k in ("precision", "world", "process_group"):
         kw.pop(k, None)
     return InfoTrainer(dims, dec_label=dec_label, aux_enc=aux_enc, **kw)

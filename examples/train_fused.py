@@ -16,6 +16,13 @@ trainer_info.py: make_info_trainer, the same choice for DeepGenerativeModel_v5).
     python examples/enhance_mcem.py --synthetic 3 --z-dim 32 --h-dim 256 64 --labels classifier --score \
         --checkpoint models/fused_run/M2_info_epoch_001_vloss_<...>.pt
 
+Gradient accumulation and data parallelism on the generic steps (disentangled-vae_amd/accumulate.py: AccumulatedStep):
+
+    # one optimizer step per 4 micro-batches of --batch frames (the stash is sized by --batch): the same run as --batch 32768
+    python examples/train_fused.py --model M2_info --synthetic 200000 --z-dim 32 --h-dim 256 64 --batch 8192 --accumulate 4
+    # 8 ranks, one per GPU, started from here; each brings --accumulate x --batch frames to an optimizer step
+    python examples/train_fused.py --model M2 --synthetic 2000000 --z-dim 32 --h-dim 256 64 --gpus 8
+
 Checkpoints are plain state_dicts with the reference's keys: the reference's evaluate / reconstruct scripts load them.
 Differences from the scripts, all deliberate: the batch size is a flag (the fused step is meant for thousands of
 frames per step; `--batch 128` reproduces the scripts' setting), std_norm is not offered (off in every script).
@@ -33,6 +40,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 make_trainer = importlib.import_module("disentangled-vae_amd.trainer").make_trainer
 make_info_trainer = importlib.import_module("disentangled-vae_amd.trainer_info").make_info_trainer
 DeviceFrames = importlib.import_module("disentangled-vae_amd.frames").DeviceFrames
+AccumulatedStep = importlib.import_module("disentangled-vae_amd.accumulate").AccumulatedStep
 
 
 def synthetic(n, y_dim, seed):
@@ -62,6 +70,81 @@ def run_epoch(data, trainers, train, shuffle):   # trainers: [main, optional for
     return (tot[:3] / nb).cpu().tolist()
 
 
+def micro_sizes(n, batch):
+    """n frames as micro-batches of `batch` and a shorter last one."""
+    return [batch] * (n // batch) + ([n % batch] if n % batch else [])
+
+
+def run_epoch_accumulated(data, acc, forks, batch, k, epoch, seed, log):
+    """One training pass with one optimizer step per k micro-batches of `batch` frames on every rank; the epoch's tail is a shorter
+    step whose last micro-batch runs on a fork.  With several ranks the permutation comes from a generator seeded alike on all of them,
+    rank r takes the r-th share of every step, and a tail that does not divide over the ranks loses at most world - 1 frames.
+    Returns the mean (ELBO, recon, KL) over the optimizer steps (and over the ranks)."""
+    world, rank = acc.world, acc.rank
+    gen = None
+    if world > 1:
+        gen = torch.Generator(device=data.device).manual_seed(seed * 1000003 + epoch)
+    tot = torch.zeros(3, dtype=torch.float64, device=data.device)
+    steps = 0
+    for rows in data.index_batches(world * k * batch, shuffle=True, generator=gen):
+        per = rows.shape[0] // world
+        if per * world != rows.shape[0]:
+            log(f"epoch {epoch}: the last step drops {rows.shape[0] - per * world} frames that do not divide over {world} ranks")
+        if per == 0:
+            break
+        mine = rows[rank * per:(rank + 1) * per]
+        acc.micro_batches = micro_sizes(per, batch)                  # announced: the default noise is that of one step on all these frames
+        lo = 0
+        for b in acc.micro_batches:
+            acc.micro(data.x, data.y, rows=mine[lo:lo + b].contiguous(), trainer=forked(acc.trainer, forks, b))
+            lo += b
+        tot += acc.apply()[:3]
+        steps += 1
+    return acc.mean_over_ranks(tot / max(steps, 1)).tolist()      # (the collective runs where the group's backend serves it)
+
+
+def forked(tr, forks, b):
+    """`tr` for its own batch size, otherwise its fork of b frames (one is kept: the tail of an epoch has one size)."""
+    if b == tr.B:
+        return tr
+    if b not in forks:
+        forks.clear()
+        forks[b] = tr.fork(b)
+    return forks[b]
+
+
+def run_validation_accumulated(data, acc, forks, group):
+    """The validation pass of a run whose optimizer step has `group` frames: the scripts' mean of batch means over batches of `group`
+    frames, each evaluated in pieces of at most one micro-batch (AccumulatedStep.evaluate), so that the workspace stays that of a
+    micro-batch and --accumulate K logs what --batch K times as large logs."""
+    tot = torch.zeros(3, dtype=torch.float64, device=data.device)
+    nb = 0
+    for rows in data.index_batches(group, shuffle=False):
+        tot += acc.evaluate(data.x, data.y, rows, lambda b: forked(acc.trainer, forks, b))[:3]
+        nb += 1
+    return (tot / nb).cpu().tolist()
+
+
+def launch_ranks(a):
+    """--gpus N with no launcher in the environment: N fresh ranks as a CHILD process, `python -m torch.distributed.run ... train_fused.py
+    <same arguments>`, started before this process has made a GPU call; nothing is exec'ed over a process that has."""
+    import socket
+    import subprocess
+    backend = os.environ.get("DVAE_DIST_BACKEND", "nccl")
+    ndev = torch.cuda.device_count()
+    if ndev < 1 or (backend == "nccl" and ndev < a.gpus):
+        sys.stderr.write(f"train_fused.py: --gpus {a.gpus} over RCCL needs {a.gpus} visible GPUs, this node shows {ndev}: RCCL ranks cannot share "
+                         "a device (DVAE_DIST_BACKEND=gloo rehearses the flow with the ranks sharing the visible devices)\n")
+        raise SystemExit(2)
+    with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={a.gpus}", "--master-addr", "127.0.0.1",
+           "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    sys.stderr.write("train_fused.py: starting the ranks: " + " ".join(cmd) + "\n")
+    raise SystemExit(subprocess.call(cmd, env=dict(os.environ)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=["M1", "M2", "M2_info"], default="M2")
@@ -86,7 +169,27 @@ def main():
                     help="M2_info: load the keys containing enc_dec_clf.classifier from this state_dict, strict=False (training_M2_info_vad_pretrain.py:102-113)")
     ap.add_argument("--out", default="models/fused_run")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--accumulate", type=int, default=1, metavar="K",
+                    help="generic steps: one optimizer step per K micro-batches of --batch frames (the workspace is sized by --batch)")
+    ap.add_argument("--gpus", type=int, default=1, metavar="N",
+                    help="generic steps: N data-parallel ranks, one per GPU, one all-reduce of the flat gradient per optimizer step")
     a = ap.parse_args()
+    if a.accumulate < 1 or a.gpus < 1:
+        ap.error("--accumulate and --gpus count from 1")
+    rank, world, pg, device = 0, 1, None, "cuda:0"
+    if a.gpus > 1:
+        if "WORLD_SIZE" not in os.environ:
+            launch_ranks(a)                         # (does not return)
+        import torch.distributed as dist
+        backend = os.environ.get("DVAE_DIST_BACKEND", "nccl")
+        local = int(os.environ.get("LOCAL_RANK", 0))
+        device = f"cuda:{local if backend == 'nccl' else local % max(torch.cuda.device_count(), 1)}"
+        torch.cuda.set_device(device)
+        dist.init_process_group(backend)
+        rank, world, pg = dist.get_rank(), dist.get_world_size(), dist.group.WORLD
+        if world != a.gpus:
+            ap.error(f"--gpus {a.gpus} under a launcher of {world} ranks")
+    accumulated = a.accumulate > 1 or world > 1
     if a.model == "M2_info":
         a.labels = "vad_labels"                     # scripts/training_M2_info_vad.py: VAD labels, alpha 0 / beta 10 / gamma 1
     y_dim = 0 if a.model == "M1" else (1 if a.labels == "vad_labels" else 513)
@@ -95,14 +198,16 @@ def main():
             ap.error("--y-dim applies to --synthetic data; with --h5 the label file decides")
         y_dim = a.y_dim
     if a.h5:
-        train, valid = DeviceFrames.from_hdf5(a.h5, "train"), DeviceFrames.from_hdf5(a.h5, "validation")
+        train, valid = DeviceFrames.from_hdf5(a.h5, "train", device), DeviceFrames.from_hdf5(a.h5, "validation", device)
     else:
         n = a.synthetic or 100000
-        train, valid = DeviceFrames(*synthetic(n, y_dim, 1)), DeviceFrames(*synthetic(max(n // 10, 1), y_dim, 2))
+        train, valid = DeviceFrames(*synthetic(n, y_dim, 1), device=device), DeviceFrames(*synthetic(max(n // 10, 1), y_dim, 2), device=device)
     if a.model == "M1":
         train.y = valid.y = None
     dims = dict(x_dim=513, y_dim=y_dim, z_dim=a.z_dim, h_dim=tuple(a.h_dim))
-    kw = dict(batch=min(a.batch, len(train)), precision=a.precision, lr=a.lr, seed=a.seed)
+    kw = dict(batch=min(a.batch, len(train)), precision=a.precision, lr=a.lr, seed=a.seed, device=device)
+    if accumulated:
+        kw["generic"] = True                        # accumulation and data parallelism of this kind are built on the generic steps
     if a.model == "M2_info":                        # the resident step at the reference geometry, csrc/train_info.hip at any other covered size
         tr = make_info_trainer(dims, alpha=a.alpha, beta=a.beta, gamma=a.gamma, dec_label=a.decoder_label, aux_enc=a.aux_enc, **kw)
         if a.init_classifier:
@@ -116,16 +221,28 @@ def main():
         if a.decoder_label != "truth" or a.aux_enc != "bce" or a.init_classifier:
             ap.error("--decoder-label, --aux-enc and --init-classifier apply to --model M2_info")
         tr = make_trainer(a.model, dims, **kw)
-    tv = tr.fork(min(a.batch, len(valid)))
+    tv = tr if accumulated else tr.fork(min(a.batch, len(valid)))         # (accumulated: validated in micro-batch pieces, below)
     train_trainers, valid_trainers = [tr], [tv]
-    os.makedirs(a.out, exist_ok=True)
-    open(os.path.join(a.out, "output_epoch.log"), "w").close()
-    print(f"{a.model} {dims}: {len(train)} training frames, {len(valid)} validation frames, batch {tr.B}, {a.precision}, {type(tr).__name__}")
+    log = (lambda *args, **kws: print(*args, **kws)) if rank == 0 else (lambda *args, **kws: None)
+    acc, forks, vforks = (AccumulatedStep(tr, pg, micro_batches=[tr.B] * a.accumulate), {}, {}) if accumulated else (None, None, None)
+    if rank == 0:
+        os.makedirs(a.out, exist_ok=True)
+        open(os.path.join(a.out, "output_epoch.log"), "w").close()
+    log(f"{a.model} {dims}: {len(train)} training frames, {len(valid)} validation frames, batch {tr.B}, {a.precision}, {type(tr).__name__}"
+        + (f", {a.accumulate} micro-batches a step on each of {world} rank(s)" if accumulated else ""))
     for epoch in range(a.epochs):
         torch.cuda.synchronize(); t0 = time.perf_counter()
-        elbo, rec, kl = run_epoch(train, train_trainers, True, True)
+        if accumulated:
+            elbo, rec, kl = run_epoch_accumulated(train, acc, forks, tr.B, a.accumulate, epoch, a.seed, log)
+        else:
+            elbo, rec, kl = run_epoch(train, train_trainers, True, True)
         torch.cuda.synchronize(); dt = time.perf_counter() - t0
-        velbo, vrec, vkl = run_epoch(valid, valid_trainers, False, False)
+        if accumulated:                             # every rank validates the same replica
+            velbo, vrec, vkl = run_validation_accumulated(valid, acc, vforks, min(tr.B * a.accumulate, len(valid)))
+        else:
+            velbo, vrec, vkl = run_epoch(valid, valid_trainers, False, False)
+        if rank != 0:                               # rank 0 writes logs and checkpoints
+            continue
         lines = [f"Epoch: {epoch}",
                  "[Train]\t\t ELBO: {:.2f}, Recon.: {:.2f}, KL: {:.2f}".format(elbo, rec, kl),
                  "[Validation]\t ELBO: {:.2f}, Recon.: {:.2f}, KL: {:.2f}".format(velbo, vrec, vkl)]
@@ -134,6 +251,8 @@ def main():
         print("\n".join(lines), f"   ({len(train) / dt / 1e6:.1f} M frames/s incl. shuffle)")
         torch.save({k: v.cpu() for k, v in tr.state_dict().items()},
                    os.path.join(a.out, "{}_epoch_{:03d}_vloss_{:.2f}.pt".format(a.model, epoch, velbo)))
+    if pg is not None:
+        torch.distributed.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -231,6 +231,18 @@ int dvae_train_generic_step(const dvae_train_generic_plan_t* plan, float* params
 /* Forward and loss only (two launches): parameters, moments and gradient slabs are left alone. */
 int dvae_train_generic_eval(const dvae_train_generic_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
                             const float* eps_noise, float elbo_eps, float* losses3, void* stream);
+/* Gradient accumulation and data parallelism: between _grads and the optimizer sits a flat gradient of plan->n_params floats in the plan's
+ * layout (16-byte aligned).  _reduce (one launch): flat[i] = (accumulate ? flat[i] : nothing) + weight * (the plan->ksplit slabs of the last
+ * _grads summed in slab order); with accumulate 0 `flat` is written and never read; the alignment gaps between tensors receive zeros, so
+ * the buffer is finite everywhere and can travel through a collective whole.  weight 1.0 leaves the sum's bits untouched.  The same launch
+ * finalises the micro-batch's loss scalars (and plan->loss_accum) as _apply would: a micro-batch is rows + weight gradients + reduce, three
+ * launches.  _apply_flat: the apply kernel on `flat` as the ONE slab, g = grad_scale * flat: Adam at `step`, packed copies, no loss
+ * scalars.  Both return DVAE_E_BADARG for a null pointer, accumulate outside {0, 1}, a non-finite weight / grad_scale or a changed plan,
+ * before anything touches the device. */
+int dvae_train_generic_reduce(const dvae_train_generic_plan_t* plan, void* ws, float* flat, int accumulate, float weight, float* losses3,
+                              void* stream);
+int dvae_train_generic_apply_flat(const dvae_train_generic_plan_t* plan, float* params, float* m, float* v, void* ws, const float* flat, int step,
+                                  double lr, double beta1, double beta2, double adam_eps, double grad_scale, void* stream);
 
 /* ---- the fused train step for the label classifier alone (csrc/train_classifier.hip): Classifier([513, [h1, h2], y_dim]) of
  * packages/models/models.py -- relu, relu, sigmoid -- under binary_cross_entropy (packages/models/utils.py:55-56) and Adam: the loop body
@@ -294,6 +306,11 @@ int dvae_train_clf_step(const dvae_train_clf_plan_t* plan, float* params, float*
 /* Forward, loss and counts only (two launches): parameters, moments and gradient slabs are left alone. */
 int dvae_train_clf_eval(const dvae_train_clf_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy, float bce_eps,
                         float* losses3, int64_t* counts4, void* stream);
+/* dvae_train_generic_reduce / _apply_flat for this step; losses3 / counts4 (and plan->count_accum) as dvae_train_clf_apply. */
+int dvae_train_clf_reduce(const dvae_train_clf_plan_t* plan, void* ws, float* flat, int accumulate, float weight, float* losses3, int64_t* counts4,
+                          void* stream);
+int dvae_train_clf_apply_flat(const dvae_train_clf_plan_t* plan, float* params, float* m, float* v, void* ws, const float* flat, int step, double lr,
+                              double beta1, double beta2, double adam_eps, double grad_scale, void* stream);
 
 /* ---- the fused train step for M2_info of ANY covered size (csrc/train_info.hip): DeepGenerativeModel_v5 of packages/models/models.py:390-444
  * -- encoder on x alone, decoder on [z | y], a relu classifier on x, an adversarial auxiliary relu classifier on z -- under the loop body of
@@ -376,6 +393,10 @@ int dvae_train_info_step(const dvae_train_info_plan_t* plan, float* params, floa
 /* Forward and losses only (two launches): parameters, moments and gradient slabs are left alone. */
 int dvae_train_info_eval(const dvae_train_info_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
                          const float* eps_noise, float elbo_eps, float* losses8, void* stream);
+/* dvae_train_generic_reduce / _apply_flat for this step (every mode); losses8 as dvae_train_info_apply. */
+int dvae_train_info_reduce(const dvae_train_info_plan_t* plan, void* ws, float* flat, int accumulate, float weight, float* losses8, void* stream);
+int dvae_train_info_apply_flat(const dvae_train_info_plan_t* plan, float* params, float* m, float* v, void* ws, const float* flat, int step, double lr,
+                               double beta1, double beta2, double adam_eps, double grad_scale, void* stream);
 
 /* Per-kernel device time of the last `dvae_train_*` calls made with profiling enabled:
  * enable != 0 brackets each launch with hipEvents on its stream (a few us of host cost each).
