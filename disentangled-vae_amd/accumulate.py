@@ -18,7 +18,7 @@ import os
 import numpy as np
 import torch
 
-from . import dp
+from . import clip, dp
 from .trainer_classifier import ClassifierTrainer
 from .trainer_generic import GenericTrainer
 from .trainer_info import InfoTrainer
@@ -133,15 +133,23 @@ class AccumulatedStep:
         return float(pending[0]) / (float(self.world) * float(sum(pending)))           # (doubles)
 
     # ---- the optimizer step ----
-    def apply(self):
+    def apply(self, max_norm=None):
         """[All-reduce,] one Adam step with grad_scale = B_0 / (world * sum B_k).  Returns the B_k-weighted mean of the micro-batch
-        losses of this rank as a device tensor (no host sync)."""
+        losses of this rank as a device tensor (no host sync).  max_norm: clip the global norm of the step's gradient (all tensors at
+        once, torch.nn.utils.clip_grad_norm_'s rule) to it on the device, behind the all-reduce -- every rank sees the same flat
+        gradient, forms the same coefficient and the replicas stay equal; one more launch, no host sync; a gradient that is not finite
+        skips the update and is counted (grad_norm, skipped_step_count(); DESIGN 4a'''')."""
         if not self._pending:
             raise RuntimeError("apply() with no micro-batch pending: call micro() first")
+        if max_norm is not None:
+            max_norm = clip.check_max_norm(max_norm)
         if self.pg is not None:
             dp.allreduce_flat_(self.flat, self.pg)                                      # one collective per optimizer step
         self._scale = self._grad_scale(self._pending)
-        self.trainer._apply_flat(self.flat, self._scale)
+        if max_norm is None:
+            self.trainer._apply_flat(self.flat, self._scale)
+        else:
+            self.trainer._apply_flat_clipped(self.flat, self._scale, max_norm)
         torch.div(self._loss_sum, float(sum(self._pending)), out=self._loss_sum)
         self.losses.copy_(self._loss_sum)
         self.counts.copy_(self._count_sum)
@@ -149,9 +157,21 @@ class AccumulatedStep:
         return self.losses
 
     # ---- reading state ----
+    @property
+    def grad_norm(self):
+        """Device float32 [total_norm, coef] of the last apply(max_norm=...): the norm before clipping and the factor applied (0: the
+        step was skipped).  No host sync."""
+        return self.trainer.grad_norm
+
+    def skipped_step_count(self):
+        """Clipped steps the device skipped for a non-finite gradient since the last call (reads and resets the counter; synchronises,
+        like bad_row_count())."""
+        return self.trainer.skipped_step_count()
+
     def grads_numpy(self):
         """The accumulator per tensor times the scale apply() uses (would use, while micro-batches are pending): the gradient of the
-        mean loss over the step's frames.  After apply() with a process group: the exchanged gradient."""
+        mean loss over the step's frames.  After apply() with a process group: the exchanged gradient.  Always the UNCLIPPED gradient:
+        apply(max_norm=...) scales inside the optimizer launch and leaves the accumulator alone."""
         tr = self.trainer
         scale = self._grad_scale(self._pending) if self._pending else self._scale
         flat = (self.flat * scale).cpu().numpy()                                        # (float32 product, as the apply kernel's)

@@ -329,7 +329,7 @@ static ApplyArgs apply_args(const dvae_train_clf_plan_t* plan, const CLayout& L,
 
 // adam: the optimizer step on every parameter; otherwise only the packed copies are rewritten (elements) and / or the loss and counts finalised
 static int launch_apply(const dvae_train_clf_plan_t* plan, const CLayout& L, const ApplyArgs& a, char* ws, bool adam, bool elements, bool finalize,
-                        long long* counts4, hipStream_t s) {
+                        long long* counts4, hipStream_t s, const GClipHost* clip = nullptr) {
     GApplyArgs g;
     memset(&g, 0, sizeof(g));
     g.a = a;
@@ -340,7 +340,7 @@ static int launch_apply(const dvae_train_clf_plan_t* plan, const CLayout& L, con
         g.cnt_partials = (const long long*)(ws + L.o_counts); g.cnt_wgs = (int)L.rows_grid; g.counts4 = counts4;
         g.cnt_accum = (long long*)(uintptr_t)plan->count_accum;
     }
-    return launch_apply_table(g, s);
+    return clip ? launch_apply_clipped_table(g, *clip, s) : launch_apply_table(g, s);
 }
 
 static int launch_rows(const dvae_train_clf_plan_t* plan, const CLayout& L, char* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
@@ -469,6 +469,19 @@ extern "C" int dvae_train_clf_apply_flat(const dvae_train_clf_plan_t* plan, floa
     ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, nullptr);
     a.slabs = flat; a.nslabs = 1;                       // the flat gradient is the one slab
     return launch_apply(plan, L, a, (char*)ws, true, true, false, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int dvae_train_clf_apply_flat_clipped(const dvae_train_clf_plan_t* plan, float* params, float* m, float* v, void* ws, const float* flat,
+                                                 int step, double lr, double beta1, double beta2, double adam_eps, double grad_scale,
+                                                 double max_norm, void* scratch, float* norm2_out, int32_t* skipped_counter, void* stream) {
+    CLayout L;
+    if (int rc = plan_layout("train_clf_apply_flat_clipped", plan, L)) return rc;
+    if (int rc = check_apply_flat_args("train_clf_apply_flat_clipped", params, m, v, ws, flat, step, lr, grad_scale)) return rc;
+    const GClipHost clip = {grad_scale, max_norm, scratch, norm2_out, skipped_counter};
+    if (int rc = check_clip_args("train_clf_apply_flat_clipped", flat, clip)) return rc;
+    ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, nullptr);
+    a.slabs = flat; a.nslabs = 1;                       // the flat gradient is the one slab
+    return launch_apply(plan, L, a, (char*)ws, true, true, false, nullptr, (hipStream_t)stream, &clip);
 }
 
 extern "C" int dvae_train_clf_step(const dvae_train_clf_plan_t* plan, float* params, float* m, float* v, void* ws, const float* x, int64_t ldx,

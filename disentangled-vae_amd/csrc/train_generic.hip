@@ -21,6 +21,9 @@
 //     and the same inputs give the same bits.
 //   * apply kernel: one thread per parameter: slab sum in slab order, adam_element (apply_common.hpp), both packed copies refreshed,
 //     loss scalars finalised from the rows kernel's per-workgroup sums (and added to the optional float64 accumulator).
+//   * reduce kernel (gradient accumulation, data parallelism): the slabs of a micro-batch summed into one flat gradient; and, for
+//     global-norm clipping on the device, a norm kernel over that flat gradient (per-chunk sums of squares in double, fixed order) in
+//     front of a guarded instantiation of the apply kernel's body (train_generic.hpp: GNormArgs / GClipArgs).
 //   * 64-bit indexing throughout; a gather index outside [0, row_count) is never dereferenced (row 0 instead, counted).
 #include <math.h>
 #include <vector>
@@ -522,8 +525,10 @@ __device__ __forceinline__ void finalize_step(const GApplyArgs& g, double (*red)
 // ---------------------------------------------------------------------------------------------------------------------------------
 // apply kernel: optimizer step, both packed copies, loss scalars (GApplyArgs: train_generic.hpp; the classifier step launches it too,
 // with its confusion counts to finalise)
-__global__ __launch_bounds__(256) void train_generic_apply_kernel(const GApplyArgs g) {
-    __shared__ double red[4][4];
+// CLIP (the guarded form, train_generic_apply_clipped_kernel): `ga` is g.a with the effective scale in gscale; the element arithmetic
+// is the same code either way
+template <bool CLIP>
+__device__ __forceinline__ void apply_body(const GApplyArgs& g, const ApplyArgs& ga, double (*red)[4]) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx < g.a.n_params) {
         int t = -1;
@@ -536,7 +541,7 @@ __global__ __launch_bounds__(256) void train_generic_apply_kernel(const GApplyAr
             if (g.adam) {
                 const float gi = fused::slab_sum_at(g.a, idx);
                 float mi, vi;
-                fused::adam_element(g.a, pi, g.a.m[idx], g.a.v[idx], gi, mi, vi);
+                fused::adam_element(CLIP ? ga : g.a, pi, g.a.m[idx], g.a.v[idx], gi, mi, vi);
                 g.a.p[idx] = pi; g.a.m[idx] = mi; g.a.v[idx] = vi;
             }
             const int i = (int)(idx - d.off);
@@ -552,6 +557,67 @@ __global__ __launch_bounds__(256) void train_generic_apply_kernel(const GApplyAr
         }
     }
     if (g.finalize && blockIdx.x == 0) finalize_step(g, red);
+}
+
+__global__ __launch_bounds__(256) void train_generic_apply_kernel(const GApplyArgs g) {
+    __shared__ double red[4][4];
+    apply_body<false>(g, g.a, red);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// global-norm clipping (GNormArgs / GClipArgs: train_generic.hpp).  The norm kernel: one workgroup a chunk of G_NORM_CHUNK floats.
+__global__ __launch_bounds__(256) void train_generic_gradnorm_kernel(const GNormArgs g) {
+    __shared__ double wsum[4];
+    const int64_t base = (int64_t)blockIdx.x * G_NORM_CHUNK;
+    f32x4 v[4];
+    int i4[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {                       // every load before the first addition; n_params is a multiple of 4 below 2^31
+        const int64_t i = base + ((int64_t)j * 256 + threadIdx.x) * 4;
+        i4[j] = (int)i;
+        v[j] = i < g.n_params ? *reinterpret_cast<const f32x4*>(g.flat + i) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int nv = 0;                                     // this piece's floats that belong to a tensor (the reduce kernel's rule)
+#pragma unroll
+        for (int k = 0; k < G_NT; ++k)
+            if ((unsigned)(i4[j] - g.off[k]) < (unsigned)g.cnt[k]) nv = g.off[k] + g.cnt[k] - i4[j];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (q < nv) s += (double)v[j][q] * (double)v[j][q];       // address order; the square is exact in double
+    }
+    s = wave_sum(s);                                    // lanes: the same tree on every lane
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) g.partials[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];       // waves in order
+}
+
+// The guarded apply kernel.  Every workgroup forms the same s from the same partials in the same order (a few hundred doubles from L2),
+// so every workgroup takes the same branch: return without a store (s not finite), or the element loop of the apply kernel under
+// gscale_eff = fl32(grad_scale * coef).  coef == 1 leaves fl32(grad_scale): the unguarded kernel's bits.
+__global__ __launch_bounds__(256) void train_generic_apply_clipped_kernel(const GApplyArgs g, const GClipArgs c) {
+    __shared__ double red[4][4];
+    __shared__ double wsum[4];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < c.nchunks; i += 256) s += c.partials[i];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    s = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+    const bool ok = isfinite(s);                        // (workgroup- and grid-uniform)
+    const double total_norm = fabs(c.grad_scale) * sqrt(s);
+    const double coef = ok ? fmin(1.0, c.max_norm / (total_norm + 1e-6)) : 0.0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        c.norm2_out[0] = (float)total_norm;
+        c.norm2_out[1] = (float)coef;
+        if (!ok) *c.skipped += 1;                       // launches of a stream are ordered: no atomic needed
+    }
+    if (!ok) return;
+    ApplyArgs ga = g.a;
+    ga.gscale = (float)(c.grad_scale * coef);           // formed in double, rounded once
+    apply_body<true>(g, ga, red);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -636,6 +702,34 @@ int launch_reduce_table(const GReduceArgs& g, hipStream_t s) {
     return 0;
 }
 
+int launch_apply_clipped_table(const GApplyArgs& g, const GClipHost& h, hipStream_t s) {
+    const int64_t P = g.a.n_params;
+    DVAE_CHECK_ARG(P >= 1 && P < ((int64_t)1 << 31) - G_NORM_CHUNK && P % 64 == 0 && g.a.nslabs == 1,
+                   "train_generic_gradnorm_kernel: %lld parameters (a multiple of 64 below 2^31: the kernel indexes tensors in 32 bits)", (long long)P);
+    GNormArgs n;
+    memset(&n, 0, sizeof(n));
+    n.flat = g.a.slabs; n.n_params = P; n.partials = (double*)h.scratch;
+    for (int k = 0; k < G_NT; ++k) { n.off[k] = (int32_t)g.t[k].off; n.cnt[k] = g.t[k].rows * g.t[k].cols; }
+    const int64_t chunks = gradnorm_chunks(P);
+    hipLaunchKernelGGL(train_generic_gradnorm_kernel, dim3((unsigned)chunks), dim3(256), 0, s, n);
+    DVAE_LAUNCH_OK("train_generic_gradnorm_kernel");
+    GClipArgs c;
+    memset(&c, 0, sizeof(c));
+    c.partials = (const double*)h.scratch; c.nchunks = (int)chunks; c.grad_scale = h.grad_scale; c.max_norm = h.max_norm;
+    c.norm2_out = h.norm2_out; c.skipped = h.skipped;
+    hipLaunchKernelGGL(train_generic_apply_clipped_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, g, c);
+    DVAE_LAUNCH_OK("train_generic_apply_clipped_kernel");
+    return 0;
+}
+
+int check_clip_args(const char* who, const float* flat, const GClipHost& h) {
+    DVAE_CHECK_ARG(h.scratch && h.norm2_out && h.skipped, "%s: null pointer", who);
+    DVAE_CHECK_ARG(h.max_norm > 0.0, "%s: max_norm %g (a positive number; +inf clips nothing)", who, h.max_norm);      // (a NaN fails the comparison)
+    DVAE_CHECK_ARG(((uintptr_t)flat & 15) == 0 && ((uintptr_t)h.scratch & 7) == 0,
+                   "%s: the flat gradient must be 16-byte aligned and the scratch buffer 8-byte aligned", who);
+    return 0;
+}
+
 int check_reduce_args(const char* who, const void* ws, const float* flat, int accumulate, float weight) {
     DVAE_CHECK_ARG(ws && flat, "%s: null pointer", who);
     DVAE_CHECK_ARG(((uintptr_t)flat & 15) == 0, "%s: the flat gradient must be 16-byte aligned", who);
@@ -710,14 +804,16 @@ static ApplyArgs apply_args(const dvae_train_generic_plan_t* plan, const GLayout
 }
 
 // adam: the optimizer step on every parameter; otherwise only the packed copies are rewritten (params != null) and / or the losses finalised
-static int launch_apply(const GLayout& L, const ApplyArgs& a, char* ws, bool adam, bool elements, bool finalize, hipStream_t s) {
+// (clip: the norm launch and the guarded apply kernel in place of the apply kernel)
+static int launch_apply(const GLayout& L, const ApplyArgs& a, char* ws, bool adam, bool elements, bool finalize, hipStream_t s,
+                        const GClipHost* clip = nullptr) {
     GApplyArgs g;
     memset(&g, 0, sizeof(g));
     g.a = a;
     if (!elements) g.a.n_params = 0;
     make_tensors(L, g.t);
     g.ws = (float*)ws; g.adam = adam ? 1 : 0; g.finalize = finalize ? 1 : 0;
-    return launch_apply_table(g, s);
+    return clip ? launch_apply_clipped_table(g, *clip, s) : launch_apply_table(g, s);
 }
 
 static int launch_rows(const dvae_train_generic_plan_t* plan, const GLayout& L, char* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
@@ -849,6 +945,28 @@ extern "C" int dvae_train_generic_apply_flat(const dvae_train_generic_plan_t* pl
     ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, nullptr);
     a.slabs = flat; a.nslabs = 1;                       // the flat gradient is the one slab
     return launch_apply(L, a, (char*)ws, true, true, false, (hipStream_t)stream);
+}
+
+extern "C" int64_t dvae_train_gradnorm_scratch_bytes(int64_t n_params) {
+    if (n_params < 1 || n_params >= ((int64_t)1 << 31) - G_NORM_CHUNK) {
+        set_error("train_gradnorm_scratch_bytes: n_params %lld (the plan's n_params: at least 1, below 2^31)", (long long)n_params);
+        return 0;
+    }
+    return gradnorm_chunks(n_params) * (int64_t)sizeof(double);
+}
+
+extern "C" int dvae_train_generic_apply_flat_clipped(const dvae_train_generic_plan_t* plan, float* params, float* m, float* v, void* ws,
+                                                     const float* flat, int step, double lr, double beta1, double beta2, double adam_eps,
+                                                     double grad_scale, double max_norm, void* scratch, float* norm2_out,
+                                                     int32_t* skipped_counter, void* stream) {
+    GLayout L;
+    if (int rc = plan_layout("train_generic_apply_flat_clipped", plan, L)) return rc;
+    if (int rc = check_apply_flat_args("train_generic_apply_flat_clipped", params, m, v, ws, flat, step, lr, grad_scale)) return rc;
+    const GClipHost clip = {grad_scale, max_norm, scratch, norm2_out, skipped_counter};
+    if (int rc = check_clip_args("train_generic_apply_flat_clipped", flat, clip)) return rc;
+    ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, nullptr);
+    a.slabs = flat; a.nslabs = 1;                       // the flat gradient is the one slab
+    return launch_apply(L, a, (char*)ws, true, true, false, (hipStream_t)stream, &clip);
 }
 
 extern "C" int dvae_train_generic_step(const dvae_train_generic_plan_t* plan, float* params, float* m, float* v, void* ws, const float* x, int64_t ldx,

@@ -146,7 +146,29 @@ struct GReduceArgs {
     float weight;
 };
 
-static_assert(sizeof(GWgradArgs) <= G_KERNARG_MAX && sizeof(GApplyArgs) <= G_KERNARG_MAX && sizeof(GReduceArgs) <= G_KERNARG_MAX,
+// Global-norm clipping of the flat gradient (include/dvae_train.h: dvae_train_*_apply_flat_clipped): two launches, no host round trip.
+//   * norm kernel (train_generic.hip: train_generic_gradnorm_kernel): workgroup c owns chunk c = floats [c G_NORM_CHUNK, (c + 1)
+//     G_NORM_CHUNK) of the flat gradient, whatever the grid of any other launch or the part: a thread loads four 16-byte pieces,
+//     squares and adds them in double in address order (a float32 square is exact in double), then lanes (xor butterfly: every lane
+//     forms the same tree), waves in order, and partials[c] is written.  Floats that belong to no tensor (the alignment gaps) count
+//     as zero whatever they hold.  No atomics: the same gradient gives the same partials on every run and every rank.
+//   * the guarded apply kernel (train_generic_apply_clipped_kernel) sums the partials in a fixed order too -- thread t of every
+//     workgroup takes chunks t, t + 256, ... ascending, then lanes, then waves -- and forms total_norm, coef and the effective scale.
+constexpr int G_NORM_CHUNK = 4096;              // floats of a chunk: 256 threads x 4 loads x 4 floats
+struct GNormArgs {
+    const float* flat; int64_t n_params;
+    double* partials;
+    int32_t off[G_NT], cnt[G_NT];               // the tensors (unused entries: cnt 0)
+};
+struct GClipArgs {
+    const double* partials; int nchunks;
+    double grad_scale, max_norm;
+    float* norm2_out;                           // [total_norm, coef]
+    int32_t* skipped;                           // + 1 when the sum of squares is not finite (the update is then not made)
+};
+
+static_assert(sizeof(GWgradArgs) <= G_KERNARG_MAX && sizeof(GApplyArgs) <= G_KERNARG_MAX && sizeof(GReduceArgs) <= G_KERNARG_MAX &&
+              sizeof(GApplyArgs) + sizeof(GClipArgs) <= G_KERNARG_MAX && sizeof(GNormArgs) <= G_KERNARG_MAX,
               "the tables travel as kernel arguments");
 
 // the launches, for a caller that has filled the tables (unused entries zeroed): n_items workgroups; one thread a parameter of
@@ -154,6 +176,13 @@ static_assert(sizeof(GWgradArgs) <= G_KERNARG_MAX && sizeof(GApplyArgs) <= G_KER
 int launch_wgrad_table(const GWgradArgs& g, int n_items, hipStream_t s);
 int launch_apply_table(const GApplyArgs& g, hipStream_t s);
 int launch_reduce_table(const GReduceArgs& g, hipStream_t s);
+// the norm launch over g.a.slabs (the flat gradient: g.a.nslabs 1) into h.scratch, then the guarded apply launch with the caller's
+// grad_scale as a double (g.a.gscale is not read)
+struct GClipHost { double grad_scale, max_norm; void* scratch; float* norm2_out; int32_t* skipped; };
+int launch_apply_clipped_table(const GApplyArgs& g, const GClipHost& h, hipStream_t s);
+inline int64_t gradnorm_chunks(int64_t n_params) { return (n_params + G_NORM_CHUNK - 1) / G_NORM_CHUNK; }
+// what the _apply_flat_clipped entry points refuse on top of check_apply_flat_args
+int check_clip_args(const char* who, const float* flat, const GClipHost& h);
 // what the _reduce / _apply_flat entry points of the three steps refuse before anything touches the device (0: fine)
 int check_reduce_args(const char* who, const void* ws, const float* flat, int accumulate, float weight);
 int check_apply_flat_args(const char* who, const float* params, const float* m, const float* v, const void* ws, const float* flat, int step,

@@ -865,7 +865,7 @@ static ApplyArgs apply_args(const dvae_train_info_plan_t* plan, const ILayout& L
 
 // adam: the optimizer step on every parameter; otherwise only the packed copies are rewritten (elements) and / or the losses finalised
 static int launch_apply(const dvae_train_info_plan_t* plan, const ILayout& L, const ApplyArgs& a, char* ws, bool adam, bool elements, bool finalize,
-                        hipStream_t s) {
+                        hipStream_t s, const GClipHost* clip = nullptr) {
     GApplyArgs g;
     memset(&g, 0, sizeof(g));
     g.a = a;
@@ -876,7 +876,7 @@ static int launch_apply(const dvae_train_info_plan_t* plan, const ILayout& L, co
         g.v_accum = (double*)(uintptr_t)plan->loss_accum;
     }
     g.ws = (float*)ws; g.adam = adam ? 1 : 0; g.finalize = finalize ? 1 : 0;
-    return launch_apply_table(g, s);
+    return clip ? launch_apply_clipped_table(g, *clip, s) : launch_apply_table(g, s);
 }
 
 template <bool DC, int AV>
@@ -1023,6 +1023,19 @@ extern "C" int dvae_train_info_apply_flat(const dvae_train_info_plan_t* plan, fl
     ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, nullptr);
     a.slabs = flat; a.nslabs = 1;                       // the flat gradient is the one slab
     return launch_apply(plan, L, a, (char*)ws, true, true, false, (hipStream_t)stream);
+}
+
+extern "C" int dvae_train_info_apply_flat_clipped(const dvae_train_info_plan_t* plan, float* params, float* m, float* v, void* ws, const float* flat,
+                                                  int step, double lr, double beta1, double beta2, double adam_eps, double grad_scale,
+                                                  double max_norm, void* scratch, float* norm2_out, int32_t* skipped_counter, void* stream) {
+    ILayout L;
+    if (int rc = plan_layout("train_info_apply_flat_clipped", plan, L)) return rc;
+    if (int rc = check_apply_flat_args("train_info_apply_flat_clipped", params, m, v, ws, flat, step, lr, grad_scale)) return rc;
+    const GClipHost clip = {grad_scale, max_norm, scratch, norm2_out, skipped_counter};
+    if (int rc = check_clip_args("train_info_apply_flat_clipped", flat, clip)) return rc;
+    ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, nullptr);
+    a.slabs = flat; a.nslabs = 1;                       // the flat gradient is the one slab
+    return launch_apply(plan, L, a, (char*)ws, true, true, false, (hipStream_t)stream, &clip);
 }
 
 extern "C" int dvae_train_info_step(const dvae_train_info_plan_t* plan, float* params, float* m, float* v, void* ws, const float* x, int64_t ldx,

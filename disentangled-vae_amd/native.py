@@ -116,6 +116,8 @@ SIGNATURES = {
     "dvae_train_generic_eval": (c_i, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_f, c_vp, c_vp]),
     "dvae_train_generic_reduce": (c_i, [c_vp, c_vp, c_vp, c_i, c_f, c_vp, c_vp]),
     "dvae_train_generic_apply_flat": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_d, c_d, c_d, c_d, c_vp]),
+    "dvae_train_generic_apply_flat_clipped": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_d, c_d, c_d, c_d, c_d, c_vp, c_vp, c_vp, c_vp]),
+    "dvae_train_gradnorm_scratch_bytes": (c_i64, [c_i64]),
     "dvae_train_clf_plan": (c_i, [c_i, c_i, c_i, c_i, c_i64, c_i, c_vp]),
     "dvae_train_clf_init": (c_i, [c_vp, c_vp, c_vp, c_vp]),
     "dvae_train_clf_repack": (c_i, [c_vp, c_vp, c_vp, c_vp]),
@@ -125,6 +127,7 @@ SIGNATURES = {
     "dvae_train_clf_eval": (c_i, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_f, c_vp, c_vp, c_vp]),
     "dvae_train_clf_reduce": (c_i, [c_vp, c_vp, c_vp, c_i, c_f, c_vp, c_vp, c_vp]),
     "dvae_train_clf_apply_flat": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_d, c_d, c_d, c_d, c_vp]),
+    "dvae_train_clf_apply_flat_clipped": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_d, c_d, c_d, c_d, c_d, c_vp, c_vp, c_vp, c_vp]),
     "dvae_train_info_plan": (c_i, [c_i, c_i, c_i, c_i, c_i64, c_i, c_vp]),
     "dvae_train_info_plan_mode": (c_i, [c_i, c_i, c_i, c_i, c_i64, c_i, c_i, c_vp]),
     "dvae_train_info_init": (c_i, [c_vp, c_vp, c_vp, c_vp]),
@@ -135,6 +138,7 @@ SIGNATURES = {
     "dvae_train_info_eval": (c_i, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_f, c_vp, c_vp]),
     "dvae_train_info_reduce": (c_i, [c_vp, c_vp, c_vp, c_i, c_f, c_vp, c_vp]),
     "dvae_train_info_apply_flat": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_d, c_d, c_d, c_d, c_vp]),
+    "dvae_train_info_apply_flat_clipped": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_d, c_d, c_d, c_d, c_d, c_vp, c_vp, c_vp, c_vp]),
     "dvae_train_profile": (c_i, [c_i]),
     "dvae_train_debug_stamps": (c_i, [c_vp]),
     "dvae_mcem_debug_stamps": (c_i, [c_vp]),

@@ -11,6 +11,7 @@ import ctypes
 import numpy as np
 import torch
 
+from . import clip
 from . import native as N
 from .trainer import MAXT, MODEL_CODE, PREC_CODE, TENSOR_NAMES
 
@@ -227,7 +228,18 @@ class GenericTrainer:
             yp, ldy = N.ptr(y), N.ld(y)
         return x, y, yp, ldy, eps_noise.contiguous()
 
-    def step(self, x, y=None, eps_noise=None, rows=None):
+    def step(self, x, y=None, eps_noise=None, rows=None, max_norm=None):
+        """max_norm=None: three launches.  A positive number: the global gradient norm is clipped to it on the device
+        (torch.nn.utils.clip_grad_norm_ over all tensors at once; a non-finite gradient skips the update and is counted: clip.py) --
+        rows, weight gradients, reduce into a private flat gradient, norm, guarded apply: five launches, still no host sync."""
+        if max_norm is not None:
+            max_norm = clip.check_max_norm(max_norm)
+            if eps_noise is None:
+                eps_noise = self.noise(self.step_count + 1)
+            flat = clip.step_flat(self)
+            self._micro(flat, 0, 1.0, x, y, eps_noise, rows)
+            self._apply_flat_clipped(flat, 1.0, max_norm)
+            return self.losses
         self._check_inputs(x, y, rows, eps_noise)
         self._sync_copies()
         self.step_count += 1
@@ -291,6 +303,18 @@ class GenericTrainer:
             N.check(self.lib.dvae_train_generic_apply_flat(ctypes.byref(self.plan), N.ptr(self._params), N.ptr(self._m), N.ptr(self._v),
                                                            N.ptr(self.ws), N.ptr(flat), self.step_count, self.lr, self.betas[0], self.betas[1],
                                                            self.adam_eps, float(grad_scale), N.stream()), "dvae_train_generic_apply_flat")
+
+    def _apply_flat_clipped(self, flat, grad_scale, max_norm):
+        """_apply_flat with the global norm of grad_scale * flat clipped to max_norm on the device (clip.py)."""
+        clip.apply_flat_clipped(self, "generic", flat, grad_scale, max_norm)
+
+    grad_norm = property(lambda self: clip.state(self)["grad_norm"],
+                         doc="Device float32 [total_norm, coef] of the last clipped step of this trainer or a fork (no host sync).")
+
+    def skipped_step_count(self):
+        """Clipped steps the device skipped for a non-finite gradient since the last call (synchronises; shared with forks).  A skipped
+        step leaves parameters, moments and packed copies untouched but still counts in step_count."""
+        return clip.skipped_step_count(self)
 
     def accumulate_losses(self, buf):
         """Running sums for epoch logging without a host sync per step: `buf` is a float64 CUDA tensor of 8 elements (or None to stop);

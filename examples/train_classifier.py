@@ -78,11 +78,22 @@ class Epoch:
                 f"F1_score: {v[4]:.4f}"), v
 
 
-def run_pass(data, trainers, batch, train, generator=None):
+def run_pass(data, trainers, batch, train, generator=None, clip_norm=None, norms=None):
+    """clip_norm: every step clips its global gradient norm to it on the device; `norms` (float64 [2] on the device) collects the sum
+    of the finite norms and their number, with no host sync."""
     ep = Epoch(data.device)
     for idx in data.index_batches(batch, shuffle=train, generator=generator):
         tr = trainers(idx.numel())
-        loss = tr.step(data.x, data.y, rows=idx) if train else tr.evaluate(data.x, data.y, rows=idx)
+        if not train:
+            loss = tr.evaluate(data.x, data.y, rows=idx)
+        elif clip_norm is None:
+            loss = tr.step(data.x, data.y, rows=idx)
+        else:
+            loss = tr.step(data.x, data.y, rows=idx, max_norm=clip_norm)
+            norm = tr.grad_norm[0]
+            ok = torch.isfinite(norm)
+            norms[0] += torch.where(ok, norm, torch.zeros_like(norm))
+            norms[1] += ok
         ep.add(loss, tr.counts)
     return ep
 
@@ -100,7 +111,12 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--save", default=None, metavar="FILE")
     ap.add_argument("--prefix", default="", help="key prefix of the saved state_dict, e.g. enc_dec_clf.classifier.")
+    ap.add_argument("--clip-norm", type=float, default=None, metavar="X",
+                    help="clip the global gradient norm of every step to X on the device (a gradient that is not finite skips its update); "
+                         "the epoch log gains the mean norm and the skipped steps")
     a = ap.parse_args()
+    if a.clip_norm is not None and not a.clip_norm > 0:
+        ap.error("--clip-norm takes a positive number")
     if a.synthetic < 2:
         ap.error("--synthetic: at least two utterances (one is held out)")
     speech = [synthetic_speech(3.0 + 0.25 * (i % 5), a.seed + i) for i in range(a.synthetic)]
@@ -124,8 +140,13 @@ def main():
     print(f"Classifier [513, {list(a.h_dim)}, {y_dim}], {a.labels} labels, batch {a.batch}, Adam lr {a.lr:g}")
     gen = torch.Generator(device=sets["train"].device).manual_seed(a.seed)
     first = last = None
+    norms = torch.zeros(2, dtype=torch.float64, device=sets["train"].device)
     for epoch in range(a.epochs):
-        t_line, t = run_pass(sets["train"], trainers, a.batch, True, gen).line("Train")
+        t_line, t = run_pass(sets["train"], trainers, a.batch, True, gen, a.clip_norm, norms).line("Train")
+        if a.clip_norm is not None:                        # read once per epoch; the counter is shared by the forks
+            total, n = norms.cpu().tolist()
+            norms.zero_()
+            t_line += f"    Grad norm: {total / max(n, 1.0):.4f} (clipped to {a.clip_norm:g})    Skipped steps: {main_tr.skipped_step_count()}"
         v_line, _ = run_pass(sets["valid"], trainers, a.batch, False).line("Validation")
         print(f"Epoch: {epoch}\n{t_line}\n{v_line}")
         first, last = (t[0] if first is None else first), t[0]

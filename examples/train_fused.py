@@ -22,6 +22,9 @@ Gradient accumulation and data parallelism on the generic steps (disentangled-va
     python examples/train_fused.py --model M2_info --synthetic 200000 --z-dim 32 --h-dim 256 64 --batch 8192 --accumulate 4
     # 8 ranks, one per GPU, started from here; each brings --accumulate x --batch frames to an optimizer step
     python examples/train_fused.py --model M2 --synthetic 2000000 --z-dim 32 --h-dim 256 64 --gpus 8
+    # the global gradient norm of every optimizer step clipped to 5 on the device (behind the all-reduce; no host sync); the epoch
+    # line gains the mean norm and the number of steps skipped for a gradient that was not finite
+    python examples/train_fused.py --model M2_info --synthetic 200000 --z-dim 32 --h-dim 256 64 --batch 8192 --accumulate 4 --clip-norm 5
 
 Checkpoints are plain state_dicts with the reference's keys: the reference's evaluate / reconstruct scripts load them.
 Differences from the scripts, all deliberate: the batch size is a flag (the fused step is meant for thousands of
@@ -51,7 +54,27 @@ def synthetic(n, y_dim, seed):
     return X, Y
 
 
-def run_epoch(data, trainers, train, shuffle):   # trainers: [main, optional fork for the last, shorter batch]
+class ClipLog:
+    """--clip-norm: the epoch's mean total_norm over the steps that were made and the number the device skipped (a gradient that is
+    not finite), summed on the device from the trainer's grad_norm after every step and read once per epoch."""
+
+    def __init__(self, tr, max_norm):
+        self.tr, self.max_norm = tr, max_norm
+        self.stat = torch.zeros(2, dtype=torch.float64, device=tr.device)          # sum of the finite norms, their number
+
+    def note(self):
+        norm = self.tr.grad_norm[0]
+        ok = torch.isfinite(norm)
+        self.stat[0] += torch.where(ok, norm, torch.zeros_like(norm))
+        self.stat[1] += ok
+
+    def read(self):
+        total, n = self.stat.cpu().tolist()
+        self.stat.zero_()
+        return total / max(n, 1.0), self.tr.skipped_step_count()
+
+
+def run_epoch(data, trainers, train, shuffle, clip=None):   # trainers: [main, optional fork for the last, shorter batch]
     """One pass; returns mean (ELBO, recon, KL) over batches like the scripts (sum of batch means / number of batches).
     The sums are kept on the device by the step itself: no host sync, no extra kernels per step."""
     tot = torch.zeros(8, dtype=torch.float64, device=data.device)
@@ -63,7 +86,13 @@ def run_epoch(data, trainers, train, shuffle):   # trainers: [main, optional for
                 trainers[1:] = [tr.fork(rows.shape[0])]
             tr = trainers[1]
         tr.accumulate_losses(tot)
-        tr.step(data.x, data.y, rows=rows) if train else tr.evaluate(data.x, data.y, rows=rows)
+        if not train:
+            tr.evaluate(data.x, data.y, rows=rows)
+        elif clip is None:
+            tr.step(data.x, data.y, rows=rows)
+        else:
+            tr.step(data.x, data.y, rows=rows, max_norm=clip.max_norm)
+            clip.note()
         nb += 1
     for tr in trainers:
         tr.accumulate_losses(None)
@@ -75,7 +104,7 @@ def micro_sizes(n, batch):
     return [batch] * (n // batch) + ([n % batch] if n % batch else [])
 
 
-def run_epoch_accumulated(data, acc, forks, batch, k, epoch, seed, log):
+def run_epoch_accumulated(data, acc, forks, batch, k, epoch, seed, log, clip=None):
     """One training pass with one optimizer step per k micro-batches of `batch` frames on every rank; the epoch's tail is a shorter
     step whose last micro-batch runs on a fork.  With several ranks the permutation comes from a generator seeded alike on all of them,
     rank r takes the r-th share of every step, and a tail that does not divide over the ranks loses at most world - 1 frames.
@@ -98,7 +127,9 @@ def run_epoch_accumulated(data, acc, forks, batch, k, epoch, seed, log):
         for b in acc.micro_batches:
             acc.micro(data.x, data.y, rows=mine[lo:lo + b].contiguous(), trainer=forked(acc.trainer, forks, b))
             lo += b
-        tot += acc.apply()[:3]
+        tot += acc.apply(max_norm=None if clip is None else clip.max_norm)[:3]
+        if clip is not None:
+            clip.note()
         steps += 1
     return acc.mean_over_ranks(tot / max(steps, 1)).tolist()      # (the collective runs where the group's backend serves it)
 
@@ -173,9 +204,14 @@ def main():
                     help="generic steps: one optimizer step per K micro-batches of --batch frames (the workspace is sized by --batch)")
     ap.add_argument("--gpus", type=int, default=1, metavar="N",
                     help="generic steps: N data-parallel ranks, one per GPU, one all-reduce of the flat gradient per optimizer step")
+    ap.add_argument("--clip-norm", type=float, default=None, metavar="X",
+                    help="generic steps: clip the global gradient norm of every optimizer step to X on the device (all tensors at once; a "
+                         "gradient that is not finite skips its update); the epoch log gains the mean norm and the skipped steps")
     a = ap.parse_args()
     if a.accumulate < 1 or a.gpus < 1:
         ap.error("--accumulate and --gpus count from 1")
+    if a.clip_norm is not None and not a.clip_norm > 0:
+        ap.error("--clip-norm takes a positive number")
     rank, world, pg, device = 0, 1, None, "cuda:0"
     if a.gpus > 1:
         if "WORLD_SIZE" not in os.environ:
@@ -206,8 +242,8 @@ def main():
         train.y = valid.y = None
     dims = dict(x_dim=513, y_dim=y_dim, z_dim=a.z_dim, h_dim=tuple(a.h_dim))
     kw = dict(batch=min(a.batch, len(train)), precision=a.precision, lr=a.lr, seed=a.seed, device=device)
-    if accumulated:
-        kw["generic"] = True                        # accumulation and data parallelism of this kind are built on the generic steps
+    if accumulated or a.clip_norm is not None:
+        kw["generic"] = True                        # accumulation, data parallelism of this kind and clipping are built on the generic steps
     if a.model == "M2_info":                        # the resident step at the reference geometry, csrc/train_info.hip at any other covered size
         tr = make_info_trainer(dims, alpha=a.alpha, beta=a.beta, gamma=a.gamma, dec_label=a.decoder_label, aux_enc=a.aux_enc, **kw)
         if a.init_classifier:
@@ -225,6 +261,7 @@ def main():
     train_trainers, valid_trainers = [tr], [tv]
     log = (lambda *args, **kws: print(*args, **kws)) if rank == 0 else (lambda *args, **kws: None)
     acc, forks, vforks = (AccumulatedStep(tr, pg, micro_batches=[tr.B] * a.accumulate), {}, {}) if accumulated else (None, None, None)
+    clip = None if a.clip_norm is None else ClipLog(tr, a.clip_norm)
     if rank == 0:
         os.makedirs(a.out, exist_ok=True)
         open(os.path.join(a.out, "output_epoch.log"), "w").close()
@@ -233,18 +270,22 @@ def main():
     for epoch in range(a.epochs):
         torch.cuda.synchronize(); t0 = time.perf_counter()
         if accumulated:
-            elbo, rec, kl = run_epoch_accumulated(train, acc, forks, tr.B, a.accumulate, epoch, a.seed, log)
+            elbo, rec, kl = run_epoch_accumulated(train, acc, forks, tr.B, a.accumulate, epoch, a.seed, log, clip)
         else:
-            elbo, rec, kl = run_epoch(train, train_trainers, True, True)
+            elbo, rec, kl = run_epoch(train, train_trainers, True, True, clip)
         torch.cuda.synchronize(); dt = time.perf_counter() - t0
         if accumulated:                             # every rank validates the same replica
             velbo, vrec, vkl = run_validation_accumulated(valid, acc, vforks, min(tr.B * a.accumulate, len(valid)))
         else:
             velbo, vrec, vkl = run_epoch(valid, valid_trainers, False, False)
+        clipped = ""
+        if clip is not None:                        # (read once per epoch, on every rank: the counter is each replica's own)
+            norm, skipped = clip.read()
+            clipped = ", grad norm: {:.3f} (clipped to {:g}), skipped steps: {}".format(norm, a.clip_norm, skipped)
         if rank != 0:                               # rank 0 writes logs and checkpoints
             continue
         lines = [f"Epoch: {epoch}",
-                 "[Train]\t\t ELBO: {:.2f}, Recon.: {:.2f}, KL: {:.2f}".format(elbo, rec, kl),
+                 "[Train]\t\t ELBO: {:.2f}, Recon.: {:.2f}, KL: {:.2f}".format(elbo, rec, kl) + clipped,
                  "[Validation]\t ELBO: {:.2f}, Recon.: {:.2f}, KL: {:.2f}".format(velbo, vrec, vkl)]
         with open(os.path.join(a.out, "output_epoch.log"), "a") as f:
             f.write("\n".join(lines) + "\n")

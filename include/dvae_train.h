@@ -243,6 +243,30 @@ int dvae_train_generic_reduce(const dvae_train_generic_plan_t* plan, void* ws, f
                               void* stream);
 int dvae_train_generic_apply_flat(const dvae_train_generic_plan_t* plan, float* params, float* m, float* v, void* ws, const float* flat, int step,
                                   double lr, double beta1, double beta2, double adam_eps, double grad_scale, void* stream);
+/* _apply_flat with the global gradient norm clipped on the device: torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type=2) over
+ * ALL tensors of the plan at once (one Adam, one norm), two launches and no host round trip.  With G = `flat`, gs = grad_scale:
+ *   s          = sum over the floats of the plan's tensors of (double)G[i]^2 (the alignment gaps count as zero whatever they hold);
+ *   total_norm = |gs| sqrt(s);   coef = min(1, max_norm / (total_norm + 1e-6));   gscale_eff = (float)(gs * coef), formed in double and
+ *                rounded once;
+ *   the update is _apply_flat's, element for element, with gscale_eff in the place of (float)grad_scale.  Where coef == 1 -- max_norm = +inf,
+ *   or any max_norm >= total_norm + 1e-6 -- parameters, moments and packed copies come out bit-identical to _apply_flat's.
+ * Order of summation: the norm launch gives workgroup c the chunk of floats [4096 c, 4096 (c + 1)) -- a compile-time constant, not a
+ * function of the grid or the part --; a thread adds its sixteen squares in address order, then lanes, then the four waves in order, and
+ * the partial goes to scratch[c] (doubles; dvae_train_gradnorm_scratch_bytes(plan->n_params) bytes, the caller's, 8-byte aligned).  The
+ * guarded apply launch sums the partials in every workgroup alike: thread t takes chunks t, t + 256, ... ascending, then lanes, then
+ * waves.  No floating-point atomics: the same `flat` gives the same s, coef and update on every run and on every rank, so replicas that
+ * exchanged `flat` stay equal.
+ * Skip rule: if s is not finite (an inf or NaN anywhere in the gradient, or an overflowing sum), NOTHING is written: parameters, both
+ * moments and both packed copies stay bit for bit as they were; *skipped_counter (a device int32 the caller zeroes and reads) goes up by
+ * one; total_norm is reported as it came out (inf or NaN) and coef as 0.  The caller's step count still advances: `step` is passed by
+ * value for the bias corrections and the host cannot know of the skip without a synchronisation, so the update after a skipped one runs
+ * with the bias corrections of one step later (a factor that tends to 1; the first steps of a run are where it matters).
+ * norm2_out: two device floats, {total_norm, coef} of this call.  DVAE_E_BADARG, before anything touches the device, for a null pointer,
+ * max_norm that is NaN or <= 0 (+inf is legal), a misaligned `flat` / scratch, and whatever _apply_flat refuses. */
+int64_t dvae_train_gradnorm_scratch_bytes(int64_t n_params);    /* 0 (and dvae_last_error) for n_params < 1 or >= 2^31 - 4096 */
+int dvae_train_generic_apply_flat_clipped(const dvae_train_generic_plan_t* plan, float* params, float* m, float* v, void* ws, const float* flat,
+                                          int step, double lr, double beta1, double beta2, double adam_eps, double grad_scale, double max_norm,
+                                          void* scratch, float* norm2_out, int32_t* skipped_counter, void* stream);
 
 /* ---- the fused train step for the label classifier alone (csrc/train_classifier.hip): Classifier([513, [h1, h2], y_dim]) of
  * packages/models/models.py -- relu, relu, sigmoid -- under binary_cross_entropy (packages/models/utils.py:55-56) and Adam: the loop body
@@ -311,6 +335,10 @@ int dvae_train_clf_reduce(const dvae_train_clf_plan_t* plan, void* ws, float* fl
                           void* stream);
 int dvae_train_clf_apply_flat(const dvae_train_clf_plan_t* plan, float* params, float* m, float* v, void* ws, const float* flat, int step, double lr,
                               double beta1, double beta2, double adam_eps, double grad_scale, void* stream);
+/* dvae_train_generic_apply_flat_clipped for this step: one norm over the six tensors. */
+int dvae_train_clf_apply_flat_clipped(const dvae_train_clf_plan_t* plan, float* params, float* m, float* v, void* ws, const float* flat, int step,
+                                      double lr, double beta1, double beta2, double adam_eps, double grad_scale, double max_norm, void* scratch,
+                                      float* norm2_out, int32_t* skipped_counter, void* stream);
 
 /* ---- the fused train step for M2_info of ANY covered size (csrc/train_info.hip): DeepGenerativeModel_v5 of packages/models/models.py:390-444
  * -- encoder on x alone, decoder on [z | y], a relu classifier on x, an adversarial auxiliary relu classifier on z -- under the loop body of
@@ -397,6 +425,10 @@ int dvae_train_info_eval(const dvae_train_info_plan_t* plan, void* ws, const flo
 int dvae_train_info_reduce(const dvae_train_info_plan_t* plan, void* ws, float* flat, int accumulate, float weight, float* losses8, void* stream);
 int dvae_train_info_apply_flat(const dvae_train_info_plan_t* plan, float* params, float* m, float* v, void* ws, const float* flat, int step, double lr,
                                double beta1, double beta2, double adam_eps, double grad_scale, void* stream);
+/* dvae_train_generic_apply_flat_clipped for this step (every mode): one norm over all 26 tensors. */
+int dvae_train_info_apply_flat_clipped(const dvae_train_info_plan_t* plan, float* params, float* m, float* v, void* ws, const float* flat, int step,
+                                       double lr, double beta1, double beta2, double adam_eps, double grad_scale, double max_norm, void* scratch,
+                                       float* norm2_out, int32_t* skipped_counter, void* stream);
 
 /* Per-kernel device time of the last `dvae_train_*` calls made with profiling enabled:
  * enable != 0 brackets each launch with hipEvents on its stream (a few us of host cost each).

@@ -18,7 +18,15 @@ inputs are resident on the device, the noise is passed in.
   2b the device time of each micro-batch (rows + weight gradients + reduce; events around one, a synchronise after it) by its position
      after the apply, as AccumulatedStep runs it and with a repack of the packed weight copies before every micro-batch, beside one
      plain step timed the same way: where an accumulated step's time goes at the largest geometries.
-  4  more than one device visible: frames/s over the ranks is NOT measured by this tool on a one-GPU machine; it says so."""
+  4  more than one device visible: frames/s over the ranks is NOT measured by this tool on a one-GPU machine; it says so.
+
+    python tools/bench_train_accumulate.py --clip [--out profiles/train_clip.json] [--reps 20]
+
+--clip measures what clipping the global gradient norm on the device costs (csrc/train_generic.hip: train_generic_gradnorm_kernel,
+train_generic_apply_clipped_kernel), against the unclipped call in the same run, alternating, at M2 z 32 / h (256, 64) / y 1 and the
+largest M2_info geometry, 128 and 8192 frames: the optimizer launch of apply() on the flat gradient of one micro-batch against the two
+launches of apply(max_norm=inf), and step() (three launches) against step(max_norm=inf) (five: the reduce and the norm launch more).
+max_norm = inf clips nothing, so both sides walk the same parameters."""
 import argparse, csv, ctypes, importlib, json, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -56,8 +64,8 @@ def alternating(fa, fb, reps):
     return summary(ua), summary(ub)
 
 
-def make(model, dims, ksplit=0):
-    kw = dict(batch=B, device="cuda:0", seed=0, ksplit=ksplit)
+def make(model, dims, ksplit=0, batch=B):
+    kw = dict(batch=batch, device="cuda:0", seed=0, ksplit=ksplit)
     return TI.make_info_trainer(dims, generic=True, **kw) if model == "M2_info" else T.make_trainer(model, dims, generic=True, **kw)
 
 
@@ -137,6 +145,40 @@ def by_position(model, dims, K=4, reps=8):
     return out
 
 
+def clip_cost(model, dims, batch, reps):
+    x, y, e = synth.device_batches(dims, batch, 1, 0, "cuda")[0]
+    tr = make(model, dims, batch=batch)
+    acc = A.AccumulatedStep(tr)
+    acc.micro(x, y, e)                                             # the flat gradient of one micro-batch
+    inf = float("inf")
+    ap, ac = alternating(lambda: tr._apply_flat(acc.flat, 1.0), lambda: tr._apply_flat_clipped(acc.flat, 1.0, inf), reps)
+    sp, sc = alternating(lambda: tr.step(x, y, e), lambda: tr.step(x, y, e, max_norm=inf), reps)
+    P = tr.plan.n_params
+    out = {"geometry": geometry(model, dims), "frames": batch, "n_params": P, "norm_chunks": (P + 4095) // 4096, "ksplit": tr.plan.ksplit,
+           "apply_us": ap, "apply_clipped_us": ac, "apply_added_us": round(ac["median"] - ap["median"], 2),
+           "apply_clipped_over_apply": round(ac["median"] / ap["median"], 4),
+           "step_us": sp, "step_clipped_us": sc, "step_added_us": round(sc["median"] - sp["median"], 2),
+           "step_clipped_over_step": round(sc["median"] / sp["median"], 4),
+           "skipped_steps": tr.skipped_step_count(), "last_grad_norm": tr.grad_norm.cpu().tolist()}
+    print(json.dumps(out), flush=True)
+    return out
+
+
+def clip_mode(a):
+    reps = a.reps if a.reps != 10 else 20
+    res = {"device": torch.cuda.get_device_name(0), "reps": reps, "calls_per_window": INNER,
+           "method": "device time from events around 10 calls in a row; median (min, max) of `reps` windows after a warm-up window; the two "
+                     "sides of a comparison alternate window by window; max_norm = inf", "clip": []}
+    for model, dims in (GEOMETRIES[0], GEOMETRIES[3]):
+        for batch in (128, B):
+            res["clip"].append(clip_cost(model, dims, batch, reps))
+            torch.cuda.empty_cache()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 def kernels_only():
     """For a kernel trace: 20 effective steps of two micro-batches at the M2_info largest geometry, ksplit as the plan chooses."""
     model, dims = GEOMETRIES[3]
@@ -164,10 +206,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--kernels-only", action="store_true")
+    ap.add_argument("--clip", action="store_true", help="the cost of clipping the global gradient norm on the device (see the module's text)")
     ap.add_argument("--trace-stats", default=None, help="kernel_stats.csv of a kernel trace of --kernels-only")
     a = ap.parse_args()
     if a.kernels_only:
         return kernels_only()
+    if a.clip:
+        return clip_mode(a)
     res = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "steps_per_window": INNER, "effective_steps": [], "reduce_alone": []}
     for model, dims in GEOMETRIES:
         res["effective_steps"] += effective_steps(model, dims, a.reps)
