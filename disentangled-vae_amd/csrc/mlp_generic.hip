@@ -88,6 +88,7 @@ struct MlpArgs {
     int y_out;
     float *soft, *hard, *logits;             // [N][y_out]; logits may be null
     int64_t tile0, ntiles;
+    const float *nmean, *ndiv;               // NORM: [513] mean and fl32(std + fl32(eps)) of the standardised encoder input
 };
 
 // acc += W[row tile] (16 x 16 kb) * act (16 kb x 16 frames): W in fragment order, act in LDS as [k][16]
@@ -110,7 +111,8 @@ __device__ __forceinline__ float mlp_act(float v) {
 }
 
 // CLF = 0: the encoder (tanh, heads, reparametrisation, column output); CLF = 1: the classifier (relu, sigmoid, hard labels)
-template <int CLF>
+// NORM (the encoder only): the x block is (p - mean) / div, formed after the power, by the rounding of the train step (train_generic.hip)
+template <int CLF, int NORM = 0>
 __global__ __launch_bounds__(256) void mlp_generic_kernel(const MlpArgs g) {
     extern __shared__ __attribute__((aligned(16))) float msm[];
     float* In = msm;                                    // [528 + yp][16]; then the output tile [outp][16]
@@ -162,6 +164,7 @@ __global__ __launch_bounds__(256) void mlp_generic_kernel(const MlpArgs g) {
                     } else {
                         p = ((const float*)g.src)[at];
                     }
+                    if (NORM) p = __fdiv_rn(__fsub_rn(p, g.nmean[k]), g.ndiv[k]);
                 }
                 In[k * MT + c] = p;
             }
@@ -283,7 +286,7 @@ static void mlp_weights(MlpArgs& g, const MlpLayout& L, const float* w) {
     g.b1 = w + L.oB1; g.b2 = w + L.oB2; g.b3 = w + L.oB3;
 }
 
-template <int CLF>
+template <int CLF, int NORM = 0>
 static int mlp_launch(const char* name, MlpArgs& g, const MlpLayout& L, hipStream_t s) {
     constexpr size_t LDS_MAX = 160 * 1024;
     if (L.lds_bytes > LDS_MAX) { set_error("%s: %zu B of LDS needed, %zu available", name, L.lds_bytes, LDS_MAX); return DVAE_E_UNSUPPORTED; }
@@ -292,7 +295,7 @@ static int mlp_launch(const char* name, MlpArgs& g, const MlpLayout& L, hipStrea
         int dev = 0;
         DVAE_HIP(hipGetDevice(&dev));
         if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-            hipError_t e = hipFuncSetAttribute((const void*)mlp_generic_kernel<CLF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
+            hipError_t e = hipFuncSetAttribute((const void*)mlp_generic_kernel<CLF, NORM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
             if (e != hipSuccess) { set_error("hipFuncSetAttribute(%s, %zu B LDS): %s", name, LDS_MAX, hipGetErrorString(e)); return (int)e; }
             if (dev >= 0 && dev < 64) attr_done[dev] = true;
         }
@@ -300,7 +303,7 @@ static int mlp_launch(const char* name, MlpArgs& g, const MlpLayout& L, hipStrea
     g.tile0 = g.lo / MT;
     g.ntiles = cdiv(g.hi, MT) - g.tile0;
     const int64_t blocks = g.ntiles < 2048 ? g.ntiles : 2048;         // the cap of the resident kernels; the rest strides
-    hipLaunchKernelGGL(mlp_generic_kernel<CLF>, dim3((unsigned)blocks), dim3(256), L.lds_bytes, s, g);
+    hipLaunchKernelGGL((mlp_generic_kernel<CLF, NORM>), dim3((unsigned)blocks), dim3(256), L.lds_bytes, s, g);
     DVAE_LAUNCH_OK(name);
     return 0;
 }
@@ -362,10 +365,10 @@ extern "C" int dvae_classify_generic_pack(int h1, int h2, int y_dim, const float
     return 0;
 }
 
-extern "C" int dvae_encode_generic_batch(const void* src, int src_complex, int64_t ld, const float* y, int64_t ldy, int64_t N, int U,
-                                         const int64_t* frame_off_host, const float* weights, int y_dim, int h1, int h2, int z_dim,
-                                         const float* eps, float* mu, float* log_var, float* z, float* Z, int64_t ntot,
-                                         const int64_t* col_host, const int64_t* tables_dev, void* stream) {
+static int encode_generic(const void* src, int src_complex, int64_t ld, const float* y, int64_t ldy, int64_t N, int U,
+                          const int64_t* frame_off_host, const float* weights, int y_dim, int h1, int h2, int z_dim,
+                          const float* eps, float* mu, float* log_var, float* z, float* Z, int64_t ntot,
+                          const int64_t* col_host, const int64_t* tables_dev, const float* nmean, const float* ndiv, void* stream) {
     DVAE_CHECK_ARG(src && frame_off_host && weights, "encode_generic_batch: null pointer");
     DVAE_CHECK_ARG(enc_dims_ok(y_dim, h1, h2, z_dim), "encode_generic_batch: y_dim %d, hidden %d / %d, z_dim %d (the kernel covers y_dim 0..%d, "
                    "hidden widths 1..%d, z_dim 1..%d)", y_dim, h1, h2, z_dim, CF, M_HMAX, M_ZMAX);
@@ -402,7 +405,29 @@ extern "C" int dvae_encode_generic_batch(const void* src, int src_complex, int64
     mlp_weights(g, L, weights);
     g.eps = eps; g.mu = mu; g.log_var = log_var; g.zs = z;
     g.Z = Z; g.ntot = ntot; g.U = U; g.tab = tables_dev;
+    if (nmean) {
+        g.nmean = nmean; g.ndiv = ndiv;
+        return mlp_launch<0, 1>("encode_generic_norm_kernel", g, L, (hipStream_t)stream);
+    }
     return mlp_launch<0>("encode_generic_kernel", g, L, (hipStream_t)stream);
+}
+
+extern "C" int dvae_encode_generic_batch(const void* src, int src_complex, int64_t ld, const float* y, int64_t ldy, int64_t N, int U,
+                                         const int64_t* frame_off_host, const float* weights, int y_dim, int h1, int h2, int z_dim,
+                                         const float* eps, float* mu, float* log_var, float* z, float* Z, int64_t ntot,
+                                         const int64_t* col_host, const int64_t* tables_dev, void* stream) {
+    return encode_generic(src, src_complex, ld, y, ldy, N, U, frame_off_host, weights, y_dim, h1, h2, z_dim, eps, mu, log_var, z, Z, ntot,
+                          col_host, tables_dev, nullptr, nullptr, stream);
+}
+
+extern "C" int dvae_encode_generic_batch_norm(const void* src, int src_complex, int64_t ld, const float* y, int64_t ldy, int64_t N, int U,
+                                              const int64_t* frame_off_host, const float* weights, int y_dim, int h1, int h2, int z_dim,
+                                              const float* eps, float* mu, float* log_var, float* z, float* Z, int64_t ntot,
+                                              const int64_t* col_host, const int64_t* tables_dev, const float* norm_mean,
+                                              const float* norm_div, void* stream) {
+    DVAE_CHECK_ARG(norm_mean && norm_div, "encode_generic_batch_norm: null norm_mean / norm_div (513 device floats each)");
+    return encode_generic(src, src_complex, ld, y, ldy, N, U, frame_off_host, weights, y_dim, h1, h2, z_dim, eps, mu, log_var, z, Z, ntot,
+                          col_host, tables_dev, norm_mean, norm_div, stream);
 }
 
 extern "C" int dvae_classify_generic_batch(const void* src, int src_complex, int64_t ld, int64_t N, int U, const int64_t* frame_off_host,

@@ -43,7 +43,7 @@ static bool dims_ok(int y, int z, int h1, int h2) {
     return y >= 0 && y <= GX && h1 >= 1 && h1 <= G_HMAX && h2 >= 1 && h2 <= G_HMAX && z >= 1 && z <= G_ZMAX;
 }
 
-static GLayout make_layout(int y, int z, int h1, int h2, int64_t B, int ksplit_hint) {
+static GLayout make_layout(int y, int z, int h1, int h2, int64_t B, int ksplit_hint, bool norm) {
     GLayout L;
     memset(&L, 0, sizeof(L));
     L.y = y; L.z = z; L.h1 = h1; L.h2 = h2;
@@ -75,6 +75,8 @@ static GLayout make_layout(int y, int z, int h1, int h2, int64_t B, int ksplit_h
     auto col = [&](int n) { const int at = s; s += n; return at; };
     L.s_h1e = col(L.h1p); L.s_h2e = col(L.h2p); L.s_z = col(L.zp); L.s_d1 = col(L.h2p); L.s_d2 = col(L.h1p);
     L.s_pe1 = col(L.h1p); L.s_pe2 = col(L.h2p); L.s_ph = col(2 * L.zp); L.s_pd1 = col(L.h2p); L.s_pd2 = col(L.h1p); L.s_da = col(GXP);
+    L.norm = norm ? 1 : 0;
+    if (norm) L.s_xn = col(GXP);                          // behind every other block: their columns do not move
     L.S = s;
     // frames, tiles, slices
     L.B = B;
@@ -129,7 +131,8 @@ static void make_gemms(const GLayout& L, GGemm* G) {
         m.dpre = dpre; m.nrt = nrt; m.rows = rows; m.wt = wt; m.bt = wt + 1; m.in_kind = kind; m.in_off = in_off; m.in_w = in_w; m.y_w = y_w;
         m.cols = in_w + y_w;
     };
-    set(0, L.s_pe1, L.h1p / 16, L.h1, 0, 0, 0, GX, L.y);
+    if (L.norm) set(0, L.s_pe1, L.h1p / 16, L.h1, 0, 1, L.s_xn, GX, L.y);      // the standardised x from the stash, labels behind it as in decoder layer 1
+    else set(0, L.s_pe1, L.h1p / 16, L.h1, 0, 0, 0, GX, L.y);
     set(1, L.s_pe2, L.h2p / 16, L.h2, 2, 1, L.s_h1e, L.h1, 0);
     set(2, L.s_ph, L.zp / 16, L.z, 4, 1, L.s_h2e, L.h2, 0);
     set(3, L.s_ph + L.zp, L.zp / 16, L.z, 6, 1, L.s_h2e, L.h2, 0);
@@ -149,8 +152,13 @@ struct GRowsArgs {
     float* stash; double* partials;
     float elbo_eps, invB;
     int fwd_only;
+    const float* nmean; const float* ndiv;    // NORM: [513] the mean and fl32(std + fl32(norm_eps)) of the standardised encoder input
 };
 
+// NORM (std_norm): encoder layer 1 reads xn = fl32(fl32(x - mean) / div) in the place of x -- the tile holds xn, which also goes to the
+// stash block s_xn for the weight gradient of that layer --, and the output layer takes the raw x of its loss terms from the caller's
+// memory again.  Everything else is the same code.
+template <bool NORM>
 __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L, const GRowsArgs g) {
     extern __shared__ __attribute__((aligned(16))) float gsm[];
     float* X = gsm;                                     // [528][16] x, then d loss / d a
@@ -197,7 +205,13 @@ __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L
             for (int cq = 0; cq < 4; ++cq) {
                 const int k = 16 * b + col, c = 4 * cq + quad;
                 const int64_t s = srow[c];
-                X[k * GT + c] = (k < GX && s >= 0) ? g.x[s * g.ldx + k] : 0.f;
+                float xv = (k < GX && s >= 0) ? g.x[s * g.ldx + k] : 0.f;
+                if (NORM) {
+                    // torch's (x - mean) / div: two correctly rounded operations; padded bins and frames past B stay exact zeros
+                    if (k < GX && s >= 0) xv = __fdiv_rn(__fsub_rn(xv, g.nmean[k]), g.ndiv[k]);
+                    if (bwd) g.stash[(r0 + c) * (int64_t)L.S + L.s_xn + k] = xv;
+                }
+                X[k * GT + c] = xv;
             }
         }
         for (int b = wave; b < ky; b += 4) {
@@ -298,6 +312,13 @@ __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L
         // ---- output layer: a = d2 D3^T + b, r = exp(a); Itakura-Saito x / r - log(x + eps) + a - 1; d loss / d a = (1 - x / r) / B -> X ----
         for (int t = wave; t < GKX; t += 4) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            float xraw[4] = {0.f, 0.f, 0.f, 0.f};
+            if (NORM && fok) {                          // requested before the product: four consecutive bins of this lane's frame
+                const float* xp = g.x + srow[col] * g.ldx + 16 * t + 4 * quad;
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (16 * t + 4 * quad + r < GX) xraw[r] = xp[r];
+            }
             acc = tg_gemm(acc, wp + L.D3 + (int64_t)t * k1 * 256, k1, Bf, lane);
             f32x4 da;
 #pragma unroll
@@ -305,7 +326,7 @@ __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L
                 const int row = 16 * t + 4 * quad + r;
                 const bool ok = fok && row < GX;
                 const float a = acc[r] + wp[L.bd3 + row];
-                const float xv = X[row * GT + col];
+                const float xv = NORM ? xraw[r] : X[row * GT + col];
                 const float q = xv * expf(-a);
                 if (ok) sum_is += (double)(q - logf(xv + g.elbo_eps) + a - 1.f);
                 da[r] = ok ? (1.f - q) * g.invB : 0.f;
@@ -770,7 +791,8 @@ static int plan_layout(const char* who, const dvae_train_generic_plan_t* plan, G
     DVAE_CHECK_ARG((plan->model == DVAE_MODEL_M1 || plan->model == DVAE_MODEL_M2) && plan->precision == DVAE_PREC_F32 &&
                    dims_ok(plan->y_dim, plan->z_dim, plan->h1, plan->h2) && (plan->model == DVAE_MODEL_M1) == (plan->y_dim == 0) && plan->B >= 1,
                    "%s: not a plan of dvae_train_generic_plan", who);
-    L = make_layout(plan->y_dim, plan->z_dim, plan->h1, plan->h2, plan->B, plan->ksplit);
+    DVAE_CHECK_ARG(plan->std_norm == 0 || plan->std_norm == 1, "%s: std_norm %d in the plan (0 or 1)", who, plan->std_norm);
+    L = make_layout(plan->y_dim, plan->z_dim, plan->h1, plan->h2, plan->B, plan->ksplit, plan->std_norm != 0);
     DVAE_CHECK_ARG(L.ws_bytes == plan->workspace_bytes && L.nslices == plan->ksplit && L.n_params == plan->n_params &&
                    L.slice_frames == plan->slice_frames, "%s: the plan was changed after dvae_train_generic_plan", who);
     return 0;
@@ -783,6 +805,8 @@ static int check_inputs(const char* who, const dvae_train_generic_plan_t* plan, 
     DVAE_CHECK_ARG((plan->y_dim > 0) == (y != nullptr), "%s: y must be given exactly when y_dim > 0 (y_dim %d)", who, plan->y_dim);
     DVAE_CHECK_ARG(!y || (ldy >= plan->y_dim && ldy < ((int64_t)1 << 20)), "%s: leading dimension of y %lld for y_dim %d", who, (long long)ldy, plan->y_dim);
     DVAE_CHECK_ARG(!plan->row_index || plan->row_count >= 1, "%s: a gather table needs row_count >= 1 (got %lld)", who, (long long)plan->row_count);
+    DVAE_CHECK_ARG(!plan->std_norm || (plan->norm_mean && plan->norm_div && (plan->norm_mean & 3) == 0 && (plan->norm_div & 3) == 0),
+                   "%s: a plan with std_norm needs the device tables norm_mean and norm_div (513 floats each)", who);
     return 0;
 }
 
@@ -818,15 +842,21 @@ static int launch_apply(const GLayout& L, const ApplyArgs& a, char* ws, bool ada
 
 static int launch_rows(const dvae_train_generic_plan_t* plan, const GLayout& L, char* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
                        const float* eps, float elbo_eps, bool fwd_only, hipStream_t s) {
-    static bool attr_done[64] = {};
-    if (int rc = raise_lds_limit((const void*)train_generic_rows_kernel, "train_generic_rows_kernel", L.lds_bytes, attr_done)) return rc;
+    static bool attr_done[2][64] = {};
+    const void* kernel = L.norm ? (const void*)train_generic_rows_kernel<true> : (const void*)train_generic_rows_kernel<false>;
+    if (int rc = raise_lds_limit(kernel, "train_generic_rows_kernel", L.lds_bytes, attr_done[L.norm])) return rc;
     GRowsArgs g;
     memset(&g, 0, sizeof(g));
     g.x = x; g.ldx = ldx; g.y = y; g.ldy = ldy; g.eps = eps;
     g.row_index = (const int64_t*)(uintptr_t)plan->row_index; g.row_count = plan->row_count; g.bad = (int*)(uintptr_t)plan->bad_row_counter;
     g.ws = (float*)ws; g.stash = (float*)(ws + L.o_stash); g.partials = (double*)(ws + L.o_partials);
     g.elbo_eps = elbo_eps; g.invB = (float)(1.0 / (double)L.B); g.fwd_only = fwd_only ? 1 : 0;
-    hipLaunchKernelGGL(train_generic_rows_kernel, dim3((unsigned)L.rows_grid), dim3(256), (size_t)L.lds_bytes, s, L, g);
+    if (L.norm) {
+        g.nmean = (const float*)(uintptr_t)plan->norm_mean; g.ndiv = (const float*)(uintptr_t)plan->norm_div;
+        hipLaunchKernelGGL(train_generic_rows_kernel<true>, dim3((unsigned)L.rows_grid), dim3(256), (size_t)L.lds_bytes, s, L, g);
+    } else {
+        hipLaunchKernelGGL(train_generic_rows_kernel<false>, dim3((unsigned)L.rows_grid), dim3(256), (size_t)L.lds_bytes, s, L, g);
+    }
     DVAE_LAUNCH_OK("train_generic_rows_kernel");
     return 0;
 }
@@ -852,7 +882,13 @@ using namespace dvae::tg;
 
 extern "C" int dvae_train_generic_plan(int model, int y_dim, int z_dim, int h1, int h2, int precision, int64_t B, int ksplit_hint,
                                        dvae_train_generic_plan_t* plan) {
+    return dvae_train_generic_plan_norm(model, y_dim, z_dim, h1, h2, precision, B, ksplit_hint, 0, plan);
+}
+
+extern "C" int dvae_train_generic_plan_norm(int model, int y_dim, int z_dim, int h1, int h2, int precision, int64_t B, int ksplit_hint,
+                                            int std_norm, dvae_train_generic_plan_t* plan) {
     DVAE_CHECK_ARG(plan, "train_generic_plan: null plan");
+    DVAE_CHECK_ARG(std_norm == 0 || std_norm == 1, "train_generic_plan: std_norm %d (0: the encoder reads x, 1: the standardised x)", std_norm);
     const char* limits = "the generic train step covers M1 (y_dim 0) and M2 (y_dim 1..513) at x 513, hidden widths 1..512, z_dim 1..128, exact fp32";
     if (model != DVAE_MODEL_M1 && model != DVAE_MODEL_M2) {
         set_error("train_generic_plan: model %d (M2_info and M2_DEC exist at the reference geometry only: dvae_train_plan); %s", model, limits);
@@ -866,8 +902,9 @@ extern "C" int dvae_train_generic_plan(int model, int y_dim, int z_dim, int h1, 
     DVAE_CHECK_ARG((model == DVAE_MODEL_M1) == (y_dim == 0), "train_generic_plan: model M%d with y_dim %d; %s", model, y_dim, limits);
     DVAE_CHECK_ARG(B >= 1 && B < ((int64_t)1 << 31), "train_generic_plan: %lld frames", (long long)B);
     DVAE_CHECK_ARG(ksplit_hint >= 0 && ksplit_hint <= G_MAX_SLICES, "train_generic_plan: %d frame slices (0 = choose, at most %d)", ksplit_hint, G_MAX_SLICES);
-    const GLayout L = make_layout(y_dim, z_dim, h1, h2, B, ksplit_hint);
+    const GLayout L = make_layout(y_dim, z_dim, h1, h2, B, ksplit_hint, std_norm != 0);
     memset(plan, 0, sizeof(*plan));
+    plan->std_norm = std_norm;
     plan->model = model; plan->y_dim = y_dim; plan->z_dim = z_dim; plan->h1 = h1; plan->h2 = h2; plan->precision = precision;
     plan->ksplit = L.nslices; plan->n_tensors = M_NT; plan->B = B; plan->n_params = L.n_params;
     for (int t = 0; t < M_NT; ++t) { plan->tensor_offset[t] = L.toff[t]; plan->tensor_rows[t] = L.trows[t]; plan->tensor_cols[t] = L.tcols[t]; }

@@ -210,6 +210,9 @@ struct GLayout {
     int64_t lds_bytes;
     int64_t toff[G_NT];
     int trows[G_NT], tcols[G_NT];
+    // std_norm (dvae_train_generic_plan_norm): encoder layer 1 reads the standardised x; its stash block of GXP columns sits behind s_da, so
+    // every other column, S and the workspace of a plan without std_norm are what they are without these two fields
+    int norm, s_xn;
 };
 
 }  // namespace tg

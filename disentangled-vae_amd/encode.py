@@ -81,10 +81,17 @@ class EncoderPack:
     """The eight state_dict tensors of an Encoder in one contiguous float32 device buffer, the layout of dvae_encode_batch:
     W1 [128][513 + y_dim] | b1 | W2 [128][128] | b2 | Wmu [16][128] | bmu | Wlv [16][128] | blv.  repack(encoder) after training.
     generic=True: the fragment-order copy of dvae_encode_generic_pack for the generic kernel, which covers every geometry
-    encoder_kind names (the reference's too); z_dim, h1, h2, y_dim: the geometry."""
+    encoder_kind names (the reference's too); z_dim, h1, h2, y_dim: the geometry.
+    norm=(mean, std) (513 floats each, as GenericTrainer's std_norm; norm_eps as there): the pack of an encoder trained on
+    standardised input -- always the generic one --, whose x block is (x - mean) / (std + norm_eps) formed in the kernel after the
+    power, torch's float32 bits (dvae_encode_generic_batch_norm); labels are not normalised."""
 
-    def __init__(self, encoder, y_dim, generic=False):
-        self.generic = bool(generic)
+    def __init__(self, encoder, y_dim, generic=False, norm=None, norm_eps=1e-8):
+        self.generic = bool(generic) or norm is not None
+        self.norm = None
+        if norm is not None:
+            from .trainer_generic import check_std_norm
+            self._norm_host = check_std_norm(norm, norm_eps, "EncoderPack: norm")[:2]
         if self.generic:
             dims = _generic_dims(encoder, y_dim)
             if dims is None:
@@ -121,6 +128,8 @@ class EncoderPack:
                                                      N.ptr(ts[6]), ts[6].stride(0), N.ptr(ts[7]), N.ptr(self.weights), N.stream()),
                         "dvae_encode_generic_pack")
             self._keep = ts                  # the pack kernels read them on the stream
+            if getattr(self, "_norm_host", None) is not None and (self.norm is None or self.norm[0].device != dev):
+                self.norm = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in self._norm_host)      # (mean, div)
             return
         flat = torch.cat([t.reshape(-1) for t in ts])
         want = N.load().dvae_encode_weights_floats(self.y_dim)
@@ -132,10 +141,11 @@ class EncoderPack:
             self.weights.copy_(flat)
 
 
-def pack_encoder(encoder, y_dim):
+def pack_encoder(encoder, y_dim, norm=None, norm_eps=1e-8):
     """The pack of `encoder` by encoder_kind: the resident pack wherever it applies, the generic one for every other covered
-    geometry; TypeError naming the shape and the limits for an encoder no kernel covers."""
-    return EncoderPack(encoder, y_dim, generic=encoder_kind(encoder, y_dim) != "resident")
+    geometry and whenever norm=(mean, std) is given; TypeError naming the shape and the limits for an encoder no kernel covers."""
+    kw = {} if norm is None else dict(norm=norm, norm_eps=norm_eps)
+    return EncoderPack(encoder, y_dim, generic=encoder_kind(encoder, y_dim) != "resident", **kw)
 
 
 class LatentBatch:
@@ -223,6 +233,14 @@ def encode_rows(pack, src, frame_off, y=None, eps=None, mu=None, log_var=None, z
         if tables_dev is None:
             tables_dev = R.upload(np.concatenate([off, col]), src.device)
     with torch.cuda.device(src.device):
+        if pack.generic and pack.norm is not None:
+            N.check(lib.dvae_encode_generic_batch_norm(N.ptr(src), int(is_complex), ld, N.ptr(y), N.ld(y) if y is not None else 0, n, off.size - 1,
+                                                       off.ctypes.data, N.ptr(pack.weights), pack.y_dim, pack.h1, pack.h2, pack.z_dim, N.ptr(eps),
+                                                       N.ptr(mu), N.ptr(log_var), N.ptr(z), N.ptr(Z), ntot,
+                                                       col.ctypes.data if col is not None else None,
+                                                       N.ptr(tables_dev) if Z is not None else None, N.ptr(pack.norm[0]), N.ptr(pack.norm[1]),
+                                                       N.stream()), "dvae_encode_generic_batch_norm")
+            return
         if pack.generic:
             N.check(lib.dvae_encode_generic_batch(N.ptr(src), int(is_complex), ld, N.ptr(y), N.ld(y) if y is not None else 0, n, off.size - 1,
                                                   off.ctypes.data, N.ptr(pack.weights), pack.y_dim, pack.h1, pack.h2, pack.z_dim, N.ptr(eps), N.ptr(mu),

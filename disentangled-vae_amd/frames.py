@@ -29,6 +29,32 @@ def _to_device_rows(a, device, chunk=1 << 18):
     return out
 
 
+def frame_stats(X, rows=None, bad=None):
+    """Per-bin (mean, std) of the frames of X, float32 device tensors [513]: the X_train_mean / X_train_std of the reference's
+    create_train_set.py, formed on the device in two launches (include/dvae.h: dvae_frame_stats -- the formula in double, the
+    order of summation fixed, std 0 and not NaN for a constant bin).  X: float32 CUDA rows [N, >= 513 by stride] (DeviceFrames.x, a
+    FrameBatch's X).  rows: an int64 CUDA index tensor (a train split of a larger store); an index outside the store is counted in
+    `bad` (an int32 CUDA tensor of one element, optional) and left out.  Fewer than two frames: ValueError."""
+    if not (torch.is_tensor(X) and X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and X.shape[1] >= F_BINS and X.shape[0] >= 1
+            and X.stride(1) == 1 and (X.shape[0] == 1 or X.stride(0) >= F_BINS)):
+        raise TypeError(f"frame_stats: X must be float32 CUDA rows [N, {F_BINS}] (row stride >= {F_BINS})")
+    if rows is not None and not (torch.is_tensor(rows) and rows.device == X.device and rows.dtype == torch.int64 and rows.dim() == 1
+                                 and rows.is_contiguous()):
+        raise TypeError(f"frame_stats: rows must be a contiguous int64 tensor [n] on {X.device}")
+    if bad is not None and not (torch.is_tensor(bad) and bad.device == X.device and bad.dtype == torch.int32 and bad.numel() == 1):
+        raise TypeError(f"frame_stats: bad must be an int32 tensor of one element on {X.device}")
+    n = X.shape[0] if rows is None else rows.numel()
+    if n < 2:
+        raise ValueError(f"frame_stats: {n} frames (the standard deviation divides by n - 1: at least 2)")
+    lib = N.load()
+    with torch.cuda.device(X.device):
+        ws = torch.empty(lib.dvae_frame_stats_workspace_bytes(n) // 8, dtype=torch.float64, device=X.device)
+        out = torch.empty((2, F_BINS), dtype=torch.float32, device=X.device)
+        N.check(lib.dvae_frame_stats(N.ptr(X), N.ld(X), X.shape[0], N.ptr(rows), 0 if rows is None else n, N.ptr(out[0]), N.ptr(out[1]),
+                                     N.ptr(bad), N.ptr(ws), N.stream()), "dvae_frame_stats")
+    return out[0], out[1]
+
+
 class DeviceFrames:
     """Frames X [N][513] and labels Y [N][y_dim] resident in HBM.
 
@@ -82,6 +108,18 @@ class DeviceFrames:
         lib = N.load()
         N.check(lib.dvae_gather_rows(N.ptr(src), src.stride(0), src.shape[0], N.ptr(idx), idx.numel(), src.shape[1], N.ptr(dst),
                                      dst.stride(0), N.ptr(self._bad), N.stream()), "dvae_gather_rows")
+
+    def stats(self, rows=None):
+        """(mean, std) per bin over the store, or over its rows `rows` (int64 device indices: the train split), as frame_stats; an
+        index outside the store goes to bad_row_count()."""
+        return frame_stats(self.x, rows, self._bad)
+
+    def bad_row_count(self):
+        """Indices outside the store that stats() and the epoch gathers skipped since the last call (synchronises)."""
+        n = int(self._bad.item())
+        if n:
+            self._bad.zero_()
+        return n
 
     def shuffled(self, generator=None):
         """One epoch's order: returns (x, y) permuted copies (buffers are reused from epoch to epoch)."""

@@ -59,6 +59,9 @@ SIGNATURES = {
     "dvae_istft_batch": (c_i, [c_vp, c_i64, c_vp, c_i, c_i, c_i, c_vp, c_i64, c_i, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "dvae_transpose": (c_i, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp]),
     "dvae_gather_rows": (c_i, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i, c_vp, c_i64, c_vp, c_vp]),
+    "dvae_frame_stats_chunk": (c_i, []),
+    "dvae_frame_stats_workspace_bytes": (c_sz, [c_i64]),
+    "dvae_frame_stats": (c_i, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dvae_vad_workspace_bytes": (c_sz, [c_i64]),
     "dvae_vad_labels": (c_i, [c_vp, c_i, c_i64, c_i, c_i, c_i64, c_d, c_vp, c_vp, c_vp]),
     "dvae_ibm_workspace_bytes": (c_sz, []),
@@ -90,6 +93,8 @@ SIGNATURES = {
     "dvae_encode_generic_batch": (c_i, [c_vp, c_i, c_i64, c_vp, c_i64, c_i64, c_i, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
                                         c_vp, c_vp, c_vp]),
     "dvae_classify_generic_batch": (c_i, [c_vp, c_i, c_i64, c_i64, c_i, c_vp, c_vp, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp]),
+    "dvae_encode_generic_batch_norm": (c_i, [c_vp, c_i, c_i64, c_vp, c_i64, c_i64, c_i, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                             c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     # include/dvae_train.h (plan pointers are passed with ctypes.byref)
     "dvae_train_plan": (c_i, [c_i, c_i, c_i, c_i64, c_i, c_vp]),
     "dvae_train_init": (c_i, [c_vp, c_vp, c_vp, c_vp]),
@@ -108,6 +113,7 @@ SIGNATURES = {
     "dvae_module_forward": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_i, c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_i, c_vp]),
     "dvae_module_backward": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_i, c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_i, c_vp]),
     "dvae_train_generic_plan": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, c_i64, c_i, c_vp]),
+    "dvae_train_generic_plan_norm": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, c_i64, c_i, c_i, c_vp]),
     "dvae_train_generic_init": (c_i, [c_vp, c_vp, c_vp, c_vp]),
     "dvae_train_generic_repack": (c_i, [c_vp, c_vp, c_vp, c_vp]),
     "dvae_train_generic_grads": (c_i, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_f, c_vp]),

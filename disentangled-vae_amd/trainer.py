@@ -495,24 +495,31 @@ class Trainer:
         return {n: (ms[i], calls[i]) for i, n in enumerate(names)}
 
 
-def trainer_kind(model, dims):
+def trainer_kind(model, dims, std_norm=False):
     """Which fused train step serves (model, dims): "resident" (the hand-tuned kernels of the reference's geometry, supported()),
     "generic" (csrc/train_generic.hip: M1 / M2, x 513, y_dim 0 / 1..513, two hidden widths 1..512, z_dim 1..128, fp32) or None.
-    Host logic only."""
+    The resident step has no standardised encoder input, so std_norm goes to the generic step at the reference geometry too (None
+    for M2_info: no fused step offers it there).  Host logic only."""
     from . import trainer_generic as G
     try:
-        if supported(model, dims):
+        if not std_norm and supported(model, dims):
             return "resident"
     except KeyError:                    # a dims dict without one of the keys names no geometry of the resident step
         pass
     return "generic" if G.covered(model, dims) else None
 
 
-def make_trainer(model, dims, generic=False, **kw):
+def make_trainer(model, dims, generic=False, std_norm=None, norm_eps=1e-8, **kw):
     """A Trainer where supported() holds (the default there: it is the faster step), otherwise a GenericTrainer; raises with the limits
-    named when neither covers (model, dims).  generic=True puts the reference geometry on the generic step too."""
+    named when neither covers (model, dims).  generic=True puts the reference geometry on the generic step too, and so does
+    std_norm=(mean, std) (GenericTrainer), which only the generic M1 / M2 step offers."""
     from . import trainer_generic as G
-    kind = trainer_kind(model, dims)
+    if std_norm is not None:
+        if not G.covered(model, dims):
+            raise NotImplementedError(f"std_norm exists on the generic M1 / M2 step only; {G.LIMITS}; got {model} {dims}")
+        generic = True
+        kw.update(std_norm=std_norm, norm_eps=norm_eps)
+    kind = trainer_kind(model, dims, std_norm is not None)
     if kind is None:
         raise NotImplementedError(f"no fused train step for {model} {dims}: the resident step covers M1 / M2 (y 1 or 513) / M2_info (y 1) at "
                                   f"x 513, z 16, h [128, 128]; {G.LIMITS}")

@@ -70,7 +70,10 @@ class ClassifierTrainer:
     sync); `counts` then holds the batch's tp, tn, fp, fn (classify.f1_from_counts(tr.counts): accuracy, precision, recall, F1)."""
 
     def __init__(self, dims_or_module, params=None, batch=128, device="cuda:0", lr=1e-4, betas=(0.9, 0.999), adam_eps=1e-8, bce_eps=1e-8,
-                 seed=None, ksplit=0, share=None, precision="fp32"):
+                 seed=None, ksplit=0, share=None, precision="fp32", std_norm=None):
+        if std_norm is not None:
+            raise NotImplementedError("std_norm exists on the generic M1 / M2 step only (trainer_generic.GenericTrainer): the reference never "
+                                      f"standardises the classifier's input; {LIMITS}")
         self.plan = make_plan(dims_or_module, batch, precision, ksplit)          # refuses before anything touches the device
         if not torch.cuda.is_available():
             raise RuntimeError("ClassifierTrainer needs the MI355X HIP path (no CPU fallback)")

@@ -26,7 +26,8 @@ class GenericPlan(ctypes.Structure):
                 ("tensor_cols", ctypes.c_int32 * MAXT), ("workspace_bytes", ctypes.c_int64), ("grad_offset_bytes", ctypes.c_int64),
                 ("Bp", ctypes.c_int64), ("rows_grid", ctypes.c_int64), ("slice_frames", ctypes.c_int64), ("wgrad_items", ctypes.c_int64),
                 ("lds_bytes", ctypes.c_int64), ("loss_accum", ctypes.c_uint64), ("row_index", ctypes.c_uint64), ("row_count", ctypes.c_int64),
-                ("bad_row_counter", ctypes.c_uint64)]
+                ("bad_row_counter", ctypes.c_uint64), ("std_norm", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("norm_mean", ctypes.c_uint64),
+                ("norm_div", ctypes.c_uint64)]
 
 
 def covered(model, dims):
@@ -37,8 +38,42 @@ def covered(model, dims):
             and 1 <= int(dims.get("z_dim", 0)) <= 128 and ((model == "M1" and y == 0) or (model == "M2" and 1 <= int(y) <= 513)))
 
 
-def make_plan(model, dims, batch, precision="fp32", ksplit=0):
-    """dvae_train_generic_plan for (model, dims, batch): host only.  Raises NotImplementedError / ValueError with the library's message."""
+def check_std_norm(std_norm, norm_eps=1e-8, who="std_norm"):
+    """(mean, div) float32 numpy vectors [513] of std_norm=(mean, std): div = fl32(std + fl32(norm_eps)), formed here once in float32 as
+    torch forms `std + eps`.  mean, std: 513 finite floats each, std >= 0, numpy arrays or tensors on any device (shape [513] or the
+    file's (513, 1)).  ValueError otherwise; host only."""
+    try:
+        mean, std = std_norm
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: a pair (mean, std) of 513 floats each is expected") from None
+    out = []
+    for name, t in (("mean", mean), ("std", std)):
+        if torch.is_tensor(t):
+            t = t.detach().cpu().numpy()
+        try:
+            a = np.asarray(t)
+            if a.dtype.kind not in "fiu":
+                raise TypeError
+            a = a.astype(np.float32).reshape(-1)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: {name} must be 513 floats (a numpy array or a tensor)") from None
+        if a.size != 513 or not np.all(np.isfinite(a)):
+            raise ValueError(f"{who}: {name} must be 513 finite floats, got {a.size} values" + ("" if a.size != 513 else ", some not finite"))
+        out.append(a)
+    mean, std = out
+    if np.any(std < 0):
+        raise ValueError(f"{who}: std must be >= 0")
+    eps = np.float32(norm_eps)
+    if not (np.isfinite(eps) and eps >= 0):
+        raise ValueError(f"{who}: norm_eps {norm_eps!r} (a finite number >= 0)")
+    div = (std + eps).astype(np.float32)
+    if np.any(div == 0):
+        raise ValueError(f"{who}: std + norm_eps is zero in {int(np.sum(div == 0))} bins: the encoder input would not be finite")
+    return mean, div, std
+
+
+def make_plan(model, dims, batch, precision="fp32", ksplit=0, std_norm=False):
+    """dvae_train_generic_plan[_norm] for (model, dims, batch): host only.  Raises NotImplementedError / ValueError with the library's message."""
     lib = N.load()
     if model not in MODEL_CODE or precision not in PREC_CODE:
         raise NotImplementedError(f"{LIMITS}; got {model} {precision}")
@@ -46,8 +81,12 @@ def make_plan(model, dims, batch, precision="fp32", ksplit=0):
     if dims.get("x_dim") != 513 or len(h) != 2:
         raise NotImplementedError(f"{LIMITS}; got {model} {dims}")
     plan = GenericPlan()
-    rc = lib.dvae_train_generic_plan(MODEL_CODE[model], 0 if model == "M1" else int(dims["y_dim"]), int(dims["z_dim"]), int(h[0]), int(h[1]),
-                                     PREC_CODE[precision], int(batch), int(ksplit), ctypes.byref(plan))
+    args = (MODEL_CODE[model], 0 if model == "M1" else int(dims["y_dim"]), int(dims["z_dim"]), int(h[0]), int(h[1]), PREC_CODE[precision],
+            int(batch), int(ksplit))
+    if std_norm:
+        rc = lib.dvae_train_generic_plan_norm(*args, 1, ctypes.byref(plan))
+    else:                               # the entry point, and so the plan, of a trainer without the switch is the one it always was
+        rc = lib.dvae_train_generic_plan(*args, ctypes.byref(plan))
     if rc != 0:
         msg = lib.dvae_last_error().decode("utf-8", "replace")
         raise (NotImplementedError if rc == 1003 else ValueError)(f"{msg} (got {model} {dims}, precision {precision})")
@@ -56,14 +95,21 @@ def make_plan(model, dims, batch, precision="fp32", ksplit=0):
 
 class GenericTrainer:
     """One object = one model replica on one GPU.  step(x, y, eps_noise) enqueues one full train step and returns a device tensor
-    [ELBO, recon, KL] (no host sync)."""
+    [ELBO, recon, KL] (no host sync).
+
+    std_norm=(mean, std) (513 floats each; check_std_norm) is the scripts' switch of that name: the encoder reads
+    [(x - mean) / (std + norm_eps) | y], the float32 bits of torch's expression, while the loss is scored against the raw x
+    (scripts/training_M2.py:136-144).  Every method works as without it; state_dict() keeps the reference's keys only -- the tables
+    are data of the train set, read back with .std_norm."""
 
     def __init__(self, model, dims, params=None, batch=128, device="cuda:0", lr=1e-4, betas=(0.9, 0.999), adam_eps=1e-8, elbo_eps=1e-8,
-                 seed=None, ksplit=0, share=None, precision="fp32", world=1):
+                 seed=None, ksplit=0, share=None, precision="fp32", world=1, std_norm=None, norm_eps=1e-8):
         if int(world) != 1:
             raise NotImplementedError(f"data-parallel training is not built on the generic step ({LIMITS}); got world={world}: wrap a "
                                       "one-GPU trainer per rank in accumulate.AccumulatedStep(trainer, process_group)")
-        self.plan = make_plan(model, dims, batch, precision, ksplit)          # refuses before anything touches the device
+        tables = check_std_norm(std_norm, norm_eps, "GenericTrainer: std_norm") if std_norm is not None and share is None else None
+        self.plan = make_plan(model, dims, batch, precision, ksplit,          # refuses before anything touches the device
+                              std_norm=tables is not None or (share is not None and share._norm is not None))
         if not torch.cuda.is_available():
             raise RuntimeError("GenericTrainer needs the MI355X HIP path (no CPU fallback)")
         self.lib = N.load()
@@ -87,7 +133,16 @@ class GenericTrainer:
             self.ws = torch.empty(self.plan.workspace_bytes, dtype=torch.uint8, device=self.device)
             self.losses = torch.zeros(3, dtype=torch.float32, device=self.device)
             self.bad_rows = torch.zeros(1, dtype=torch.int32, device=self.device)
+            if share is not None:
+                self._norm = share._norm                    # (mean, div, std) on the device: a fork carries the tables
+            elif tables is not None:
+                self._norm = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in tables)
+            else:
+                self._norm = None
+        self.norm_eps = share.norm_eps if share is not None else norm_eps
         self.plan.bad_row_counter = self.bad_rows.data_ptr()
+        if self._norm is not None:
+            self.plan.norm_mean, self.plan.norm_div = self._norm[0].data_ptr(), self._norm[1].data_ptr()
         self.seed = int(seed) if seed is not None else (share.seed if share is not None else int(torch.initial_seed()))
         self._copy_version = self._shared["version"]
         if share is None:
@@ -106,6 +161,11 @@ class GenericTrainer:
     @property
     def step_count(self):
         return self._shared["step_count"]
+
+    @property
+    def std_norm(self):
+        """(mean, std) as given, float32 device tensors [513], or None."""
+        return None if self._norm is None else (self._norm[0], self._norm[2])
 
     @step_count.setter
     def step_count(self, v):

@@ -85,7 +85,9 @@ class InfoTrainer:
     model = "M2_info"
 
     def __init__(self, dims, params=None, batch=128, device="cuda:0", lr=1e-4, betas=(0.9, 0.999), adam_eps=1e-8, elbo_eps=1e-8,
-                 alpha=0.0, beta=10.0, gamma=1.0, seed=None, ksplit=0, share=None, dec_label="truth", aux_enc="bce"):
+                 alpha=0.0, beta=10.0, gamma=1.0, seed=None, ksplit=0, share=None, dec_label="truth", aux_enc="bce", std_norm=None):
+        if std_norm is not None:
+            raise NotImplementedError(STD_NORM_REFUSAL)
         self.plan = make_plan(dims, batch, ksplit, dec_label, aux_enc)      # refuses before anything touches the device
         self.dec_label, self.aux_enc = dec_label, aux_enc
         self.plan.info_alpha, self.plan.info_beta, self.plan.info_gamma = float(alpha), float(beta), float(gamma)
@@ -349,6 +351,10 @@ class InfoTrainer:
         self.plan.loss_accum = 0 if buf is None else buf.data_ptr()
 
 
+STD_NORM_REFUSAL = ("std_norm exists on the generic M1 / M2 step only (trainer_generic.GenericTrainer): the M2_info step's classifier and encoder "
+                    "read one x tile, and the reference's M2_info script loads the statistics without using them; " + LIMITS)
+
+
 def info_trainer_kind(dims, dec_label="truth", aux_enc="bce"):
     """Which fused train step serves M2_info at `dims`: "resident" (the hand-tuned kernels of the reference's geometry,
     trainer.supported), "generic" (csrc/train_info.hip) or None.  The resident step has the default options only, so any other
@@ -362,11 +368,13 @@ def info_trainer_kind(dims, dec_label="truth", aux_enc="bce"):
     return "generic" if covered(dims) else None
 
 
-def make_info_trainer(dims, generic=False, dec_label="truth", aux_enc="bce", **kw):
+def make_info_trainer(dims, generic=False, dec_label="truth", aux_enc="bce", std_norm=None, **kw):
     """The resident Trainer("M2_info", ...) where trainer.supported holds (the default there: the faster step, the 16-bit operand policies,
     data-parallel training), otherwise an InfoTrainer; generic=True, or an option other than dec_label="truth" / aux_enc="bce", puts the
     reference geometry on the generic step too.  Raises with the limits named when neither covers `dims`, and for a 16-bit policy or
     world != 1 on the generic step; ValueError naming the choices for an unknown option, before anything touches the device."""
+    if std_norm is not None:
+        raise NotImplementedError(STD_NORM_REFUSAL)
     kind = info_trainer_kind(dims, dec_label, aux_enc)
     if kind is None or (generic and not covered(dims)):
         raise NotImplementedError(f"no fused M2_info train step for {dims}: the resident step covers x 513, z 16, h [128, 128], y 1; {LIMITS}")

@@ -82,6 +82,8 @@ def main():
     ap.add_argument("--out", default="enhanced")
     ap.add_argument("--fused-start", action="store_true", help="McemBatch.init_parameters(fused_start=True): the start of the EM loop in a fixed "
                     "number of launches (one encoder launch for Z, one draw each for W and H); another draw order than the default")
+    ap.add_argument("--std-norm", default=None, metavar="NORM_PT", help="with --fused-start: the encoder was trained on standardised input "
+                    "(examples/train_fused.py --std-norm); the norm.pt written there (X_train_mean / X_train_std) goes into the encoder pack")
     ap.add_argument("--score", action="store_true", help="with --synthetic (whose speech is known): SI-SDR and ESTOI of mixture and estimate per utterance")
     ap.add_argument("--snr", type=float, nargs="+", default=None, help="with --synthetic: mix every utterance with synthetic noise at each of "
                     "these SNRs (dB) on the device instead of adding a fixed 0.2 * randn on the host")
@@ -149,7 +151,13 @@ def main():
         mb = McemBatch(vae, niter=a.niter, nsamples_E_step=10, burnin_E_step=30, nsamples_WF=25, burnin_WF=75, var_RW=0.01,
                        nmf_rank=10, precision=a.precision)                                                      # evaluate_ntcd_M2.py:92-99
     # the fused start's encoder by its kind too: labels reach the encoder of M2 (y_dim 1), not that of M2_info's M2v3 variant
-    enc_pack = encode.pack_encoder(mb.vae.encoder, 1 if mb.label_in_encoder else 0) if a.fused_start else None
+    norm = None
+    if a.std_norm:
+        if not a.fused_start:
+            ap.error("--std-norm applies to --fused-start (the encoder pack carries the statistics)")
+        st = torch.load(a.std_norm, map_location="cpu")
+        norm = (st["X_train_mean"], st["X_train_std"])
+    enc_pack = encode.pack_encoder(mb.vae.encoder, 1 if mb.label_in_encoder else 0, norm=norm) if a.fused_start else None
     mb.init_parameters(X, Y, fused_start=a.fused_start, encoder_pack=enc_pack)
     cost = mb.run()
     # Wiener filtering and ISTFT of both estimates in one launch: istft(S_hat, max_len=len(w)) / istft(N_hat, ...) per utterance

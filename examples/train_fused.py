@@ -28,7 +28,14 @@ Gradient accumulation and data parallelism on the generic steps (disentangled-va
 
 Checkpoints are plain state_dicts with the reference's keys: the reference's evaluate / reconstruct scripts load them.
 Differences from the scripts, all deliberate: the batch size is a flag (the fused step is meant for thousands of
-frames per step; `--batch 128` reproduces the scripts' setting), std_norm is not offered (off in every script).
+frames per step; `--batch 128` reproduces the scripts' setting).
+
+The scripts' std_norm switch (M1 / M2; off in every script, as here without the flag):
+
+    # the encoder reads (x - mean) / (std + 1e-8), the loss is scored against the raw frames; the statistics are the file's
+    # X_train_mean / X_train_std where it has them, else those of the train split taken on the device (DeviceFrames.stats);
+    # norm.pt beside the checkpoints holds them for examples/enhance_mcem.py --std-norm
+    python examples/train_fused.py --model M2 --synthetic 200000 --y-dim 1 --z-dim 32 --h-dim 256 64 --std-norm
 """
 import argparse
 import importlib
@@ -207,7 +214,12 @@ def main():
     ap.add_argument("--clip-norm", type=float, default=None, metavar="X",
                     help="generic steps: clip the global gradient norm of every optimizer step to X on the device (all tensors at once; a "
                          "gradient that is not finite skips its update); the epoch log gains the mean norm and the skipped steps")
+    ap.add_argument("--std-norm", action="store_true",
+                    help="M1 / M2 (generic step): standardise the encoder input with the train split's per-bin mean and standard deviation, "
+                         "from --h5 where the file has them, else computed on the device; writes norm.pt beside the checkpoints")
     a = ap.parse_args()
+    if a.std_norm and a.model == "M2_info":
+        ap.error("--std-norm applies to --model M1 / M2 (the reference's M2_info script loads the statistics without using them)")
     if a.accumulate < 1 or a.gpus < 1:
         ap.error("--accumulate and --gpus count from 1")
     if a.clip_norm is not None and not a.clip_norm > 0:
@@ -256,6 +268,19 @@ def main():
     else:
         if a.decoder_label != "truth" or a.aux_enc != "bce" or a.init_classifier:
             ap.error("--decoder-label, --aux-enc and --init-classifier apply to --model M2_info")
+        if a.std_norm:
+            stats = None
+            if a.h5:
+                from packages.data_handling import FrameFile
+                stats = FrameFile(a.h5, "train").stats()
+            source = "the file's" if stats is not None else "taken on the device from the train split"
+            mean, std = (torch.as_tensor(t) for t in (stats if stats is not None else train.stats()))
+            kw["std_norm"] = (mean, std)
+            if rank == 0:
+                os.makedirs(a.out, exist_ok=True)       # the shape of the reference's file: (513, 1)
+                torch.save({"X_train_mean": mean.cpu().reshape(513, 1), "X_train_std": std.cpu().reshape(513, 1)}, os.path.join(a.out, "norm.pt"))
+                print(f"std_norm: statistics {source}; mean {float(mean.min()):.3g} .. {float(mean.max()):.3g}, "
+                      f"std {float(std.min()):.3g} .. {float(std.max()):.3g} -> {os.path.join(a.out, 'norm.pt')}")
         tr = make_trainer(a.model, dims, **kw)
     tv = tr if accumulated else tr.fork(min(a.batch, len(valid)))         # (accumulated: validated in micro-batch pieces, below)
     train_trainers, valid_trainers = [tr], [tv]

@@ -237,6 +237,29 @@ int dvae_transpose(const float* in, int64_t rows, int64_t cols, int64_t ldi, flo
 int dvae_gather_rows(const float* src, int64_t ld, int64_t nsrc, const int64_t* idx, int64_t n, int cols, float* dst,
                      int64_t ldd, int* bad_count, void* stream);
 
+/* ---- train-set statistics (csrc/frame_stats.hip): X_train_mean / X_train_std of scripts/create_train_set.py:123-219 ----
+ * dvae_frame_stats: per-bin mean and standard deviation over the frames of X, float32 rows [n_store][ld] with ld >= 513 (the layout of
+ *   the frame store and of a FrameBatch's rows), into mean[513] and std[513] (device float32).  rows == NULL: every frame; else rows is
+ *   a device int64 table of n_rows indices into the store (a train split of a larger store; an index may repeat).
+ *   Contract: the reference's formula evaluated in double,
+ *     s = sum x,  q = sum x^2 (the square of a float32 is exact in double),  mean = s / n,  std = sqrt((q - n mean^2) / (n - 1)),
+ *   every operation rounded on its own, both results rounded to float32 at the end.  One deliberate departure from numpy: where rounding
+ *   makes q - n mean^2 negative (a constant bin), std is 0, not NaN.
+ *   An index outside [0, n_store) is never dereferenced: it is counted in *bad_count (device int, may be NULL) and left out of both sums;
+ *   n is the number of valid indices.  n < 2 is refused (DVAE_E_BADARG) where the host can see it -- n_store < 2 without a table,
+ *   n_rows < 2 with one --; a table that leaves fewer than two valid indices gives NaN in every bin.
+ *   Order of summation: two launches on `stream`, no host synchronisation.  Chunk c is the frames (or table entries)
+ *   [c C, (c + 1) C), C = DVAE_FRAME_STATS_CHUNK, a constant whatever the grid; within a chunk wave w of four adds the frames w, w + 4, ...
+ *   ascending into its own accumulators, then the waves are added in wave order; the finalising launch, one thread a bin, adds the chunks
+ *   in chunk order.  No floating-point atomics: the result depends on (X, rows) alone -- the same bits on every run, and for a table
+ *   of valid indices the bits of the contiguous copy of those rows (an index left out adds nothing but keeps its place in the order).
+ *   workspace: dvae_frame_stats_workspace_bytes(n) bytes of device memory, 8-byte aligned (0 for n < 1), n = n_rows or n_store. */
+#define DVAE_FRAME_STATS_CHUNK 4096
+int dvae_frame_stats_chunk(void);
+size_t dvae_frame_stats_workspace_bytes(int64_t n);
+int dvae_frame_stats(const float* X, int64_t ld, int64_t n_store, const int64_t* rows, int64_t n_rows, float* mean, float* std,
+                     int* bad_count, void* workspace, void* stream);
+
 /* ---- label makers of the training-set builders (packages/processing/target.py) ----
  * dvae_vad_labels: clean_speech_VAD (target.py:5-56, center=False): vad[t] = E[t] > 10^vad_threshold * min_t E[t],
  *   E[t] = sum of squares of frame t (double accumulation); y: n samples (float32, or float64 when in_f64), the zero
@@ -507,6 +530,15 @@ int dvae_encode_generic_batch(const void* src, int src_complex, int64_t ld, cons
                               const int64_t* tables_dev, void* stream);
 int dvae_classify_generic_batch(const void* src, int src_complex, int64_t ld, int64_t N, int U, const int64_t* frame_off_host,
                                 const float* weights, int y_dim, int h1, int h2, float* soft, float* hard, float* logits, void* stream);
+/* dvae_encode_generic_batch for an encoder trained on standardised input (the std_norm switch of the train scripts; dvae_train.h:
+ * dvae_train_generic_plan_norm): norm_mean, norm_div are device tables of 513 floats, and the x block of layer 1 is
+ * xn = fl32(fl32(p - norm_mean) / norm_div), p the power formed from a complex frame or read from a float row -- one IEEE subtraction
+ * and one correctly rounded IEEE division, torch's (p - mean) / div bit for bit.  Labels are not normalised; the padded inputs 513..527 and
+ * rows outside the table stay exact zeros.  Everything else, argument for argument, is dvae_encode_generic_batch. */
+int dvae_encode_generic_batch_norm(const void* src, int src_complex, int64_t ld, const float* y, int64_t ldy, int64_t N, int U,
+                                   const int64_t* frame_off_host, const float* weights, int y_dim, int h1, int h2, int z_dim,
+                                   const float* eps, float* mu, float* log_var, float* z, float* Z, int64_t ntot, const int64_t* col_host,
+                                   const int64_t* tables_dev, const float* norm_mean, const float* norm_div, void* stream);
 
 #ifdef __cplusplus
 }

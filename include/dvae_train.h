@@ -206,12 +206,28 @@ typedef struct {
     uint64_t row_index;
     int64_t  row_count;
     uint64_t bad_row_counter;
+    /* std_norm (dvae_train_generic_plan_norm; 0 from dvae_train_generic_plan): set by the planner and part of the layout.  With it the
+       caller sets, before the first launch, two device tables of 513 floats that stay alive and unchanged while the plan is used:
+       norm_mean = mean, norm_div = fl32(std + fl32(norm_eps)) formed once on the host in float32. */
+    int32_t  std_norm;
+    int32_t  reserved0;
+    uint64_t norm_mean;
+    uint64_t norm_div;
 } dvae_train_generic_plan_t;
 
 /* Host only.  ksplit_hint 0 = choose.  DVAE_E_UNSUPPORTED for M2_info / M2_DEC and the bf16 policies (they exist at the reference geometry
  * only), DVAE_E_BADARG naming the limits for a size outside them. */
 int dvae_train_generic_plan(int model, int y_dim, int z_dim, int h1, int h2, int precision, int64_t B, int ksplit_hint,
                             dvae_train_generic_plan_t* plan);
+/* dvae_train_generic_plan with the scripts' std_norm switch (scripts/training_M1.py:128-134, training_M2.py:136-144): std_norm 1 plans
+ * the step whose ENCODER reads [xn | y], xn = fl32(fl32(x - mean) / div) per bin -- one IEEE subtraction and one correctly rounded IEEE
+ * division in float32, bit for bit torch's (x - mean) / div --, while the labels, the Itakura-Saito term, its derivative and log(x + eps)
+ * use the raw x: `model(x_norm, y)` scored by `elbo(x, r, ...)`.  Padded bins and frames past B stay exact zeros.  The rows kernel keeps xn in
+ * a further stash block of 528 columns (behind every other block), from which the weight gradient of encoder layer 1 is formed; the
+ * weight-gradient, apply, reduce, norm and clipped-apply kernels are the ones of the plain step.  std_norm 0 is dvae_train_generic_plan:
+ * the same layout, workspace size, LDS and launches.  Every dvae_train_generic_* call below serves both kinds of plan. */
+int dvae_train_generic_plan_norm(int model, int y_dim, int z_dim, int h1, int h2, int precision, int64_t B, int ksplit_hint, int std_norm,
+                                 dvae_train_generic_plan_t* plan);
 /* One-time setup of `ws` (item table, packed weight copies from `params`); synchronises the stream once. */
 int dvae_train_generic_init(const dvae_train_generic_plan_t* plan, const float* params, void* ws, void* stream);
 /* Rebuild both packed weight copies after `params` was written from outside. */

@@ -53,6 +53,15 @@ class FrameFile:
         self._ensure()
         return self._x, self._y
 
+    def stats(self):
+        """The split's per-bin statistics as the file holds them (scripts/create_train_set.py:123-219: `X_<split>_mean` /
+        `X_<split>_std`, written as (513, 1)): (mean, std) float32 numpy vectors [513], or None where the file has none."""
+        with self._open() as f:
+            names = ['X_{}_{}'.format(self.split, k) for k in ('mean', 'std')]
+            if not all(n in f for n in names):
+                return None
+            return tuple(np.asarray(f[n][...], dtype=np.float32).reshape(-1) for n in names)
+
     def close(self):
         if self._h is not None:
             self._h.close()
