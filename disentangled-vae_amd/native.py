@@ -236,3 +236,15 @@ def as_f32_2d(t, what):
 
 def ld(t2):
     return t2.stride(0) if t2.shape[0] > 1 else max(t2.shape[1], 1)
+
+
+MAX_LD = 1 << 20          # the train steps' bound on a leading dimension (32-bit offsets inside a tile)
+
+
+def check_row_stride(t, width, name):
+    """ValueError unless the train-step kernels can read t [n, width] where it lies: with more than one row and unit column stride (a
+    tensor with another column stride is copied by the caller), the row stride must be at least the width -- rows that overlap or
+    repeat, as expand() and as_strided() make them, are refused -- and below MAX_LD.  One row has no stride to speak of.  Host only."""
+    if t.shape[0] > 1 and t.stride(1) == 1 and not width <= t.stride(0) < MAX_LD:
+        raise ValueError(f"{name}: row stride {t.stride(0)} of a [{t.shape[0]}, {width}] tensor (the rows must not overlap or repeat: at least "
+                         f"{width}, below {MAX_LD}); pass {name}.contiguous()")

@@ -309,6 +309,9 @@ class Trainer:
         if rows is not None:
             if not (rows.device == self.device and rows.dtype == torch.int64 and rows.shape == (B,) and rows.is_contiguous()):
                 raise ValueError(f"rows must be a contiguous int64 tensor [{B}] on {self.device}")
+        N.check_row_stride(x, 513, "x")                 # here, before a step is counted: the library would refuse only after
+        if self.y_dim:
+            N.check_row_stride(y, self.y_dim, "y")
         # the kernels clamp an index outside [0, n) to row 0 and count it in self.bad_rows (no out-of-range read)
         self.plan.row_index = 0 if rows is None else rows.data_ptr()
         self.plan.row_count = 0 if rows is None else n

@@ -233,6 +233,8 @@ class InfoTrainer:
             raise ValueError(f"eps_noise must be a float32 tensor [{B}, {self.z_dim}] on {self.device}")
         if rows is not None and not (rows.device == self.device and rows.dtype == torch.int64 and rows.shape == (B,) and rows.is_contiguous()):
             raise ValueError(f"rows must be a contiguous int64 tensor [{B}] on {self.device}")
+        N.check_row_stride(x, 513, "x")                 # here, before a step is counted: the library would refuse only after
+        N.check_row_stride(y, self.y_dim, "y")
         self.plan.row_index = 0 if rows is None else rows.data_ptr()
         self.plan.row_count = 0 if rows is None else n
 
