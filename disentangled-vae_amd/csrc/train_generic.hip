@@ -24,6 +24,9 @@
 //   * reduce kernel (gradient accumulation, data parallelism): the slabs of a micro-batch summed into one flat gradient; and, for
 //     global-norm clipping on the device, a norm kernel over that flat gradient (per-chunk sums of squares in double, fixed order) in
 //     front of a guarded instantiation of the apply kernel's body (train_generic.hpp: GNormArgs / GClipArgs).
+//   * module modes of the rows kernel (dvae_module_generic_forward / _backward; module_path.py: GenericModuleEngine): the forward chain
+//     with the model's outputs written, and the backward chain started from upstream gradients of (r, z, mu, log_var) in the place of
+//     the ELBO's -- the drop-in modules' forward as ONE autograd Function under the caller's own loss and optimizer.
 //   * 64-bit indexing throughout; a gather index outside [0, row_count) is never dereferenced (row 0 instead, counted).
 #include <math.h>
 #include <vector>
@@ -154,12 +157,31 @@ struct GRowsArgs {
     int fwd_only;
     const float* nmean; const float* ndiv;    // NORM: [513] the mean and fl32(std + fl32(norm_eps)) of the standardised encoder input
 };
+// the module modes (dvae_module_generic_forward / _backward): the model's outputs, or the upstream gradients of them (each may be null)
+struct GModuleArgs {
+    float* out_r; int64_t ld_r;       // [B][513]
+    float* out_mu; float* out_lv; float* out_z;       // [B][z]; out_z may be null
+    const float* g_r; int64_t ld_gr;  // [B][513]
+    const float* g_mu; const float* g_lv; const float* g_z;       // [B][z]
+};
+constexpr int ROWS_STEP = 0, ROWS_MODULE_FWD = 1, ROWS_MODULE_BWD = 2;
+struct __attribute__((packed, aligned(4))) G4U { f32x4 v; };      // 16 bytes at dword alignment (rows of 513 floats)
 
 // NORM (std_norm): encoder layer 1 reads xn = fl32(fl32(x - mean) / div) in the place of x -- the tile holds xn, which also goes to the
 // stash block s_xn for the weight gradient of that layer --, and the output layer takes the raw x of its loss terms from the caller's
 // memory again.  Everything else is the same code.
-template <bool NORM>
-__global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L, const GRowsArgs g) {
+// MODE (ROWS_STEP: the train step and its forward-only evaluation, the code it was before the other two existed):
+//   ROWS_MODULE_FWD  the forward chain alone -- no stash, no loss sums, no partials -- with the model's outputs written: r = exp(a) as four
+//                    consecutive bins of a lane's frame, mu, log_var and z from the reparametrisation phase.  Padded bins, padded latent
+//                    columns and frames past B are never written.
+//   ROWS_MODULE_BWD  the forward recomputed with the stash writes of a train step, then the same backward phases from upstream gradients
+//                    in the place of the ELBO's: da = g_r r; dz = dpre_d1 D1[:, :z] + g_z; d mu = dz + g_mu; d log_var = dz std eps / 2 +
+//                    g_lv.  No 1 / B and no KL term: the upstream gradients carry both.  A null pointer is a zero gradient; a frame past
+//                    B, a padded bin and a padded latent column contribute exact zeros.  The weight-gradient and reduce kernels read
+//                    the stash this leaves as they read a train step's.
+template <bool NORM, int MODE = ROWS_STEP>
+__global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L, const GRowsArgs g, const GModuleArgs mo) {
+    static_assert(MODE == ROWS_STEP || !NORM, "the module modes take the encoder input as it is given");
     extern __shared__ __attribute__((aligned(16))) float gsm[];
     float* X = gsm;                                     // [528][16] x, then d loss / d a
     float* Y = X + GT * GXP;                            // [yp][16]
@@ -172,7 +194,7 @@ __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L
     const int col = lane & 15, quad = lane >> 4;
     const int ky = L.yp >> 4, k1 = L.h1p >> 4, k2 = L.h2p >> 4, kz = L.zp >> 4;
     const float* wp = g.ws;
-    const bool bwd = !g.fwd_only;
+    const bool bwd = MODE == ROWS_MODULE_BWD || (MODE == ROWS_STEP && !g.fwd_only);
     double sum_is = 0.0, sum_kl = 0.0;
 
     for (int64_t tile = blockIdx.x; tile < L.tiles; tile += gridDim.x) {
@@ -273,10 +295,23 @@ __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L
             const float sd = expf(0.5f * lv), ev = expf(lv);
             const float zv = mu + sd * e;
             Bf[j * GT + c] = zv;
-            C[j * GT + c] = ok ? mu * g.invB : 0.f;
-            C[(L.zp + j) * GT + c] = ok ? -0.5f * (1.f - ev) * g.invB : 0.f;
-            C[(2 * L.zp + j) * GT + c] = 0.5f * sd * e;
-            if (ok) sum_kl += (double)(-0.5f * (lv - mu * mu - ev));
+            if constexpr (MODE == ROWS_STEP) {
+                C[j * GT + c] = ok ? mu * g.invB : 0.f;
+                C[(L.zp + j) * GT + c] = ok ? -0.5f * (1.f - ev) * g.invB : 0.f;
+                C[(2 * L.zp + j) * GT + c] = 0.5f * sd * e;
+                if (ok) sum_kl += (double)(-0.5f * (lv - mu * mu - ev));
+            } else if constexpr (MODE == ROWS_MODULE_FWD) {
+                if (ok) {
+                    const int64_t o = (r0 + c) * L.z + j;
+                    mo.out_mu[o] = mu; mo.out_lv[o] = lv;
+                    if (mo.out_z) mo.out_z[o] = zv;
+                }
+            } else {                                    // the upstream gradients of mu and log_var in the place of the KL parts
+                const int64_t o = (r0 + c) * L.z + j;
+                C[j * GT + c] = (ok && mo.g_mu) ? mo.g_mu[o] : 0.f;
+                C[(L.zp + j) * GT + c] = (ok && mo.g_lv) ? mo.g_lv[o] : 0.f;
+                C[(2 * L.zp + j) * GT + c] = 0.5f * sd * e;
+            }
             if (bwd) g.stash[(r0 + c) * (int64_t)L.S + L.s_z + j] = zv;
         }
         __syncthreads();
@@ -319,17 +354,40 @@ __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L
                 for (int r = 0; r < 4; ++r)
                     if (16 * t + 4 * quad + r < GX) xraw[r] = xp[r];
             }
+            f32x4 gr = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (MODE == ROWS_MODULE_BWD) {   // requested before the product as well: four consecutive bins of this lane's frame
+                if (fok && mo.g_r) {
+                    const float* gp = mo.g_r + (r0 + col) * mo.ld_gr + 16 * t + 4 * quad;
+                    if (16 * t + 4 * quad + 3 < GX) gr = reinterpret_cast<const G4U*>(gp)->v;
+                    else if (16 * t + 4 * quad < GX) gr[0] = gp[0];         // bin 512 (513 = 4 * 128 + 1: a group holds four bins or this one)
+                }
+            }
             acc = tg_gemm(acc, wp + L.D3 + (int64_t)t * k1 * 256, k1, Bf, lane);
+            if constexpr (MODE == ROWS_MODULE_FWD) {
+                f32x4 rv;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) rv[r] = expf(acc[r] + wp[L.bd3 + 16 * t + 4 * quad + r]);
+                if (fok) {
+                    float* rp = mo.out_r + (r0 + col) * mo.ld_r + 16 * t + 4 * quad;
+                    if (16 * t + 4 * quad + 3 < GX) reinterpret_cast<G4U*>(rp)->v = rv;
+                    else if (16 * t + 4 * quad < GX) rp[0] = rv[0];
+                }
+                continue;
+            }
             f32x4 da;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = 16 * t + 4 * quad + r;
                 const bool ok = fok && row < GX;
                 const float a = acc[r] + wp[L.bd3 + row];
-                const float xv = NORM ? xraw[r] : X[row * GT + col];
-                const float q = xv * expf(-a);
-                if (ok) sum_is += (double)(q - logf(xv + g.elbo_eps) + a - 1.f);
-                da[r] = ok ? (1.f - q) * g.invB : 0.f;
+                if constexpr (MODE == ROWS_MODULE_BWD) {
+                    da[r] = (ok && mo.g_r) ? gr[r] * expf(a) : 0.f;
+                } else {
+                    const float xv = NORM ? xraw[r] : X[row * GT + col];
+                    const float q = xv * expf(-a);
+                    if (ok) sum_is += (double)(q - logf(xv + g.elbo_eps) + a - 1.f);
+                    da[r] = ok ? (1.f - q) * g.invB : 0.f;
+                }
                 if (bwd) X[row * GT + col] = da[r];
             }
             st4(L.s_da, t, da);
@@ -369,7 +427,20 @@ __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L
         // ---- dz = dpre_d1 D1[:, :z]; d mu = dz + mu / B; d log_var = dz eps std / 2 + its KL part -> C rows 0 .. 2 zp - 1 ----
         for (int t = wave; t < kz; t += 4) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            float gz[4] = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (MODE == ROWS_MODULE_BWD) {   // the upstream gradient of z: four consecutive columns of this lane's frame
+                if (fok && mo.g_z) {
+                    const float* zp_ = mo.g_z + (r0 + col) * L.z + 16 * t + 4 * quad;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (16 * t + 4 * quad + r < L.z) gz[r] = zp_[r];
+                }
+            }
             acc = tg_gemm(acc, wp + L.D1zT + (int64_t)t * k2 * 256, k2, A, lane);
+            if constexpr (MODE == ROWS_MODULE_BWD) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[r] += gz[r];
+            }
             f32x4 dm, dl;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -409,6 +480,7 @@ __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L
             st4(L.s_pe1, t, d);
         }
     }
+    if constexpr (MODE != ROWS_STEP) return;           // no loss sums, no partials
     // the workgroup's loss sums: waves in order
     sum_is = wave_sum(sum_is); sum_kl = wave_sum(sum_kl);
     __syncthreads();                                    // the last tile's readers of X are done: its first bytes hold the sums
@@ -425,8 +497,6 @@ __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // weight-gradient kernel (GWgradArgs: train_generic.hpp; the classifier step launches it too)
-struct __attribute__((packed, aligned(4))) G4U { f32x4 v; };      // 16 bytes at dword alignment (rows of 513 floats)
-
 // One item = 64 rows of one matrix (four 16-row tiles of dPre) x four 64-column blocks of its input (the bias is one more block behind
 // them), one block a wave, x one frame slice.  A wave keeps a 64 x 64 block of dW in 16 accumulators: per four frames it loads one dPre value
 // per row tile (a quarter wave reads 16 consecutive floats of a frame) and ONE 16-byte piece of the input row -- columns 4 j .. 4 j + 3 of
@@ -841,21 +911,31 @@ static int launch_apply(const GLayout& L, const ApplyArgs& a, char* ws, bool ada
 }
 
 static int launch_rows(const dvae_train_generic_plan_t* plan, const GLayout& L, char* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
-                       const float* eps, float elbo_eps, bool fwd_only, hipStream_t s) {
-    static bool attr_done[2][64] = {};
-    const void* kernel = L.norm ? (const void*)train_generic_rows_kernel<true> : (const void*)train_generic_rows_kernel<false>;
-    if (int rc = raise_lds_limit(kernel, "train_generic_rows_kernel", L.lds_bytes, attr_done[L.norm])) return rc;
+                       const float* eps, float elbo_eps, bool fwd_only, hipStream_t s, int mode = ROWS_STEP, const GModuleArgs* module = nullptr) {
+    static bool attr_done[4][64] = {};
+    const void* kernel = mode == ROWS_MODULE_FWD ? (const void*)train_generic_rows_kernel<false, ROWS_MODULE_FWD>
+                       : mode == ROWS_MODULE_BWD ? (const void*)train_generic_rows_kernel<false, ROWS_MODULE_BWD>
+                       : L.norm ? (const void*)train_generic_rows_kernel<true> : (const void*)train_generic_rows_kernel<false>;
+    if (int rc = raise_lds_limit(kernel, "train_generic_rows_kernel", L.lds_bytes, attr_done[mode == ROWS_STEP ? L.norm : 1 + mode])) return rc;
+    GModuleArgs mo;
+    memset(&mo, 0, sizeof(mo));
+    if (module) mo = *module;
     GRowsArgs g;
     memset(&g, 0, sizeof(g));
     g.x = x; g.ldx = ldx; g.y = y; g.ldy = ldy; g.eps = eps;
     g.row_index = (const int64_t*)(uintptr_t)plan->row_index; g.row_count = plan->row_count; g.bad = (int*)(uintptr_t)plan->bad_row_counter;
     g.ws = (float*)ws; g.stash = (float*)(ws + L.o_stash); g.partials = (double*)(ws + L.o_partials);
     g.elbo_eps = elbo_eps; g.invB = (float)(1.0 / (double)L.B); g.fwd_only = fwd_only ? 1 : 0;
-    if (L.norm) {
+    const dim3 grid((unsigned)L.rows_grid), block(256);
+    if (mode == ROWS_MODULE_FWD) {
+        hipLaunchKernelGGL((train_generic_rows_kernel<false, ROWS_MODULE_FWD>), grid, block, (size_t)L.lds_bytes, s, L, g, mo);
+    } else if (mode == ROWS_MODULE_BWD) {
+        hipLaunchKernelGGL((train_generic_rows_kernel<false, ROWS_MODULE_BWD>), grid, block, (size_t)L.lds_bytes, s, L, g, mo);
+    } else if (L.norm) {
         g.nmean = (const float*)(uintptr_t)plan->norm_mean; g.ndiv = (const float*)(uintptr_t)plan->norm_div;
-        hipLaunchKernelGGL(train_generic_rows_kernel<true>, dim3((unsigned)L.rows_grid), dim3(256), (size_t)L.lds_bytes, s, L, g);
+        hipLaunchKernelGGL(train_generic_rows_kernel<true>, grid, block, (size_t)L.lds_bytes, s, L, g, mo);
     } else {
-        hipLaunchKernelGGL(train_generic_rows_kernel<false>, dim3((unsigned)L.rows_grid), dim3(256), (size_t)L.lds_bytes, s, L, g);
+        hipLaunchKernelGGL(train_generic_rows_kernel<false>, grid, block, (size_t)L.lds_bytes, s, L, g, mo);
     }
     DVAE_LAUNCH_OK("train_generic_rows_kernel");
     return 0;
@@ -1025,4 +1105,59 @@ extern "C" int dvae_train_generic_eval(const dvae_train_generic_plan_t* plan, vo
     if (int rc = launch_rows(plan, L, (char*)ws, x, ldx, y, ldy, eps_noise, elbo_eps, true, s)) return rc;
     const ApplyArgs a = apply_args(plan, L, nullptr, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, losses3);
     return launch_apply(L, a, (char*)ws, false, false, true, s);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// the whole-model autograd path of the drop-in modules at any covered size (disentangled-vae_amd/module_path.py: GenericModuleEngine)
+static int check_module(const char* who, const dvae_train_generic_plan_t* plan, const float* params, const void* ws, const float* x, int64_t ldx,
+                        const float* y, int64_t ldy, const float* eps) {
+    DVAE_CHECK_ARG(!plan->std_norm, "%s: a std_norm plan (the module path takes the encoder input as given: normalise x in torch and pass it)", who);
+    DVAE_CHECK_ARG(!plan->row_index, "%s: a gather table in the plan (row_index: the module path reads the batch itself)", who);
+    DVAE_CHECK_ARG(params, "%s: null pointer", who);
+    return check_inputs(who, plan, ws, x, ldx, y, ldy, eps);
+}
+
+extern "C" int dvae_module_generic_forward(const dvae_train_generic_plan_t* plan, const float* params, void* ws, const float* x, int64_t ldx,
+                                           const float* y, int64_t ldy, const float* eps_noise, float* out_r, int64_t ld_r, float* out_mu,
+                                           float* out_lv, float* out_z, int repack, void* stream) {
+    GLayout L;
+    if (int rc = plan_layout("module_generic_forward", plan, L)) return rc;
+    if (int rc = check_module("module_generic_forward", plan, params, ws, x, ldx, y, ldy, eps_noise)) return rc;
+    DVAE_CHECK_ARG(out_r && out_mu && out_lv, "module_generic_forward: null pointer (out_z alone may be null)");
+    DVAE_CHECK_ARG(ld_r >= GX && ld_r < ((int64_t)1 << 20), "module_generic_forward: ld_r %lld (the leading dimension of out_r: at least 513)", (long long)ld_r);
+    hipStream_t s = (hipStream_t)stream;
+    if (repack) {                                       // every element of both packed copies from `params`; the padding is dvae_train_generic_init's
+        const ApplyArgs a = apply_args(plan, L, (float*)params, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, nullptr);
+        if (int rc = launch_apply(L, a, (char*)ws, false, true, false, s)) return rc;
+    }
+    GModuleArgs mo;
+    memset(&mo, 0, sizeof(mo));
+    mo.out_r = out_r; mo.ld_r = ld_r; mo.out_mu = out_mu; mo.out_lv = out_lv; mo.out_z = out_z;
+    return launch_rows(plan, L, (char*)ws, x, ldx, y, ldy, eps_noise, 0.f, true, s, ROWS_MODULE_FWD, &mo);
+}
+
+extern "C" int dvae_module_generic_backward(const dvae_train_generic_plan_t* plan, const float* params, void* ws, const float* x, int64_t ldx,
+                                            const float* y, int64_t ldy, const float* eps_noise, const float* g_r, int64_t ld_gr,
+                                            const float* g_mu, const float* g_lv, const float* g_z, float* grad_flat, int accumulate,
+                                            void* stream) {
+    GLayout L;
+    if (int rc = plan_layout("module_generic_backward", plan, L)) return rc;
+    if (int rc = check_module("module_generic_backward", plan, params, ws, x, ldx, y, ldy, eps_noise)) return rc;
+    if (int rc = check_reduce_args("module_generic_backward", ws, grad_flat, accumulate, 1.f)) return rc;
+    DVAE_CHECK_ARG(!g_r || (ld_gr >= GX && ld_gr < ((int64_t)1 << 20)), "module_generic_backward: ld_gr %lld (the leading dimension of g_r: at least 513)",
+                   (long long)ld_gr);
+    hipStream_t s = (hipStream_t)stream;
+    GModuleArgs mo;
+    memset(&mo, 0, sizeof(mo));
+    mo.g_r = g_r; mo.ld_gr = ld_gr; mo.g_mu = g_mu; mo.g_lv = g_lv; mo.g_z = g_z;
+    if (int rc = launch_rows(plan, L, (char*)ws, x, ldx, y, ldy, eps_noise, 0.f, false, s, ROWS_MODULE_BWD, &mo)) return rc;
+    if (int rc = launch_wgrad(plan, L, (char*)ws, x, ldx, y, ldy, s)) return rc;
+    GReduceArgs g;                                      // the slabs in slab order into grad_flat; weight 1: the sum's bits; nothing to finalise
+    memset(&g, 0, sizeof(g));
+    g.f.a = apply_args(plan, L, nullptr, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, nullptr);
+    g.f.a.accum = nullptr;
+    make_tensors(L, g.f.t);
+    g.f.ws = (float*)ws; g.f.finalize = 0;
+    g.flat = grad_flat; g.accumulate = accumulate; g.weight = 1.f;
+    return launch_reduce_table(g, s);
 }

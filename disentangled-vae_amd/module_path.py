@@ -25,6 +25,26 @@ runs the per-layer Functions of ops.py on the exact fp32 matrix cores, like dire
 workspace is ever built for a forward-only call.  DVAE_MODULE_PATH=layers takes the per-layer path everywhere.
 
 MFMA operand policy: DVAE_MODULE_PRECISION (default bf16x3, the parity-grade split-bf16 policy; bf16 = fast and loose).
+
+Any other covered size (opt-in).  An M1 / M2 module of another geometry -- `h_dim = [256, 64]`, `z_dim = 32` edited into the script --
+takes one Function per nn.Linear by default, as it always did.  With the switch on it runs as ONE Function as well, on
+`GenericModuleEngine`: the generic rows kernel (csrc/train_generic.hip) in its two module modes,
+
+    forward : dvae_module_generic_forward  = packed-copy refresh + rows kernel, forward chain with the outputs written   (2 launches)
+    backward: dvae_module_generic_backward = rows kernel (forward recomputed, backward from the upstream gradients)
+              + weight-gradient kernel + reduce into one flat gradient                                               (3 launches)
+
+within `trainer_generic.covered`: M1 / M2, x 513, y 0..513, two hidden widths 1..512, z 1..128, no flow.  Any loss written in torch on
+(r, z, mu, log_var) -- a weighted or warmed-up KL term, free bits, a regulariser on z -- becomes the upstream gradients of that one
+backward.  The switch:
+    DVAE_MODULE_GENERIC unset / 0   off: every call keeps the path and the bits it had
+    DVAE_MODULE_GENERIC=1           on for the sizes the resident engine does not serve
+    DVAE_MODULE_GENERIC=force       on, and the reference geometry goes through the generic engine too (tests, A/B runs)
+    set_generic(module, mode)       the same per module (None: follow the environment); engine_kind(module, model) tells the outcome
+DVAE_MODULE_PRECISION does not apply there: the generic path is exact fp32 (the f32 MFMA), whatever it says.  The rules above hold
+unchanged: inference stays on the per-layer kernels, DVAE_MODULE_PATH=layers wins.  Not covered: the M2_info body ("M2_DEC": encoder on
+x alone) of other sizes lives in another rows kernel (csrc/train_info.hip) and stays per-layer; and whether the generic engine should be
+the default is left to the measurement in DESIGN 4b.
 """
 import ctypes
 import os
@@ -32,6 +52,7 @@ import os
 import torch
 
 from . import native as N
+from . import trainer_generic as TG
 from .trainer import MODEL_CODE, PREC_CODE, TENSOR_NAMES, TrainPlan
 
 
@@ -56,10 +77,16 @@ def vae_parameters(module, model):
 class ModuleEngine:
     """Fused kernels bound to one module instance (M1, M2, or the encoder + decoder of a _v3: M2_DEC)."""
 
+    kind = "resident"
+
     def __init__(self, module, model, y_dim):
+        self.precision = _precision()
+        self.z_dim = 16
+        self._bind(module, model, y_dim)
+
+    def _bind(self, module, model, y_dim):
         self.lib = N.load()
         self.model, self.y_dim = model, int(y_dim)
-        self.precision = _precision()
         named = vae_parameters(module, model)
         sd_names = [n for n, _ in named]
         if sd_names != TENSOR_NAMES:
@@ -184,6 +211,69 @@ def _rows_ok(t):
     return t.contiguous()
 
 
+class GenericModuleEngine(ModuleEngine):
+    """The same surface on the generic kernels (module docstring): an M1 / M2 module of any covered size, exact fp32.  The 14 parameters
+    are views of one flat buffer in the generic plan's tensor_offset layout; a plan per batch size holds its workspace (packed copies,
+    stash, slabs)."""
+    kind = "generic"
+
+    def __init__(self, module, model, dims):
+        self.precision = "fp32"
+        self.dims = dict(dims)
+        self.z_dim = int(dims["z_dim"])
+        self._bind(module, model, dims.get("y_dim", 0) if model != "M1" else 0)
+
+    def _plan(self, B):
+        got = self.plans.pop(B, None)
+        if got is None:
+            while len(self.plans) >= self.MAX_PLANS:
+                self.plans.pop(next(iter(self.plans)))
+            got = [TG.make_plan(self.model, self.dims, B), None, False]
+        self.plans[B] = got                        # most recently used last
+        return got
+
+    def _ready(self, B):
+        ent = self._plan(B)
+        if not ent[2]:
+            with torch.cuda.device(self.device):
+                ent[1] = torch.empty(ent[0].workspace_bytes, dtype=torch.uint8, device=self.device)
+                N.check(self.lib.dvae_train_generic_init(ctypes.byref(ent[0]), N.ptr(self.flat), N.ptr(ent[1]), N.stream()), "dvae_train_generic_init")
+            ent[2] = True
+        return ent[0], ent[1]
+
+    def forward(self, x, y, eps):
+        B, Z = x.shape[0], self.z_dim
+        if self.params[0].device != self.device:
+            raise RuntimeError("module moved to another device after the fused engine was built")
+        self._alias()
+        plan, ws = self._ready(B)
+        with torch.cuda.device(self.device):
+            r = torch.empty((B, 513), dtype=torch.float32, device=self.device)
+            mlz = torch.empty((3, B, Z), dtype=torch.float32, device=self.device)
+            yp, ldy = (N.ptr(y), N.ld(y)) if self.y_dim else (None, 0)
+            m0 = mlz.data_ptr()                      # mu | log_var | z, [B, z_dim] fp32 each
+            N.check(self.lib.dvae_module_generic_forward(ctypes.byref(plan), N.ptr(self.flat), N.ptr(ws), N.ptr(x), N.ld(x), yp, ldy, N.ptr(eps),
+                                                         N.ptr(r), 513, m0, m0 + 4 * B * Z, m0 + 8 * B * Z, 1, N.stream()),
+                    "dvae_module_generic_forward")
+        mu, lv, z = mlz.unbind(0)
+        return r, z, mu, lv
+
+    def backward(self, x, y, eps, gr, gz, gmu, glv, needs):
+        """-> list of 14 parameter gradients (None where `needs` is False): views of one flat buffer of this call."""
+        B = x.shape[0]
+        plan, ws = self._ready(B)
+        f32c = lambda t: None if t is None else _rows_ok(t.to(torch.float32))
+        gr_ = f32c(gr)
+        gz, gmu, glv = (None if t is None else t.to(torch.float32).contiguous() for t in (gz, gmu, glv))
+        with torch.cuda.device(self.device):
+            dst = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
+            yp, ldy = (N.ptr(y), N.ld(y)) if self.y_dim else (None, 0)
+            N.check(self.lib.dvae_module_generic_backward(ctypes.byref(plan), N.ptr(self.flat), N.ptr(ws), N.ptr(x), N.ld(x), yp, ldy, N.ptr(eps),
+                                                          N.ptr(gr_), 0 if gr_ is None else N.ld(gr_), N.ptr(gmu), N.ptr(glv), N.ptr(gz),
+                                                          N.ptr(dst), 0, N.stream()), "dvae_module_generic_backward")
+        return [dst.as_strided(shp, std, o) if need else None for (shp, std, o), need in zip(self._grad_views(), needs)]
+
+
 class VaeFunction(torch.autograd.Function):
     """(r, z, mu, log_var) = model(x, y) with reparametrisation noise eps; the parameters are inputs of the Function and
     backward returns their gradients (module docstring)."""
@@ -214,6 +304,68 @@ class VaeFunction(torch.autograd.Function):
         return (None, None, None, None, *grads)
 
 
+GENERIC_MODES = {"": "off", "0": "off", "off": "off", "1": "on", "on": "on", "force": "force"}
+
+
+def generic_mode(module=None):
+    """"off" | "on" | "force": the module's own setting (set_generic) or else DVAE_MODULE_GENERIC (module docstring)."""
+    m = module.__dict__.get("_dvae_generic") if module is not None else None
+    if m is None:
+        m = os.environ.get("DVAE_MODULE_GENERIC", "0")
+    try:
+        return GENERIC_MODES[str(m).lower()]
+    except KeyError:
+        raise ValueError(f"DVAE_MODULE_GENERIC / set_generic: {m!r} (0 / off, 1 / on, force)") from None
+
+
+def set_generic(module, mode):
+    """The switch of the generic engine for this module alone: "off" / 0, "on" / 1, "force", or None to follow DVAE_MODULE_GENERIC again.
+    Takes effect at the next forward (an engine of the other kind is rebuilt on the same parameters)."""
+    if mode is not None:
+        mode = "on" if mode is True else "off" if mode is False else str(mode).lower()
+        if mode not in GENERIC_MODES:
+            raise ValueError(f"set_generic: mode {mode!r} (0 / off, 1 / on, force, or None)")
+    object.__setattr__(module, "_dvae_generic", mode)
+
+
+def _resident_geometry(module, model):
+    return (module.z_dim == 16 and module.flow is None
+            and [tuple(l.weight.shape) for l in module.encoder.hidden] == [(128, 513 + (module.y_dim if model == "M2" else 0)), (128, 128)]
+            and [tuple(l.weight.shape) for l in module.decoder.hidden] == [(128, 16 + (module.y_dim if model != "M1" else 0)), (128, 128)]
+            and tuple(module.decoder.reconstruction.weight.shape) == (513, 128)
+            and (model == "M1" or module.y_dim in ((1, 513) if model == "M2" else (1,))))
+
+
+def generic_dims(module, model):
+    """dims of an M1 / M2 module the generic engine covers (trainer_generic.covered and every layer of the plan's shape), else None.
+    Host logic only."""
+    if model not in ("M1", "M2") or module.flow is not None:
+        return None
+    enc, dec = list(module.encoder.hidden), list(module.decoder.hidden)
+    if len(enc) != 2 or len(dec) != 2 or not all(isinstance(l, torch.nn.Linear) and l.bias is not None for l in enc + dec):
+        return None
+    y = int(module.y_dim) if model == "M2" else 0
+    z, h1, h2 = int(module.z_dim), enc[0].out_features, enc[1].out_features
+    dims = dict(x_dim=enc[0].in_features - y, y_dim=y, z_dim=z, h_dim=(h1, h2))
+    sample, rec = module.encoder.sample, module.decoder.reconstruction
+    shapes = [tuple(l.weight.shape) for l in (enc[0], enc[1], getattr(sample, "mu", rec), getattr(sample, "log_var", rec), dec[0], dec[1], rec)]
+    if not TG.covered(model, dims) or shapes != [(h1, 513 + y), (h2, h1), (z, h2), (z, h2), (h2, z + y), (h1, h2), (513, h1)]:
+        return None
+    return dims
+
+
+def engine_kind(module, model):
+    """"resident", "generic" or None: the engine a grad-mode forward of this module on CUDA float32 tensors would take as the switches
+    stand (DVAE_MODULE_PATH, DVAE_MODULE_GENERIC, set_generic).  Host logic only: nothing is built and no device is touched."""
+    if not enabled():
+        return None
+    mode = generic_mode(module)
+    dims = generic_dims(module, model) if mode != "off" else None
+    if _resident_geometry(module, model) and not (mode == "force" and dims is not None):
+        return "resident"
+    return "generic" if dims is not None else None
+
+
 def engine_for(module, model, x, y):
     """The module's engine when this call can take the fused path, else None.  model: "M1" | "M2" | "M2_DEC" (module: a _v3)."""
     if not (enabled() and x.is_cuda and x.dim() == 2 and x.shape[1] == 513 and x.dtype == torch.float32 and x.shape[0] > 0):
@@ -222,26 +374,27 @@ def engine_for(module, model, x, y):
         return None                                  # gradients with respect to the data are a layer-path feature
     if not torch.is_grad_enabled():
         return None                                  # inference: the exact-fp32 per-layer kernels (module docstring)
+    mode = generic_mode(module)
     eng = module.__dict__.get("_dvae_engine")
-    if eng is not None and not eng.current():
-        eng = None                                   # a parameter object was replaced: a new engine on the new set
+    if eng is not None and not (eng.current() and eng.mode == mode):
+        eng = None                                   # a parameter object was replaced, or the switch moved: a new engine on the set
         module.__dict__.pop("_dvae_engine", None)
     if not any(p.requires_grad for p in (eng.params if eng is not None else [p for _, p in vae_parameters(module, model)])):
         return None                                  # every parameter frozen: inference as well
     if eng is None:
-        if module.__dict__.get("_dvae_engine_off"):
+        if module.__dict__.get("_dvae_engine_off") == mode:
             return None
-        ok = (module.z_dim == 16 and module.flow is None
-              and [tuple(l.weight.shape) for l in module.encoder.hidden] == [(128, 513 + (module.y_dim if model == "M2" else 0)), (128, 128)]
-              and [tuple(l.weight.shape) for l in module.decoder.hidden] == [(128, 16 + (module.y_dim if model != "M1" else 0)), (128, 128)]
-              and tuple(module.decoder.reconstruction.weight.shape) == (513, 128)
-              and (model == "M1" or module.y_dim in ((1, 513) if model == "M2" else (1,)))
-              and all(p.is_cuda and p.dtype == torch.float32 for _, p in vae_parameters(module, model))
+        kind = engine_kind(module, model)
+        ok = (kind is not None and all(p.is_cuda and p.dtype == torch.float32 for _, p in vae_parameters(module, model))
               and [n for n, _ in vae_parameters(module, model)] == TENSOR_NAMES)
         if not ok:
-            object.__setattr__(module, "_dvae_engine_off", True)
+            object.__setattr__(module, "_dvae_engine_off", mode)
             return None
-        eng = ModuleEngine(module, model, module.y_dim if model != "M1" else 0)
+        if kind == "generic":
+            eng = GenericModuleEngine(module, model, generic_dims(module, model))
+        else:
+            eng = ModuleEngine(module, model, module.y_dim if model != "M1" else 0)
+        eng.mode = mode
         object.__setattr__(module, "_dvae_engine", eng)
     if not eng.usable(x):
         return None
@@ -251,11 +404,11 @@ def engine_for(module, model, x, y):
 
 
 def run(eng, x, y, eps):
-    """-> (r, z, mu, log_var).  eps: [B, 16] float32 on x's device."""
+    """-> (r, z, mu, log_var).  eps: [B, z_dim] float32 on x's device (z_dim 16 on the resident engine)."""
     x = _rows_ok(x)
     if y is not None:
         y = _rows_ok(y)
     eps = eps.to(device=x.device, dtype=torch.float32).contiguous()
-    if eps.shape != (x.shape[0], 16):
-        raise RuntimeError(f"reparametrisation noise must be [{x.shape[0]}, 16], got {tuple(eps.shape)}")
+    if eps.shape != (x.shape[0], eng.z_dim):
+        raise RuntimeError(f"reparametrisation noise must be [{x.shape[0]}, {eng.z_dim}], got {tuple(eps.shape)}")
     return VaeFunction.apply(eng, x, y, eps, *eng.params)

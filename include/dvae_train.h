@@ -284,6 +284,27 @@ int dvae_train_generic_apply_flat_clipped(const dvae_train_generic_plan_t* plan,
                                           int step, double lr, double beta1, double beta2, double adam_eps, double grad_scale, double max_norm,
                                           void* scratch, float* norm2_out, int32_t* skipped_counter, void* stream);
 
+/* Whole-model autograd path of the drop-in modules at ANY covered size (disentangled-vae_amd/module_path.py: GenericModuleEngine):
+ * dvae_module_forward / dvae_module_backward above on a dvae_train_generic_plan_t (M1 / M2, exact fp32), `ws` set up by
+ * dvae_train_generic_init.  Two further modes of the generic rows kernel; the weight-gradient and reduce kernels are the train step's.
+ *   _forward : (repack != 0: both packed weight copies rewritten from `params` first, one launch) then ONE launch: r = model(x, y)
+ *              [B, 513] (ld_r >= 513), mu, log_var, z [B, z_dim] (out_z may be NULL); eps_noise [B, z_dim].  Padding between the rows of
+ *              out_r is not written.  No stash, no loss sums.
+ *   _backward: three launches -- the rows kernel recomputes the forward and runs the backward chain from the upstream gradients g_r
+ *              [B, 513] (ld_gr >= 513), g_mu, g_lv, g_z [B, z_dim], each NULL = zero: da = g_r r; dz = dpre_d1 D1[:, :z] + g_z;
+ *              d mu = dz + g_mu; d log_var = dz std eps / 2 + g_lv (no 1 / B, no KL term: the upstream gradients carry both); the
+ *              weight-gradient kernel; the reduce kernel into grad_flat[n_params] (plan layout, 16-byte aligned): accumulate 0
+ *              overwrites every element, accumulate 1 adds with one float32 addition per element; the alignment gaps between the
+ *              tensors receive zeros in either mode, as from dvae_train_generic_reduce.
+ * The same inputs give the same bits.  DVAE_E_BADARG by name, before anything is launched: ld_r / ld_gr below 513, ldx below 513 or ldy
+ * below y_dim (rows that overlap), a std_norm plan (normalise in torch and pass x_norm), a plan with a gather table, a null pointer. */
+int dvae_module_generic_forward(const dvae_train_generic_plan_t* plan, const float* params, void* ws, const float* x, int64_t ldx,
+                                const float* y, int64_t ldy, const float* eps_noise, float* out_r, int64_t ld_r, float* out_mu,
+                                float* out_lv, float* out_z, int repack, void* stream);
+int dvae_module_generic_backward(const dvae_train_generic_plan_t* plan, const float* params, void* ws, const float* x, int64_t ldx,
+                                 const float* y, int64_t ldy, const float* eps_noise, const float* g_r, int64_t ld_gr,
+                                 const float* g_mu, const float* g_lv, const float* g_z, float* grad_flat, int accumulate, void* stream);
+
 /* ---- the fused train step for the label classifier alone (csrc/train_classifier.hip): Classifier([513, [h1, h2], y_dim]) of
  * packages/models/models.py -- relu, relu, sigmoid -- under binary_cross_entropy (packages/models/utils.py:55-56) and Adam: the loop body
  * the reference sketches in scripts/train_audio_net.py, and the net it otherwise trains only as a side net of M2_info
