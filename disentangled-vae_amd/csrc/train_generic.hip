@@ -27,6 +27,10 @@
 //   * module modes of the rows kernel (dvae_module_generic_forward / _backward; module_path.py: GenericModuleEngine): the forward chain
 //     with the model's outputs written, and the backward chain started from upstream gradients of (r, z, mu, log_var) in the place of
 //     the ELBO's -- the drop-in modules' forward as ONE autograd Function under the caller's own loss and optimizer.
+//   * the M2_info body in the module modes (DEC; plans of dvae_module_generic_plan, model M2_DEC): encoder layer 1 on x alone -- W1y
+//     has no elements --, the label tile for decoder layer 1 only, and in the backward mode the label gradient g_y = dpre_d1 D1[:, z:]
+//     beside dz, from one more transposed copy D1yT behind the last packed copy (dvae_module_generic_backward_y).  The weight-gradient,
+//     reduce and apply kernels are the same code on this plan's tables.
 //   * 64-bit indexing throughout; a gather index outside [0, row_count) is never dereferenced (row 0 instead, counted).
 #include <math.h>
 #include <vector>
@@ -46,16 +50,16 @@ static bool dims_ok(int y, int z, int h1, int h2) {
     return y >= 0 && y <= GX && h1 >= 1 && h1 <= G_HMAX && h2 >= 1 && h2 <= G_HMAX && z >= 1 && z <= G_ZMAX;
 }
 
-static GLayout make_layout(int y, int z, int h1, int h2, int64_t B, int ksplit_hint, bool norm) {
+static GLayout make_layout(int y, int z, int h1, int h2, int64_t B, int ksplit_hint, bool norm, bool dec = false) {
     GLayout L;
     memset(&L, 0, sizeof(L));
-    L.y = y; L.z = z; L.h1 = h1; L.h2 = h2;
+    L.y = y; L.z = z; L.h1 = h1; L.h2 = h2; L.dec = dec ? 1 : 0;
     L.yp = y ? up16(y) : 0; L.zp = up16(z); L.h1p = up16(h1); L.h2p = up16(h2);
     L.hm = L.h1p > L.h2p ? L.h1p : L.h2p;
     if (L.zp > L.hm) L.hm = L.zp;
     // parameters: state_dict order, 256-byte aligned
     const int rows[M_NT] = {h1, h1, h2, h2, z, z, z, z, h2, h2, h1, h1, GX, GX};
-    const int cols[M_NT] = {GX + y, 1, h1, 1, h2, 1, h2, 1, z + y, 1, h2, 1, h1, 1};
+    const int cols[M_NT] = {GX + (dec ? 0 : y), 1, h1, 1, h2, 1, h2, 1, z + y, 1, h2, 1, h1, 1};
     int64_t o = 0;
     for (int t = 0; t < M_NT; ++t) {
         L.toff[t] = o; L.trows[t] = rows[t]; L.tcols[t] = cols[t];
@@ -65,13 +69,14 @@ static GLayout make_layout(int y, int z, int h1, int h2, int64_t B, int ksplit_h
     // packed copies
     o = 0;
     auto take = [&](int64_t n) { const int64_t at = o; o = al64(o + n); return at; };
-    L.W1x = take((int64_t)L.h1p * GXP); L.W1y = take((int64_t)L.h1p * L.yp);
+    L.W1x = take((int64_t)L.h1p * GXP); L.W1y = take(dec ? 0 : (int64_t)L.h1p * L.yp);
     L.W2 = take((int64_t)L.h2p * L.h1p); L.Wh = take((int64_t)2 * L.zp * L.h2p);
     L.D1z = take((int64_t)L.h2p * L.zp); L.D1y = take((int64_t)L.h2p * L.yp);
     L.D2 = take((int64_t)L.h1p * L.h2p); L.D3 = take((int64_t)GXP * L.h1p);
     L.D3T = take((int64_t)L.h1p * GXP); L.D2T = take((int64_t)L.h2p * L.h1p); L.D1zT = take((int64_t)L.zp * L.h2p);
     L.WhT = take((int64_t)L.h2p * 2 * L.zp); L.W2T = take((int64_t)L.h1p * L.h2p);
     L.b1 = take(L.h1p); L.b2 = take(L.h2p); L.bh = take(2 * L.zp); L.bd1 = take(L.h2p); L.bd2 = take(L.h1p); L.bd3 = take(GXP);
+    if (dec) take((int64_t)L.yp * L.h2p);                  // D1yT, behind the last packed copy: d1yT_off
     L.wpack_elems = o;
     // the stash of a frame
     int s = 0;
@@ -103,6 +108,10 @@ static GLayout make_layout(int y, int z, int h1, int h2, int64_t B, int ksplit_h
     return L;
 }
 
+// DEC: the transposed copy of decoder layer 1's label columns ([yp][h2p], fragment order as D1zT) starts where the packed copies of a
+// plan without it end
+static int64_t d1yT_off(const GLayout& L) { return al64(L.bd3 + GXP); }
+
 static void make_tensors(const GLayout& L, GTensor* T) {
     for (int t = 0; t < G_NT; ++t) {
         GTensor& d = T[t];
@@ -125,6 +134,10 @@ static void make_tensors(const GLayout& L, GTensor* T) {
     T[11].f0 = L.bd2;
     T[12].f0 = L.D3; T[12].kb0 = k1; T[12].t0 = L.D3T; T[12].tkb = GKX; T[12].tcmax = L.h1;
     T[13].f0 = L.bd3;
+    if (L.dec) {                                          // W1y is empty: every column of tensor 0 is x; the label columns of tensor 8 also go to D1yT
+        T[0].kb1 = 0;
+        T[8].t1 = d1yT_off(L); T[8].tkb1 = k2;
+    }
 }
 
 static void make_gemms(const GLayout& L, GGemm* G) {
@@ -134,8 +147,9 @@ static void make_gemms(const GLayout& L, GGemm* G) {
         m.dpre = dpre; m.nrt = nrt; m.rows = rows; m.wt = wt; m.bt = wt + 1; m.in_kind = kind; m.in_off = in_off; m.in_w = in_w; m.y_w = y_w;
         m.cols = in_w + y_w;
     };
-    if (L.norm) set(0, L.s_pe1, L.h1p / 16, L.h1, 0, 1, L.s_xn, GX, L.y);      // the standardised x from the stash, labels behind it as in decoder layer 1
-    else set(0, L.s_pe1, L.h1p / 16, L.h1, 0, 0, 0, GX, L.y);
+    const int y0 = L.dec ? 0 : L.y;                       // DEC: the encoder does not see the labels
+    if (L.norm) set(0, L.s_pe1, L.h1p / 16, L.h1, 0, 1, L.s_xn, GX, y0);       // the standardised x from the stash, labels behind it as in decoder layer 1
+    else set(0, L.s_pe1, L.h1p / 16, L.h1, 0, 0, 0, GX, y0);
     set(1, L.s_pe2, L.h2p / 16, L.h2, 2, 1, L.s_h1e, L.h1, 0);
     set(2, L.s_ph, L.zp / 16, L.z, 4, 1, L.s_h2e, L.h2, 0);
     set(3, L.s_ph + L.zp, L.zp / 16, L.z, 6, 1, L.s_h2e, L.h2, 0);
@@ -159,7 +173,10 @@ struct GRowsArgs {
 };
 // the module modes (dvae_module_generic_forward / _backward): the model's outputs, or the upstream gradients of them (each may be null)
 struct GModuleArgs {
-    float* out_r; int64_t ld_r;       // [B][513]
+    // what the kernel writes row by row: forward r [B][513]; backward (DEC) the label gradient [B][y], null: not asked for.  One mode
+    // writes one of them, so they share their place and the arguments of the instantiations without DEC stay where they were
+    union { float* out_r; float* out_gy; };
+    union { int64_t ld_r; int64_t ld_gy; };
     float* out_mu; float* out_lv; float* out_z;       // [B][z]; out_z may be null
     const float* g_r; int64_t ld_gr;  // [B][513]
     const float* g_mu; const float* g_lv; const float* g_z;       // [B][z]
@@ -179,9 +196,15 @@ struct __attribute__((packed, aligned(4))) G4U { f32x4 v; };      // 16 bytes at
 //                    g_lv.  No 1 / B and no KL term: the upstream gradients carry both.  A null pointer is a zero gradient; a frame past
 //                    B, a padded bin and a padded latent column contribute exact zeros.  The weight-gradient and reduce kernels read
 //                    the stash this leaves as they read a train step's.
-template <bool NORM, int MODE = ROWS_STEP>
+// DEC (the module modes on an M2_DEC plan): encoder layer 1 is the x product alone; the label tile is staged as ever and read by decoder
+//   layer 1.  In the backward mode the dz phase has ky more row tiles behind its kz: g_y = dpre_d1 D1[:, z:] on D1yT, a lane's four
+//   consecutive label columns of its frame stored straight from the accumulator -- no LDS, no further barrier.  The encoder gives g_y
+//   nothing, and there is no 1 / B.  A frame past B, a column >= y and the padding of a row are never written; out_gy null: the tiles
+//   are not computed.
+template <bool NORM, int MODE = ROWS_STEP, bool DEC = false>
 __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L, const GRowsArgs g, const GModuleArgs mo) {
     static_assert(MODE == ROWS_STEP || !NORM, "the module modes take the encoder input as it is given");
+    static_assert(!DEC || MODE != ROWS_STEP, "there is no train step on an M2_DEC plan");
     extern __shared__ __attribute__((aligned(16))) float gsm[];
     float* X = gsm;                                     // [528][16] x, then d loss / d a
     float* Y = X + GT * GXP;                            // [yp][16]
@@ -250,7 +273,7 @@ __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L
         for (int t = wave; t < k1; t += 4) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
             acc = tg_gemm(acc, wp + L.W1x + (int64_t)t * GKX * 256, GKX, X, lane);
-            acc = tg_gemm(acc, wp + L.W1y + (int64_t)t * ky * 256, ky, Y, lane);
+            if constexpr (!DEC) acc = tg_gemm(acc, wp + L.W1y + (int64_t)t * ky * 256, ky, Y, lane);
             f32x4 h;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -425,8 +448,26 @@ __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L
         }
         __syncthreads();
         // ---- dz = dpre_d1 D1[:, :z]; d mu = dz + mu / B; d log_var = dz eps std / 2 + its KL part -> C rows 0 .. 2 zp - 1 ----
-        for (int t = wave; t < kz; t += 4) {
+        const int ndz = (DEC && MODE == ROWS_MODULE_BWD && mo.out_gy) ? kz + ky : kz;
+        const int64_t D1yT = (L.bd3 + GXP + 63) / 64 * 64;       // d1yT_off(L): behind the last packed copy
+        for (int t = wave; t < ndz; t += 4) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (DEC && MODE == ROWS_MODULE_BWD) {
+                if (t >= kz) {                          // g_y = dpre_d1 D1[:, z:]: label columns 16 (t - kz) + 4 quad .. + 3 of this lane's frame
+                    const int c0 = 16 * (t - kz) + 4 * quad;
+                    acc = tg_gemm(acc, wp + D1yT + (int64_t)(t - kz) * k2 * 256, k2, A, lane);
+                    if (fok) {
+                        float* gp = mo.out_gy + (r0 + col) * mo.ld_gy + c0;
+                        if (c0 + 3 < L.y) reinterpret_cast<G4U*>(gp)->v = acc;
+                        else {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                if (c0 + r < L.y) gp[r] = acc[r];
+                        }
+                    }
+                    continue;
+                }
+            }
             float gz[4] = {0.f, 0.f, 0.f, 0.f};
             if constexpr (MODE == ROWS_MODULE_BWD) {   // the upstream gradient of z: four consecutive columns of this lane's frame
                 if (fok && mo.g_z) {
@@ -856,13 +897,19 @@ int raise_lds_limit(const void* kernel, const char* name, int64_t lds_bytes, boo
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // host
-static int plan_layout(const char* who, const dvae_train_generic_plan_t* plan, GLayout& L) {
+// dec_ok: the entry point serves the M2_DEC plans of dvae_module_generic_plan too (init, repack, the module modes); the train-step entry
+// points do not
+static int plan_layout(const char* who, const dvae_train_generic_plan_t* plan, GLayout& L, bool dec_ok = false) {
     DVAE_CHECK_ARG(plan, "%s: null plan", who);
-    DVAE_CHECK_ARG((plan->model == DVAE_MODEL_M1 || plan->model == DVAE_MODEL_M2) && plan->precision == DVAE_PREC_F32 &&
+    const bool dec = plan->model == DVAE_MODEL_M2_DEC;
+    DVAE_CHECK_ARG(!dec || dec_ok, "%s: a plan of model M2_DEC (dvae_module_generic_plan: the module entry points serve it; there is no train step "
+                   "on the M2_info body alone -- dvae_train_info_* trains the whole model)", who);
+    DVAE_CHECK_ARG((plan->model == DVAE_MODEL_M1 || plan->model == DVAE_MODEL_M2 || dec) && plan->precision == DVAE_PREC_F32 &&
                    dims_ok(plan->y_dim, plan->z_dim, plan->h1, plan->h2) && (plan->model == DVAE_MODEL_M1) == (plan->y_dim == 0) && plan->B >= 1,
-                   "%s: not a plan of dvae_train_generic_plan", who);
+                   "%s: not a plan of dvae_train_generic_plan / dvae_module_generic_plan", who);
     DVAE_CHECK_ARG(plan->std_norm == 0 || plan->std_norm == 1, "%s: std_norm %d in the plan (0 or 1)", who, plan->std_norm);
-    L = make_layout(plan->y_dim, plan->z_dim, plan->h1, plan->h2, plan->B, plan->ksplit, plan->std_norm != 0);
+    DVAE_CHECK_ARG(!dec || !plan->std_norm, "%s: std_norm on a plan of model M2_DEC", who);
+    L = make_layout(plan->y_dim, plan->z_dim, plan->h1, plan->h2, plan->B, plan->ksplit, plan->std_norm != 0, dec);
     DVAE_CHECK_ARG(L.ws_bytes == plan->workspace_bytes && L.nslices == plan->ksplit && L.n_params == plan->n_params &&
                    L.slice_frames == plan->slice_frames, "%s: the plan was changed after dvae_train_generic_plan", who);
     return 0;
@@ -912,11 +959,16 @@ static int launch_apply(const GLayout& L, const ApplyArgs& a, char* ws, bool ada
 
 static int launch_rows(const dvae_train_generic_plan_t* plan, const GLayout& L, char* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
                        const float* eps, float elbo_eps, bool fwd_only, hipStream_t s, int mode = ROWS_STEP, const GModuleArgs* module = nullptr) {
-    static bool attr_done[4][64] = {};
-    const void* kernel = mode == ROWS_MODULE_FWD ? (const void*)train_generic_rows_kernel<false, ROWS_MODULE_FWD>
-                       : mode == ROWS_MODULE_BWD ? (const void*)train_generic_rows_kernel<false, ROWS_MODULE_BWD>
+    static bool attr_done[6][64] = {};
+    const bool dec = L.dec != 0;
+    DVAE_CHECK_ARG(!dec || mode != ROWS_STEP, "train_generic_rows_kernel: no train step on a plan of model M2_DEC");
+    const void* kernel = mode == ROWS_MODULE_FWD ? (dec ? (const void*)train_generic_rows_kernel<false, ROWS_MODULE_FWD, true>
+                                                       : (const void*)train_generic_rows_kernel<false, ROWS_MODULE_FWD>)
+                       : mode == ROWS_MODULE_BWD ? (dec ? (const void*)train_generic_rows_kernel<false, ROWS_MODULE_BWD, true>
+                                                       : (const void*)train_generic_rows_kernel<false, ROWS_MODULE_BWD>)
                        : L.norm ? (const void*)train_generic_rows_kernel<true> : (const void*)train_generic_rows_kernel<false>;
-    if (int rc = raise_lds_limit(kernel, "train_generic_rows_kernel", L.lds_bytes, attr_done[mode == ROWS_STEP ? L.norm : 1 + mode])) return rc;
+    if (int rc = raise_lds_limit(kernel, "train_generic_rows_kernel", L.lds_bytes,
+                                 attr_done[mode == ROWS_STEP ? L.norm : (dec ? 3 : 1) + mode])) return rc;
     GModuleArgs mo;
     memset(&mo, 0, sizeof(mo));
     if (module) mo = *module;
@@ -927,7 +979,11 @@ static int launch_rows(const dvae_train_generic_plan_t* plan, const GLayout& L, 
     g.ws = (float*)ws; g.stash = (float*)(ws + L.o_stash); g.partials = (double*)(ws + L.o_partials);
     g.elbo_eps = elbo_eps; g.invB = (float)(1.0 / (double)L.B); g.fwd_only = fwd_only ? 1 : 0;
     const dim3 grid((unsigned)L.rows_grid), block(256);
-    if (mode == ROWS_MODULE_FWD) {
+    if (mode == ROWS_MODULE_FWD && dec) {
+        hipLaunchKernelGGL((train_generic_rows_kernel<false, ROWS_MODULE_FWD, true>), grid, block, (size_t)L.lds_bytes, s, L, g, mo);
+    } else if (mode == ROWS_MODULE_BWD && dec) {
+        hipLaunchKernelGGL((train_generic_rows_kernel<false, ROWS_MODULE_BWD, true>), grid, block, (size_t)L.lds_bytes, s, L, g, mo);
+    } else if (mode == ROWS_MODULE_FWD) {
         hipLaunchKernelGGL((train_generic_rows_kernel<false, ROWS_MODULE_FWD>), grid, block, (size_t)L.lds_bytes, s, L, g, mo);
     } else if (mode == ROWS_MODULE_BWD) {
         hipLaunchKernelGGL((train_generic_rows_kernel<false, ROWS_MODULE_BWD>), grid, block, (size_t)L.lds_bytes, s, L, g, mo);
@@ -960,6 +1016,16 @@ static int launch_wgrad(const dvae_train_generic_plan_t* plan, const GLayout& L,
 using namespace dvae;
 using namespace dvae::tg;
 
+static void fill_plan(dvae_train_generic_plan_t* plan, const GLayout& L, int model, int precision, int std_norm) {
+    memset(plan, 0, sizeof(*plan));
+    plan->std_norm = std_norm;
+    plan->model = model; plan->y_dim = L.y; plan->z_dim = L.z; plan->h1 = L.h1; plan->h2 = L.h2; plan->precision = precision;
+    plan->ksplit = L.nslices; plan->n_tensors = M_NT; plan->B = L.B; plan->n_params = L.n_params;
+    for (int t = 0; t < M_NT; ++t) { plan->tensor_offset[t] = L.toff[t]; plan->tensor_rows[t] = L.trows[t]; plan->tensor_cols[t] = L.tcols[t]; }
+    plan->workspace_bytes = L.ws_bytes; plan->grad_offset_bytes = L.o_grads; plan->Bp = L.Bp; plan->rows_grid = L.rows_grid;
+    plan->slice_frames = L.slice_frames; plan->wgrad_items = L.n_items; plan->lds_bytes = L.lds_bytes;
+}
+
 extern "C" int dvae_train_generic_plan(int model, int y_dim, int z_dim, int h1, int h2, int precision, int64_t B, int ksplit_hint,
                                        dvae_train_generic_plan_t* plan) {
     return dvae_train_generic_plan_norm(model, y_dim, z_dim, h1, h2, precision, B, ksplit_hint, 0, plan);
@@ -983,19 +1049,13 @@ extern "C" int dvae_train_generic_plan_norm(int model, int y_dim, int z_dim, int
     DVAE_CHECK_ARG(B >= 1 && B < ((int64_t)1 << 31), "train_generic_plan: %lld frames", (long long)B);
     DVAE_CHECK_ARG(ksplit_hint >= 0 && ksplit_hint <= G_MAX_SLICES, "train_generic_plan: %d frame slices (0 = choose, at most %d)", ksplit_hint, G_MAX_SLICES);
     const GLayout L = make_layout(y_dim, z_dim, h1, h2, B, ksplit_hint, std_norm != 0);
-    memset(plan, 0, sizeof(*plan));
-    plan->std_norm = std_norm;
-    plan->model = model; plan->y_dim = y_dim; plan->z_dim = z_dim; plan->h1 = h1; plan->h2 = h2; plan->precision = precision;
-    plan->ksplit = L.nslices; plan->n_tensors = M_NT; plan->B = B; plan->n_params = L.n_params;
-    for (int t = 0; t < M_NT; ++t) { plan->tensor_offset[t] = L.toff[t]; plan->tensor_rows[t] = L.trows[t]; plan->tensor_cols[t] = L.tcols[t]; }
-    plan->workspace_bytes = L.ws_bytes; plan->grad_offset_bytes = L.o_grads; plan->Bp = L.Bp; plan->rows_grid = L.rows_grid;
-    plan->slice_frames = L.slice_frames; plan->wgrad_items = L.n_items; plan->lds_bytes = L.lds_bytes;
+    fill_plan(plan, L, model, precision, std_norm);
     return 0;
 }
 
 extern "C" int dvae_train_generic_repack(const dvae_train_generic_plan_t* plan, const float* params, void* ws, void* stream) {
     GLayout L;
-    if (int rc = plan_layout("train_generic_repack", plan, L)) return rc;
+    if (int rc = plan_layout("train_generic_repack", plan, L, true)) return rc;
     DVAE_CHECK_ARG(params && ws, "train_generic_repack: null pointer");
     hipStream_t s = (hipStream_t)stream;
     DVAE_HIP(hipMemsetAsync(ws, 0, (size_t)L.wpack_elems * 4, s));          // the padding of the packed copies
@@ -1005,7 +1065,7 @@ extern "C" int dvae_train_generic_repack(const dvae_train_generic_plan_t* plan, 
 
 extern "C" int dvae_train_generic_init(const dvae_train_generic_plan_t* plan, const float* params, void* ws, void* stream) {
     GLayout L;
-    if (int rc = plan_layout("train_generic_init", plan, L)) return rc;
+    if (int rc = plan_layout("train_generic_init", plan, L, true)) return rc;
     DVAE_CHECK_ARG(params && ws, "train_generic_init: null pointer");
     hipStream_t s = (hipStream_t)stream;
     GGemm gm[M_NG];
@@ -1121,7 +1181,7 @@ extern "C" int dvae_module_generic_forward(const dvae_train_generic_plan_t* plan
                                            const float* y, int64_t ldy, const float* eps_noise, float* out_r, int64_t ld_r, float* out_mu,
                                            float* out_lv, float* out_z, int repack, void* stream) {
     GLayout L;
-    if (int rc = plan_layout("module_generic_forward", plan, L)) return rc;
+    if (int rc = plan_layout("module_generic_forward", plan, L, true)) return rc;
     if (int rc = check_module("module_generic_forward", plan, params, ws, x, ldx, y, ldy, eps_noise)) return rc;
     DVAE_CHECK_ARG(out_r && out_mu && out_lv, "module_generic_forward: null pointer (out_z alone may be null)");
     DVAE_CHECK_ARG(ld_r >= GX && ld_r < ((int64_t)1 << 20), "module_generic_forward: ld_r %lld (the leading dimension of out_r: at least 513)", (long long)ld_r);
@@ -1136,20 +1196,24 @@ extern "C" int dvae_module_generic_forward(const dvae_train_generic_plan_t* plan
     return launch_rows(plan, L, (char*)ws, x, ldx, y, ldy, eps_noise, 0.f, true, s, ROWS_MODULE_FWD, &mo);
 }
 
-extern "C" int dvae_module_generic_backward(const dvae_train_generic_plan_t* plan, const float* params, void* ws, const float* x, int64_t ldx,
-                                            const float* y, int64_t ldy, const float* eps_noise, const float* g_r, int64_t ld_gr,
-                                            const float* g_mu, const float* g_lv, const float* g_z, float* grad_flat, int accumulate,
-                                            void* stream) {
+static int module_backward(const char* who, const dvae_train_generic_plan_t* plan, const float* params, void* ws, const float* x, int64_t ldx,
+                           const float* y, int64_t ldy, const float* eps_noise, const float* g_r, int64_t ld_gr, const float* g_mu,
+                           const float* g_lv, const float* g_z, float* grad_flat, int accumulate, float* g_y, int64_t ld_gy, void* stream) {
     GLayout L;
-    if (int rc = plan_layout("module_generic_backward", plan, L)) return rc;
-    if (int rc = check_module("module_generic_backward", plan, params, ws, x, ldx, y, ldy, eps_noise)) return rc;
-    if (int rc = check_reduce_args("module_generic_backward", ws, grad_flat, accumulate, 1.f)) return rc;
-    DVAE_CHECK_ARG(!g_r || (ld_gr >= GX && ld_gr < ((int64_t)1 << 20)), "module_generic_backward: ld_gr %lld (the leading dimension of g_r: at least 513)",
+    if (int rc = plan_layout(who, plan, L, true)) return rc;
+    if (int rc = check_module(who, plan, params, ws, x, ldx, y, ldy, eps_noise)) return rc;
+    if (int rc = check_reduce_args(who, ws, grad_flat, accumulate, 1.f)) return rc;
+    DVAE_CHECK_ARG(!g_r || (ld_gr >= GX && ld_gr < ((int64_t)1 << 20)), "%s: ld_gr %lld (the leading dimension of g_r: at least 513)", who,
                    (long long)ld_gr);
+    DVAE_CHECK_ARG(!g_y || L.dec, "%s: g_y on a plan of model %d (the label gradient exists for model M2_DEC alone: dvae_module_generic_plan)", who,
+                   plan->model);
+    DVAE_CHECK_ARG(!g_y || (ld_gy >= L.y && ld_gy < ((int64_t)1 << 20)), "%s: ld_gy %lld (the leading dimension of g_y: at least y_dim %d)", who,
+                   (long long)ld_gy, L.y);
     hipStream_t s = (hipStream_t)stream;
     GModuleArgs mo;
     memset(&mo, 0, sizeof(mo));
     mo.g_r = g_r; mo.ld_gr = ld_gr; mo.g_mu = g_mu; mo.g_lv = g_lv; mo.g_z = g_z;
+    mo.out_gy = g_y; mo.ld_gy = ld_gy;
     if (int rc = launch_rows(plan, L, (char*)ws, x, ldx, y, ldy, eps_noise, 0.f, false, s, ROWS_MODULE_BWD, &mo)) return rc;
     if (int rc = launch_wgrad(plan, L, (char*)ws, x, ldx, y, ldy, s)) return rc;
     GReduceArgs g;                                      // the slabs in slab order into grad_flat; weight 1: the sum's bits; nothing to finalise
@@ -1160,4 +1224,40 @@ extern "C" int dvae_module_generic_backward(const dvae_train_generic_plan_t* pla
     g.f.ws = (float*)ws; g.f.finalize = 0;
     g.flat = grad_flat; g.accumulate = accumulate; g.weight = 1.f;
     return launch_reduce_table(g, s);
+}
+
+extern "C" int dvae_module_generic_backward(const dvae_train_generic_plan_t* plan, const float* params, void* ws, const float* x, int64_t ldx,
+                                            const float* y, int64_t ldy, const float* eps_noise, const float* g_r, int64_t ld_gr,
+                                            const float* g_mu, const float* g_lv, const float* g_z, float* grad_flat, int accumulate,
+                                            void* stream) {
+    return module_backward("module_generic_backward", plan, params, ws, x, ldx, y, ldy, eps_noise, g_r, ld_gr, g_mu, g_lv, g_z, grad_flat, accumulate,
+                           nullptr, 0, stream);
+}
+
+extern "C" int dvae_module_generic_backward_y(const dvae_train_generic_plan_t* plan, const float* params, void* ws, const float* x, int64_t ldx,
+                                              const float* y, int64_t ldy, const float* eps_noise, const float* g_r, int64_t ld_gr,
+                                              const float* g_mu, const float* g_lv, const float* g_z, float* grad_flat, int accumulate,
+                                              float* g_y, int64_t ld_gy, void* stream) {
+    return module_backward("module_generic_backward_y", plan, params, ws, x, ldx, y, ldy, eps_noise, g_r, ld_gr, g_mu, g_lv, g_z, grad_flat,
+                           accumulate, g_y, ld_gy, stream);
+}
+
+// Host only.  M1 / M2: dvae_train_generic_plan's plan byte for byte.  M2_DEC: the M2_info body -- tensor 0 [h1, 513], tensor 8 [h2, z + y].
+extern "C" int dvae_module_generic_plan(int model, int y_dim, int z_dim, int h1, int h2, int64_t B, int ksplit_hint,
+                                        dvae_train_generic_plan_t* plan) {
+    if (model == DVAE_MODEL_M1 || model == DVAE_MODEL_M2) return dvae_train_generic_plan(model, y_dim, z_dim, h1, h2, DVAE_PREC_F32, B, ksplit_hint, plan);
+    DVAE_CHECK_ARG(plan, "module_generic_plan: null plan");
+    const char* limits = "the generic module engine covers M1 (y_dim 0), M2 and M2_DEC (the M2_info body: encoder on x alone; y_dim 1..513) at x 513, "
+                         "hidden widths 1..512, z_dim 1..128, exact fp32";
+    if (model != DVAE_MODEL_M2_DEC) {
+        set_error("module_generic_plan: model %d (M2_info as a whole has its own train step, dvae_train_info_plan; its body is model M2_DEC); %s", model, limits);
+        return DVAE_E_UNSUPPORTED;
+    }
+    DVAE_CHECK_ARG(dims_ok(y_dim, z_dim, h1, h2) && y_dim >= 1, "module_generic_plan: model M2_DEC with y_dim %d, hidden %d / %d, z_dim %d; %s", y_dim, h1,
+                   h2, z_dim, limits);
+    DVAE_CHECK_ARG(B >= 1 && B < ((int64_t)1 << 31), "module_generic_plan: %lld frames", (long long)B);
+    DVAE_CHECK_ARG(ksplit_hint >= 0 && ksplit_hint <= G_MAX_SLICES, "module_generic_plan: %d frame slices (0 = choose, at most %d)", ksplit_hint, G_MAX_SLICES);
+    const GLayout L = make_layout(y_dim, z_dim, h1, h2, B, ksplit_hint, false, true);
+    fill_plan(plan, L, model, DVAE_PREC_F32, 0);
+    return 0;
 }

@@ -4,6 +4,7 @@
 // launches of those two kernels, which live in train_generic.hip and serve all three steps.  Below them: the plain structs of the
 // M1 / M2 step alone.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include <vector>
 #include "common.hpp"
@@ -195,6 +196,7 @@ constexpr int64_t G_LDS_MAX = 160 * 1024;
 // the M1 / M2 step
 struct GLayout {
     int y, z, h1, h2, yp, zp, h1p, h2p, hm;     // sizes and their multiples of 16 (yp 0 without labels); hm = max(h1p, h2p, zp)
+    int dec;                                    // M2_DEC (dvae_module_generic_plan): the encoder reads x alone.  In the four bytes that padded hm: no other field moves
     // packed copies, float offsets from the start of the workspace: forward [out tile][k block], x / z block and label block apart;
     // the heads are one matrix (mu rows 0 .. z - 1, log_var rows zp .. zp + z - 1)
     int64_t W1x, W1y, W2, Wh, D1z, D1y, D2, D3;
@@ -214,6 +216,8 @@ struct GLayout {
     // every other column, S and the workspace of a plan without std_norm are what they are without these two fields
     int norm, s_xn;
 };
+
+static_assert(offsetof(GLayout, W1x) == 40 && offsetof(GLayout, dec) == 36, "dec sits in the padding behind hm: the kernel arguments of the train step do not move");
 
 }  // namespace tg
 }  // namespace dvae

@@ -42,9 +42,21 @@ backward.  The switch:
     DVAE_MODULE_GENERIC=force       on, and the reference geometry goes through the generic engine too (tests, A/B runs)
     set_generic(module, mode)       the same per module (None: follow the environment); engine_kind(module, model) tells the outcome
 DVAE_MODULE_PRECISION does not apply there: the generic path is exact fp32 (the f32 MFMA), whatever it says.  The rules above hold
-unchanged: inference stays on the per-layer kernels, DVAE_MODULE_PATH=layers wins.  Not covered: the M2_info body ("M2_DEC": encoder on
-x alone) of other sizes lives in another rows kernel (csrc/train_info.hip) and stays per-layer; and whether the generic engine should be
-the default is left to the measurement in DESIGN 4b.
+unchanged: inference stays on the per-layer kernels, DVAE_MODULE_PATH=layers wins.  Whether the generic engine should be the default is
+left to the measurement in DESIGN 4b.
+
+The M2_info body of any covered size (opt-in, a switch of its own).  `DeepGenerativeModel_v3` / `_v5` ("M2_DEC": encoder on x alone, decoder
+on [z | y]) with an edited geometry, or with IBM labels (y 513) at the reference widths, runs per layer by default as well.  With
+    DVAE_MODULE_INFO_BODY unset / 0 / off   as ever: the resident engine at 128 / 128 / 16 / y 1, per-layer elsewhere
+    DVAE_MODULE_INFO_BODY=1 / on            resident where it serves, else the generic engine on a plan of dvae_module_generic_plan: two hidden
+                                            layers, x 513, y 1..513, h 1..512, z 1..128, biases, no flow
+    DVAE_MODULE_INFO_BODY=force             the generic engine wherever covered (tests, A/B runs)
+    set_info_body(module, mode)             the same per module, on a _v3 or a _v5 (forwarded to its enc_dec_clf); None: the environment
+the body is ONE Function on the DEC variant of the generic rows kernel's module modes.  DVAE_MODULE_GENERIC says nothing about this body,
+and this switch nothing about M1 / M2.  On the generic engine of this body -- and there only -- the label input may carry a gradient:
+`model(x, classifier(x))` of scripts/training_M2_info_vad_pretrain.py:162-163 stays on the fused path, and the Function's backward returns
+d loss / d y = dpre_d1 D1[:, z:] in the slot of y (dvae_module_generic_backward_y: computed beside dz in the rows kernel, no further
+launch).  A gradient with respect to x, and with respect to y on M2 or on the resident engine, stays a layer-path feature.
 """
 import ctypes
 import os
@@ -228,7 +240,7 @@ class GenericModuleEngine(ModuleEngine):
         if got is None:
             while len(self.plans) >= self.MAX_PLANS:
                 self.plans.pop(next(iter(self.plans)))
-            got = [TG.make_plan(self.model, self.dims, B), None, False]
+            got = [TG.make_plan(self.model, self.dims, B) if self.model != "M2_DEC" else make_body_plan(self.dims, B), None, False]
         self.plans[B] = got                        # most recently used last
         return got
 
@@ -258,8 +270,9 @@ class GenericModuleEngine(ModuleEngine):
         mu, lv, z = mlz.unbind(0)
         return r, z, mu, lv
 
-    def backward(self, x, y, eps, gr, gz, gmu, glv, needs):
-        """-> list of 14 parameter gradients (None where `needs` is False): views of one flat buffer of this call."""
+    def backward(self, x, y, eps, gr, gz, gmu, glv, needs, need_y=False):
+        """-> list of 14 parameter gradients (None where `needs` is False): views of one flat buffer of this call.  need_y (the M2_DEC
+        body only): the list and the label gradient, a fresh [B, y] tensor."""
         B = x.shape[0]
         plan, ws = self._ready(B)
         f32c = lambda t: None if t is None else _rows_ok(t.to(torch.float32))
@@ -268,10 +281,15 @@ class GenericModuleEngine(ModuleEngine):
         with torch.cuda.device(self.device):
             dst = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
             yp, ldy = (N.ptr(y), N.ld(y)) if self.y_dim else (None, 0)
-            N.check(self.lib.dvae_module_generic_backward(ctypes.byref(plan), N.ptr(self.flat), N.ptr(ws), N.ptr(x), N.ld(x), yp, ldy, N.ptr(eps),
-                                                          N.ptr(gr_), 0 if gr_ is None else N.ld(gr_), N.ptr(gmu), N.ptr(glv), N.ptr(gz),
-                                                          N.ptr(dst), 0, N.stream()), "dvae_module_generic_backward")
-        return [dst.as_strided(shp, std, o) if need else None for (shp, std, o), need in zip(self._grad_views(), needs)]
+            head = (ctypes.byref(plan), N.ptr(self.flat), N.ptr(ws), N.ptr(x), N.ld(x), yp, ldy, N.ptr(eps), N.ptr(gr_),
+                    0 if gr_ is None else N.ld(gr_), N.ptr(gmu), N.ptr(glv), N.ptr(gz), N.ptr(dst), 0)
+            if need_y:
+                gy = torch.empty((B, self.y_dim), dtype=torch.float32, device=self.device)
+                N.check(self.lib.dvae_module_generic_backward_y(*head, N.ptr(gy), self.y_dim, N.stream()), "dvae_module_generic_backward_y")
+            else:
+                N.check(self.lib.dvae_module_generic_backward(*head, N.stream()), "dvae_module_generic_backward")
+        grads = [dst.as_strided(shp, std, o) if need else None for (shp, std, o), need in zip(self._grad_views(), needs)]
+        return (grads, gy) if need_y else grads
 
 
 class VaeFunction(torch.autograd.Function):
@@ -300,6 +318,9 @@ class VaeFunction(torch.autograd.Function):
                                    f"between forward and backward); run the forward again")
         if any(p.data_ptr() != want for p, want in zip(eng.params, eng.pptrs)):
             raise RuntimeError("a parameter's storage was replaced between forward and backward (module.to() / .data assignment): run the forward again")
+        if ctx.has_y and ctx.needs_input_grad[2]:       # engine_for lets a label input with a gradient through to the generic M2_DEC engine alone
+            grads, gy = eng.backward(x, y, eps, gr, gz, gmu, glv, ctx.needs_input_grad[4:], need_y=True)
+            return (None, None, gy, None, *grads)
         grads = eng.backward(x, y if ctx.has_y else None, eps, gr, gz, gmu, glv, ctx.needs_input_grad[4:])
         return (None, None, None, None, *grads)
 
@@ -328,6 +349,55 @@ def set_generic(module, mode):
     object.__setattr__(module, "_dvae_generic", mode)
 
 
+def info_body_mode(module=None):
+    """"off" | "on" | "force": the module's own setting (set_info_body) or else DVAE_MODULE_INFO_BODY (module docstring)."""
+    m = module.__dict__.get("_dvae_info_body") if module is not None else None
+    if m is None:
+        m = os.environ.get("DVAE_MODULE_INFO_BODY", "0")
+    try:
+        return GENERIC_MODES[str(m).lower()]
+    except KeyError:
+        raise ValueError(f"DVAE_MODULE_INFO_BODY / set_info_body: {m!r} (0 / off, 1 / on, force)") from None
+
+
+def set_info_body(module, mode):
+    """The switch of the generic engine for the M2_info body of this module alone -- a DeepGenerativeModel_v3, or a _v5 (forwarded to its
+    enc_dec_clf): "off" / 0, "on" / 1, "force", or None to follow DVAE_MODULE_INFO_BODY again.  Takes effect at the next forward."""
+    if mode is not None:
+        mode = "on" if mode is True else "off" if mode is False else str(mode).lower()
+        if mode not in GENERIC_MODES:
+            raise ValueError(f"set_info_body: mode {mode!r} (0 / off, 1 / on, force, or None)")
+    body = module.__dict__.get("_modules", {}).get("enc_dec_clf", module)
+    object.__setattr__(body, "_dvae_info_body", mode)
+
+
+def _mode_of(module, model):
+    """the switch that speaks for this model: DVAE_MODULE_INFO_BODY for the M2_info body, DVAE_MODULE_GENERIC for M1 / M2"""
+    return info_body_mode(module) if model == "M2_DEC" else generic_mode(module)
+
+
+def make_body_plan(dims, batch, ksplit=0):
+    """dvae_module_generic_plan for the M2_DEC body (dims, batch): host only.  Raises NotImplementedError / ValueError with the library's message."""
+    lib = N.load()
+    h = tuple(dims["h_dim"])
+    if dims.get("x_dim") != 513 or len(h) != 2:
+        raise NotImplementedError(f"the generic module engine covers x_dim 513 and two hidden widths; got M2_DEC {dims}")
+    plan = TG.GenericPlan()
+    rc = lib.dvae_module_generic_plan(MODEL_CODE["M2_DEC"], int(dims["y_dim"]), int(dims["z_dim"]), int(h[0]), int(h[1]), int(batch), int(ksplit),
+                                      ctypes.byref(plan))
+    if rc != 0:
+        msg = lib.dvae_last_error().decode("utf-8", "replace")
+        raise (NotImplementedError if rc == 1003 else ValueError)(f"{msg} (got M2_DEC {dims})")
+    return plan
+
+
+def body_covered(dims):
+    """The geometry limits of the M2_DEC body on the generic engine (host logic only)."""
+    h = tuple(dims.get("h_dim", ()))
+    return (dims.get("x_dim") == 513 and len(h) == 2 and all(1 <= int(v) <= 512 for v in h) and 1 <= int(dims.get("z_dim", 0)) <= 128
+            and 1 <= int(dims.get("y_dim", 0) or 0) <= 513)
+
+
 def _resident_geometry(module, model):
     return (module.z_dim == 16 and module.flow is None
             and [tuple(l.weight.shape) for l in module.encoder.hidden] == [(128, 513 + (module.y_dim if model == "M2" else 0)), (128, 128)]
@@ -337,29 +407,32 @@ def _resident_geometry(module, model):
 
 
 def generic_dims(module, model):
-    """dims of an M1 / M2 module the generic engine covers (trainer_generic.covered and every layer of the plan's shape), else None.
-    Host logic only."""
-    if model not in ("M1", "M2") or module.flow is not None:
+    """dims of an M1 / M2 module, or of the M2_DEC body of a _v3, the generic engine covers (trainer_generic.covered / body_covered and every
+    layer of the plan's shape), else None.  Host logic only."""
+    if model not in ("M1", "M2", "M2_DEC") or module.flow is not None:
         return None
     enc, dec = list(module.encoder.hidden), list(module.decoder.hidden)
     if len(enc) != 2 or len(dec) != 2 or not all(isinstance(l, torch.nn.Linear) and l.bias is not None for l in enc + dec):
         return None
-    y = int(module.y_dim) if model == "M2" else 0
+    y = int(module.y_dim) if model != "M1" else 0
+    ye = y if model == "M2" else 0                   # the label columns of encoder layer 1
     z, h1, h2 = int(module.z_dim), enc[0].out_features, enc[1].out_features
-    dims = dict(x_dim=enc[0].in_features - y, y_dim=y, z_dim=z, h_dim=(h1, h2))
+    dims = dict(x_dim=enc[0].in_features - ye, y_dim=y, z_dim=z, h_dim=(h1, h2))
     sample, rec = module.encoder.sample, module.decoder.reconstruction
     shapes = [tuple(l.weight.shape) for l in (enc[0], enc[1], getattr(sample, "mu", rec), getattr(sample, "log_var", rec), dec[0], dec[1], rec)]
-    if not TG.covered(model, dims) or shapes != [(h1, 513 + y), (h2, h1), (z, h2), (z, h2), (h2, z + y), (h1, h2), (513, h1)]:
+    ok = body_covered(dims) if model == "M2_DEC" else TG.covered(model, dims)
+    if not ok or shapes != [(h1, 513 + ye), (h2, h1), (z, h2), (z, h2), (h2, z + y), (h1, h2), (513, h1)]:
         return None
     return dims
 
 
 def engine_kind(module, model):
     """"resident", "generic" or None: the engine a grad-mode forward of this module on CUDA float32 tensors would take as the switches
-    stand (DVAE_MODULE_PATH, DVAE_MODULE_GENERIC, set_generic).  Host logic only: nothing is built and no device is touched."""
+    stand (DVAE_MODULE_PATH; DVAE_MODULE_GENERIC / set_generic for M1 / M2; DVAE_MODULE_INFO_BODY / set_info_body, and that switch only,
+    for the M2_DEC body).  Host logic only: nothing is built and no device is touched."""
     if not enabled():
         return None
-    mode = generic_mode(module)
+    mode = _mode_of(module, model)
     dims = generic_dims(module, model) if mode != "off" else None
     if _resident_geometry(module, model) and not (mode == "force" and dims is not None):
         return "resident"
@@ -370,11 +443,12 @@ def engine_for(module, model, x, y):
     """The module's engine when this call can take the fused path, else None.  model: "M1" | "M2" | "M2_DEC" (module: a _v3)."""
     if not (enabled() and x.is_cuda and x.dim() == 2 and x.shape[1] == 513 and x.dtype == torch.float32 and x.shape[0] > 0):
         return None
-    if x.requires_grad or (y is not None and y.requires_grad):
-        return None                                  # gradients with respect to the data are a layer-path feature
+    y_grad = y is not None and y.requires_grad
+    if x.requires_grad or (y_grad and model != "M2_DEC"):
+        return None                                  # gradients with respect to the data are a layer-path feature (but see y_grad below)
     if not torch.is_grad_enabled():
         return None                                  # inference: the exact-fp32 per-layer kernels (module docstring)
-    mode = generic_mode(module)
+    mode = _mode_of(module, model)
     eng = module.__dict__.get("_dvae_engine")
     if eng is not None and not (eng.current() and eng.mode == mode):
         eng = None                                   # a parameter object was replaced, or the switch moved: a new engine on the set
@@ -398,6 +472,8 @@ def engine_for(module, model, x, y):
         object.__setattr__(module, "_dvae_engine", eng)
     if not eng.usable(x):
         return None
+    if y_grad and eng.kind != "generic":
+        return None                                  # the label gradient exists on the generic engine of the M2_DEC body alone
     if model != "M1" and (y is None or y.dim() != 2 or y.shape != (x.shape[0], eng.y_dim) or y.dtype != torch.float32 or y.device != x.device):
         return None
     return eng

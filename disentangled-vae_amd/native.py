@@ -126,6 +126,9 @@ SIGNATURES = {
     "dvae_train_gradnorm_scratch_bytes": (c_i64, [c_i64]),
     "dvae_module_generic_forward": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i, c_vp]),
     "dvae_module_generic_backward": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i, c_vp]),
+    "dvae_module_generic_plan": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i64, c_i, c_vp]),
+    "dvae_module_generic_backward_y": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_i64,
+                                             c_vp]),
     "dvae_train_clf_plan": (c_i, [c_i, c_i, c_i, c_i, c_i64, c_i, c_vp]),
     "dvae_train_clf_init": (c_i, [c_vp, c_vp, c_vp, c_vp]),
     "dvae_train_clf_repack": (c_i, [c_vp, c_vp, c_vp, c_vp]),

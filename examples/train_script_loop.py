@@ -7,9 +7,16 @@ torch.optim.Adam) on an M1 / M2 module of ANY covered size, run as one autograd 
     # an objective the fused train step does not have -- here it is three lines of torch on (r, mu, log_var)
     python examples/train_script_loop.py --model M1 --synthetic 20000 --z-dim 32 --h-dim 256 64 --kl-weight 0.25 --warmup 200
 
+    # the M2_info loop bodies (two torch.optim.Adam, the drop-in DeepGenerativeModel_v5): the main script's, scripts/training_M2_info_vad.py:
+    # 159-198, and under --decoder-label classifier the pretrain script's, scripts/training_M2_info_vad_pretrain.py:162-200, whose decoder
+    # reads the classifier's output, so that the body's label input carries a gradient
+    python examples/train_script_loop.py --model M2_info --synthetic 20000 --z-dim 32 --h-dim 256 64
+    python examples/train_script_loop.py --model M2_info --y-dim 513 --z-dim 16 --h-dim 128 128 --decoder-label classifier --aux-enc entropy --gamma 10
+
 The script sets the switch itself (DVAE_MODULE_GENERIC=1; `module_path.set_generic(model, "on")` does the same for one module) and prints
 which engine the module takes: "generic" here, "resident" at the reference's z 16 / h 128 128, None outside the covered sizes (the
-per-layer kernels).  Whoever wants the whole step fused, optimizer included, uses examples/train_fused.py.
+per-layer kernels).  For M2_info the switch is the body's own, module_path.set_info_body(model, "on") (DVAE_MODULE_INFO_BODY=1), and the
+classifier and the auxiliary net stay per-layer calls, as the script makes them.  Whoever wants the whole step fused, optimizer included, uses examples/train_fused.py.
 """
 import argparse
 import importlib
@@ -23,7 +30,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("DVAE_MODULE_GENERIC", "1")
 module_path = importlib.import_module("disentangled-vae_amd.module_path")
-from packages.models.models import DeepGenerativeModel, VariationalAutoencoder      # noqa: E402
+script_loops = importlib.import_module("disentangled-vae_amd.script_loops")
+from packages.models.models import DeepGenerativeModel, DeepGenerativeModel_v5, VariationalAutoencoder      # noqa: E402
 from packages.models.utils import elbo                                               # noqa: E402
 
 
@@ -48,7 +56,7 @@ class Warmup:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", choices=["M1", "M2"], default="M2")
+    ap.add_argument("--model", choices=["M1", "M2", "M2_info"], default="M2")
     ap.add_argument("--synthetic", type=int, default=20000, metavar="N", help="frames of synthetic power spectra")
     ap.add_argument("--y-dim", type=int, default=1)
     ap.add_argument("--z-dim", type=int, default=32)
@@ -59,10 +67,17 @@ def main():
     ap.add_argument("--kl-weight", type=float, default=1.0, help="weight of the KL term, applied in torch")
     ap.add_argument("--warmup", type=int, default=0, help="steps over which the KL weight rises linearly from 0")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--decoder-label", choices=list(script_loops.DECODER_LABELS), default="truth", help="M2_info: what the decoder reads beside z")
+    ap.add_argument("--aux-enc", choices=list(script_loops.AUX_ENCS), default="bce", help="M2_info: the adversarial term on the encoder")
+    ap.add_argument("--alpha", type=float, default=0.0)
+    ap.add_argument("--beta", type=float, default=10.0)
+    ap.add_argument("--gamma", type=float, default=1.0)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("train_script_loop.py needs the MI355X HIP path (no CPU fallback)")
     torch.manual_seed(a.seed)
+    if a.model == "M2_info":
+        return main_info(a)
     y_dim = a.y_dim if a.model == "M2" else 0
     if a.model == "M1":
         model = VariationalAutoencoder([513, a.z_dim, list(a.h_dim)])
@@ -95,6 +110,31 @@ def main():
         l, rc, kl = (tot / nb).tolist()
         print(f"epoch {epoch + 1:3d}  loss {l:.3f}  recon {rc:.3f}  KL {kl:.3f}  KL weight {beta.t:.3f}  "
               f"{1e6 * (time.time() - t0) / nb:.0f} us / step", flush=True)
+
+
+def main_info(a):
+    model = DeepGenerativeModel_v5([513, a.y_dim, a.z_dim, list(a.h_dim)]).cuda()
+    module_path.set_info_body(model, "on")
+    print(f"engine_kind: {module_path.engine_kind(model.enc_dec_clf, 'M2_DEC')}", flush=True)
+    X, Y = synthetic(a.synthetic, a.y_dim, a.seed)
+    X, Y = torch.from_numpy(X).cuda(), torch.from_numpy(Y).cuda()
+    opt_body = torch.optim.Adam(model.enc_dec_clf.parameters(), lr=a.lr, betas=(0.9, 0.999))      # one optimizer per sub-model, as in the scripts
+    opt_aux = torch.optim.Adam(model.auxiliary.parameters(), lr=a.lr, betas=(0.9, 0.999))
+    names = ("ELBO", "recon", "KL", "enc_loss", "classif_loss", "aux_loss")
+    for epoch in range(a.epochs):
+        t0 = time.time()
+        tot = torch.zeros(len(names), dtype=torch.float64, device="cuda")
+        perm = torch.randperm(X.shape[0], device="cuda")
+        nb = 0
+        for lo in range(0, X.shape[0], a.batch):
+            idx = perm[lo:lo + a.batch]
+            L = script_loops.info_step(model, opt_body, opt_aux, X[idx], Y[idx], decoder_label=a.decoder_label, aux_enc=a.aux_enc,
+                                       alpha=a.alpha, beta=a.beta, gamma=a.gamma)
+            tot += torch.stack([L[k] for k in names]).double()
+            nb += 1
+        torch.cuda.synchronize()
+        print(f"epoch {epoch + 1:3d}  " + "  ".join(f"{k} {v:.3f}" for k, v in zip(names, (tot / nb).tolist()))
+              + f"  {1e6 * (time.time() - t0) / nb:.0f} us / step", flush=True)
 
 
 if __name__ == "__main__":

@@ -182,7 +182,7 @@ int dvae_train_repack(const dvae_train_plan_t* plan, const float* params, void* 
  * flat buffers laid out per the plan (state_dict order, 256-byte aligned tensors), scratch in `ws`, results stream-ordered. */
 typedef struct {
     /* inputs (echoed) */
-    int32_t model;            /* DVAE_MODEL_M1 or DVAE_MODEL_M2 */
+    int32_t model;            /* DVAE_MODEL_M1 or DVAE_MODEL_M2 (DVAE_MODEL_M2_DEC: dvae_module_generic_plan, the module entry points only) */
     int32_t y_dim, z_dim, h1, h2;
     int32_t precision;        /* DVAE_PREC_F32 */
     int32_t ksplit;           /* frame slices of the weight-gradient reduction = slabs the apply kernel sums (at most 16) */
@@ -304,6 +304,26 @@ int dvae_module_generic_forward(const dvae_train_generic_plan_t* plan, const flo
 int dvae_module_generic_backward(const dvae_train_generic_plan_t* plan, const float* params, void* ws, const float* x, int64_t ldx,
                                  const float* y, int64_t ldy, const float* eps_noise, const float* g_r, int64_t ld_gr,
                                  const float* g_mu, const float* g_lv, const float* g_z, float* grad_flat, int accumulate, void* stream);
+/* The M2_info body ("M2_DEC": DeepGenerativeModel_v3's encoder on x ALONE, decoder on [z | y]) of any covered size on the same two entry
+ * points.  dvae_module_generic_plan (host only): for DVAE_MODEL_M1 / _M2 the plan of dvae_train_generic_plan at DVAE_PREC_F32, byte for
+ * byte; for DVAE_MODEL_M2_DEC, y_dim 1..513 with the same limits on h1 / h2 / z_dim, a plan whose tensor 0 is [h1, 513] (the encoder has no
+ * label columns: the packed label block of encoder layer 1 has no elements) and whose tensor 8 is [h2, z_dim + y_dim]; one more packed
+ * copy, the transposed label columns of decoder layer 1, sits behind the last packed copy of the workspace.  The plan is exact fp32 (there
+ * is no precision argument; a plan whose precision field was changed is refused as any changed plan).  DVAE_E_BADARG naming the limits for
+ * a size outside them, DVAE_E_UNSUPPORTED for any other model (M2_info as a whole: dvae_train_info_plan).
+ * dvae_train_generic_init / _repack and dvae_module_generic_forward / _backward accept an M2_DEC plan (y is required).  Every train-step
+ * entry point above (_grads, _step, _eval, _apply, _reduce, _apply_flat, _apply_flat_clipped) refuses it with DVAE_E_BADARG naming the
+ * model before anything is launched: there is no train step on the body alone.
+ * dvae_module_generic_backward_y is _backward plus the gradient with respect to the labels: g_y [B, y_dim] (ld_gy >= y_dim) receives
+ * dpre_d1 D1[:, z:] -- the decoder's share, the only one: the encoder does not see y; no 1 / B, as for the other upstream gradients --
+ * computed beside dz in the rows kernel, no further launch.  Padding between the rows of g_y is not written.  g_y NULL: exactly _backward
+ * (nothing further is computed or written).  The parameter gradients have the same bits with and without g_y.  DVAE_E_BADARG by name,
+ * before anything is launched: ld_gy below y_dim, a g_y on a plan whose model is not M2_DEC, and whatever _backward refuses. */
+int dvae_module_generic_plan(int model, int y_dim, int z_dim, int h1, int h2, int64_t B, int ksplit_hint, dvae_train_generic_plan_t* plan);
+int dvae_module_generic_backward_y(const dvae_train_generic_plan_t* plan, const float* params, void* ws, const float* x, int64_t ldx,
+                                   const float* y, int64_t ldy, const float* eps_noise, const float* g_r, int64_t ld_gr,
+                                   const float* g_mu, const float* g_lv, const float* g_z, float* grad_flat, int accumulate,
+                                   float* g_y, int64_t ld_gy, void* stream);
 
 /* ---- the fused train step for the label classifier alone (csrc/train_classifier.hip): Classifier([513, [h1, h2], y_dim]) of
  * packages/models/models.py -- relu, relu, sigmoid -- under binary_cross_entropy (packages/models/utils.py:55-56) and Adam: the loop body

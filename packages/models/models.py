@@ -16,8 +16,8 @@ nn.Linear + activation pair is one call of `_dense`:
     PyTorch's own host cost, not by 64 launches per step.  DVAE_MODULE_PATH=layers keeps the per-layer Functions.
   * CUDA tensors at any other covered size (M1 / M2, x 513, y 0..513, two hidden widths 1..512, z 1..128) through the M1 / M2 model
     forward -> the per-layer Functions by default; with DVAE_MODULE_GENERIC=1 (or module_path.set_generic(model, "on")) ONE autograd
-    Function as well, on the generic kernels in exact fp32 (module_path.GenericModuleEngine).  The M2_info body of other sizes stays
-    per-layer.
+    Function as well, on the generic kernels in exact fp32 (module_path.GenericModuleEngine).  The M2_info body (_v3 / _v5) of other sizes, or with
+    y 513, likewise under its own switch DVAE_MODULE_INFO_BODY=1 (module_path.set_info_body), label gradient included.
   * host tensors  -> the same ATen ops the reference runs on CPU (the
     reference's CPU mode; scripts select it when no GPU exists).  This is
     selected by the tensors' device only, never as a substitute for the HIP path.
