@@ -312,6 +312,20 @@ class Reference:
         self.replaced, self.margin = 0, np.inf
         if model == "M2_info":
             self.replaced, self.margin = make_tie_free(self.params, self.x, self.y, self.e)
+        self._build()
+
+    @classmethod
+    def at(cls, model, y_dim, params, x, y, e):
+        """The reference of one step on GIVEN float32 parameters and frames (tests/later_steps.py) in the place of the family's."""
+        self = cls.__new__(cls)
+        self.family, self.model, self.B, self.dims = "given", model, int(x.shape[0]), dims_of(y_dim)
+        self.params, self.x, self.y, self.e = params, x, y, e
+        self.replaced, self.margin = 0, np.inf
+        self._build()
+        return self
+
+    def _build(self):
+        model = self.model
         a = (model, self.params, self.x, self.y, self.e)
         self.truth = oracle_grads(*a)
         self.restated = {"fp32": oracle_grads(*a, dtype=np.float32), "fp32 k-steps": oracle_grads(*a, dtype=np.float32, hook=KStepOrderF32())}

@@ -269,13 +269,29 @@ class Reference:
         self.key = (kind, case, mode, B, ksplit, family, micro)
         self.label = case_label(*self.key)
         self.params, self.x, self.y, self.e = case_inputs(kind, case, B, family)
-        self.z_dim = None if kind == "clf" else case[1]
         if family == "bench" and mode in (None, DEFAULT_MODE):
-            self.truth = MODS[kind].truth(case, B)[1][0]
+            self._build(MODS[kind].truth(case, B)[1][0])
         elif family == "bench":
-            self.truth = mc.truth(case, B, tuple(mode))[1][0]
+            self._build(mc.truth(case, B, tuple(mode))[1][0])
         else:
-            self.truth = self.run(np.arange(B), np.float64)
+            self._build()
+
+    @classmethod
+    def at(cls, kind, case, mode, params, x, y, e, ksplit, micro=None, label=None):
+        """The reference of one step on GIVEN float32 parameters and frames (tests/later_steps.py: step k of a trainer, whose
+        parameters are what the device reports before it) in the place of case_inputs(...); everything else as __init__ builds it."""
+        self = cls.__new__(cls)
+        self.key = (kind, case, None if mode is None else tuple(mode), int(x.shape[0]), ksplit, "given", micro)
+        self.label = case_label(*self.key) if label is None else label
+        self.params, self.x, self.y, self.e = params, x, y, e
+        self._build()
+        return self
+
+    def _build(self, truth=None):
+        """truth None: the float64 oracle on the frames as they stand (what the cases modules' cached truths hold, bit for bit)."""
+        kind, case, mode, B, ksplit, family, micro = self.key
+        self.z_dim = None if kind == "clf" else case[1]
+        self.truth = self.run(np.arange(B), np.float64) if truth is None else truth
         self.sizes = (B,) if micro is None else tuple(micro)
         assert sum(self.sizes) == B
         self.plans = [slice_plan(b, ksplit) for b in self.sizes]

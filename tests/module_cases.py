@@ -324,6 +324,18 @@ class Reference:
         self.x, self.y, self.e = gu.make_batch(self.dims, B, BATCH_SEED)
         self.up = make_upstream(B)
         self.keys = tuple(UPSTREAMS) if B in FULL_CROSS_AT else ("all",)
+        self._build()
+
+    @classmethod
+    def at(cls, model, y_dim, params, x, y, e, up, keys=("all",)):
+        """The reference on GIVEN float32 parameters, frames and upstream gradients (tests/later_steps.py) in the place of the case's."""
+        self = cls.__new__(cls)
+        self.model, self.y_dim, self.B, self.dims = model, y_dim, int(x.shape[0]), gc.dims_of(y_dim)
+        self.params, self.x, self.y, self.e, self.up, self.keys = params, x, y, e, up, tuple(keys)
+        self._build()
+        return self
+
+    def _build(self):
         for arr in (self.x, self.y, self.e, *self.up.values()):
             if arr is not None:
                 arr.setflags(write=False)

@@ -138,9 +138,22 @@ class Reference:
         self.case, self.B = tuple(case), B
         self.params, self.x, self.y, self.e = inputs(self.case, B)
         self.up = mg.make_upstream(B, case[1])
+        self.keys = tuple(UPSTREAMS) if B == FULL_CROSS_AT else ("all",)
+        self._build()
+
+    @classmethod
+    def at(cls, case, params, x, y, e, up, keys=("all",)):
+        """The reference on GIVEN float32 parameters, frames and upstream gradients (tests/later_steps.py) in the place of the case's."""
+        self = cls.__new__(cls)
+        self.case, self.B = tuple(case), int(x.shape[0])
+        self.params, self.x, self.y, self.e, self.up, self.keys = params, x, y, e, up, tuple(keys)
+        self._build()
+        return self
+
+    def _build(self):
+        case, B = self.case, self.B
         for a in self.up.values():
             a.setflags(write=False)
-        self.keys = tuple(UPSTREAMS) if B == FULL_CROSS_AT else ("all",)
         self.slice_frames, self.nslices = slice_plan(case, B)
         self.out, self.truth = self.run()
         a = self._figures(*self.run(np.float32))

@@ -73,8 +73,13 @@ def pool(case, B, batch_seed=BATCH_SEED):
 
 
 def frame_ok(case, x):
-    """Per frame of x (float64 oracle): both conditions of the module docstring hold."""
-    p = {k: v.astype(np.float64) for k, v in params_of(case).items()}
+    """Per frame of x (float64 oracle): both conditions of the module docstring hold under the case's own parameters."""
+    return frames_ok(params_of(case), x)
+
+
+def frames_ok(params, x):
+    """frame_ok under any parameters (tests/later_steps.py: those a later step starts from)."""
+    p = {k: np.asarray(v).astype(np.float64) for k, v in params.items()}
     h = x.astype(np.float64)
     ok = np.ones(x.shape[0], bool)
     for name in ("hidden.0", "hidden.1", "output_layer"):
