@@ -170,6 +170,9 @@ struct GRowsArgs {
     float elbo_eps, invB;
     int fwd_only;
     const float* nmean; const float* ndiv;    // NORM: [513] the mean and fl32(std + fl32(norm_eps)) of the standardised encoder input
+    // the weighted KL term (plan->kl_weight w, plan->kl_floor): kl_scale = fl32(fl32(w) * invB) -- invB itself at w = 1 --, the scale of the
+    // KL parts of d mu and d log_var where the element k = -0.5 (lv - mu^2 - e^lv) is not below kl_floor; they are exact zeros below it
+    float kl_scale, kl_floor;
 };
 // the module modes (dvae_module_generic_forward / _backward): the model's outputs, or the upstream gradients of them (each may be null)
 struct GModuleArgs {
@@ -201,10 +204,15 @@ struct __attribute__((packed, aligned(4))) G4U { f32x4 v; };      // 16 bytes at
 //   consecutive label columns of its frame stored straight from the accumulator -- no LDS, no further barrier.  The encoder gives g_y
 //   nothing, and there is no 1 / B.  A frame past B, a column >= y and the padding of a row are never written; out_gy null: the tiles
 //   are not computed.
-template <bool NORM, int MODE = ROWS_STEP, bool DEC = false>
+// KLW (ROWS_STEP only; plan->kl_weight / kl_floor other than 1 / 0): the KL parts of d mu and d log_var carry kl_scale = w / B where the
+//   element k = -0.5 (lv - mu^2 - e^lv) is not below kl_floor and are exact zeros below it, and the workgroup's third partial is the sum
+//   of max(k, kl_floor).  A template flag and not the two scalars alone: the instantiations without it are the code they were,
+//   instruction for instruction (DESIGN 4a': the resource table).
+template <bool NORM, int MODE = ROWS_STEP, bool DEC = false, bool KLW = false>
 __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L, const GRowsArgs g, const GModuleArgs mo) {
     static_assert(MODE == ROWS_STEP || !NORM, "the module modes take the encoder input as it is given");
     static_assert(!DEC || MODE != ROWS_STEP, "there is no train step on an M2_DEC plan");
+    static_assert(!KLW || MODE == ROWS_STEP, "the module modes' upstream gradients carry the loss");
     extern __shared__ __attribute__((aligned(16))) float gsm[];
     float* X = gsm;                                     // [528][16] x, then d loss / d a
     float* Y = X + GT * GXP;                            // [yp][16]
@@ -219,6 +227,7 @@ __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L
     const float* wp = g.ws;
     const bool bwd = MODE == ROWS_MODULE_BWD || (MODE == ROWS_STEP && !g.fwd_only);
     double sum_is = 0.0, sum_kl = 0.0;
+    [[maybe_unused]] double sum_kc = 0.0;               // KLW: the KL elements clamped from below at kl_floor
 
     for (int64_t tile = blockIdx.x; tile < L.tiles; tile += gridDim.x) {
         const int64_t r0 = tile * GT;
@@ -319,10 +328,20 @@ __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L
             const float zv = mu + sd * e;
             Bf[j * GT + c] = zv;
             if constexpr (MODE == ROWS_STEP) {
-                C[j * GT + c] = ok ? mu * g.invB : 0.f;
-                C[(L.zp + j) * GT + c] = ok ? -0.5f * (1.f - ev) * g.invB : 0.f;
-                C[(2 * L.zp + j) * GT + c] = 0.5f * sd * e;
-                if (ok) sum_kl += (double)(-0.5f * (lv - mu * mu - ev));
+                if constexpr (KLW) {
+                    // the KL element and its weight: w / B where it is not below the floor (torch.clamp's gradient), zero below it
+                    const float k = -0.5f * (lv - mu * mu - ev);
+                    const float ks = (ok && !(k < g.kl_floor)) ? g.kl_scale : 0.f;
+                    C[j * GT + c] = ok ? mu * ks : 0.f;
+                    C[(L.zp + j) * GT + c] = ok ? -0.5f * (1.f - ev) * ks : 0.f;
+                    C[(2 * L.zp + j) * GT + c] = 0.5f * sd * e;
+                    if (ok) { sum_kl += (double)k; sum_kc += (double)(k < g.kl_floor ? g.kl_floor : k); }
+                } else {
+                    C[j * GT + c] = ok ? mu * g.invB : 0.f;
+                    C[(L.zp + j) * GT + c] = ok ? -0.5f * (1.f - ev) * g.invB : 0.f;
+                    C[(2 * L.zp + j) * GT + c] = 0.5f * sd * e;
+                    if (ok) sum_kl += (double)(-0.5f * (lv - mu * mu - ev));
+                }
             } else if constexpr (MODE == ROWS_MODULE_FWD) {
                 if (ok) {
                     const int64_t o = (r0 + c) * L.z + j;
@@ -524,15 +543,22 @@ __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L
     if constexpr (MODE != ROWS_STEP) return;           // no loss sums, no partials
     // the workgroup's loss sums: waves in order
     sum_is = wave_sum(sum_is); sum_kl = wave_sum(sum_kl);
+    if constexpr (KLW) sum_kc = wave_sum(sum_kc);
     __syncthreads();                                    // the last tile's readers of X are done: its first bytes hold the sums
     double (*red)[2] = reinterpret_cast<double (*)[2]>(gsm);
-    if (lane == 0) { red[wave][0] = sum_is; red[wave][1] = sum_kl; }
+    [[maybe_unused]] double* redk = reinterpret_cast<double*>(gsm) + 8;
+    if (lane == 0) {
+        red[wave][0] = sum_is; red[wave][1] = sum_kl;
+        if constexpr (KLW) redk[wave] = sum_kc;
+    }
     __syncthreads();
     if (tid == 0) {
         double* p = g.partials + 4 * (int64_t)blockIdx.x;
         p[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
         p[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
-        p[2] = 0.0; p[3] = 0.0;
+        if constexpr (KLW) p[2] = ((redk[0] + redk[1]) + redk[2]) + redk[3];     // the clamped KL sum (GApplyArgs: kl_partials)
+        else p[2] = 0.0;
+        p[3] = 0.0;
     }
 }
 
@@ -636,6 +662,21 @@ __device__ __forceinline__ void finalize_step(const GApplyArgs& g, double (*red)
         for (int i = 0; i < g.cnt_wgs; ++i) c += g.cnt_partials[4 * (int64_t)i + threadIdx.x];
         g.counts4[threadIdx.x] = c;
         if (g.cnt_accum) g.cnt_accum[threadIdx.x] += c;
+    }
+    if (g.kl_partials) {                                // the weighted KL term: one partial a thread, then waves in order, as below
+        __syncthreads();                                // write_losses has read `red`
+        double v = (int)threadIdx.x < g.a.npartials ? g.kl_partials[(int64_t)threadIdx.x * g.kl_stride] : 0.0;
+        v = wave_sum(v);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][0] = v;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+#pragma clang fp contract(off)
+            const float kc = (float)((red[0][0] + red[1][0] + red[2][0] + red[3][0]) / (double)g.a.B);
+            const float wk = g.kl_w * kc;
+            g.a.losses3[0] = g.a.losses3[1] + wk;                            // the objective: recon + w mean sum max(k, floor); [1], [2] stay raw
+            if (g.a.info) g.a.losses3[3] = g.a.losses3[0] + g.a.losses3[4] - g.a.losses3[6];
+            if (g.kl_accum) for (int q = 0; q < (g.a.info ? 8 : 3); ++q) g.kl_accum[q] += (double)g.a.losses3[q];
+        }
     }
     if (g.v_partials) {                                 // one partial a thread: workgroup order within a wave's sum, waves in order
         static_assert(G_ROWS_GRID <= 256, "one thread of the finalising workgroup per rows workgroup");
@@ -909,6 +950,8 @@ static int plan_layout(const char* who, const dvae_train_generic_plan_t* plan, G
                    "%s: not a plan of dvae_train_generic_plan / dvae_module_generic_plan", who);
     DVAE_CHECK_ARG(plan->std_norm == 0 || plan->std_norm == 1, "%s: std_norm %d in the plan (0 or 1)", who, plan->std_norm);
     DVAE_CHECK_ARG(!dec || !plan->std_norm, "%s: std_norm on a plan of model M2_DEC", who);
+    DVAE_CHECK_ARG(plan->kl_weight >= 0.0 && isfinite(plan->kl_weight) && plan->kl_floor >= 0.0 && isfinite(plan->kl_floor),
+                   "%s: kl_weight %g / kl_floor %g in the plan (finite numbers >= 0; the planner sets 1 and 0)", who, plan->kl_weight, plan->kl_floor);
     L = make_layout(plan->y_dim, plan->z_dim, plan->h1, plan->h2, plan->B, plan->ksplit, plan->std_norm != 0, dec);
     DVAE_CHECK_ARG(L.ws_bytes == plan->workspace_bytes && L.nslices == plan->ksplit && L.n_params == plan->n_params &&
                    L.slice_frames == plan->slice_frames, "%s: the plan was changed after dvae_train_generic_plan", who);
@@ -946,29 +989,43 @@ static ApplyArgs apply_args(const dvae_train_generic_plan_t* plan, const GLayout
 
 // adam: the optimizer step on every parameter; otherwise only the packed copies are rewritten (params != null) and / or the losses finalised
 // (clip: the norm launch and the guarded apply kernel in place of the apply kernel)
-static int launch_apply(const GLayout& L, const ApplyArgs& a, char* ws, bool adam, bool elements, bool finalize, hipStream_t s,
-                        const GClipHost* clip = nullptr) {
+// The weighted KL term of a finalising launch.  The plan's defaults (1, 0) leave every argument as it was; any other pair hands the
+// finalising workgroup the clamped KL sums (slot 2 of the rows kernel's partials), and the running sums go through kl_accum.
+static bool kl_weighted(const dvae_train_generic_plan_t* plan) { return !((float)plan->kl_weight == 1.f && (float)plan->kl_floor == 0.f); }
+static void weighted_kl(const dvae_train_generic_plan_t* plan, const GLayout& L, char* ws, GApplyArgs& g) {
+    if (!kl_weighted(plan)) return;
+    const float w = (float)plan->kl_weight;
+    g.kl_partials = (const double*)(ws + L.o_partials) + 2; g.kl_stride = 4; g.kl_w = w;
+    g.kl_accum = g.a.accum; g.a.accum = nullptr;
+}
+
+static int launch_apply(const dvae_train_generic_plan_t* plan, const GLayout& L, const ApplyArgs& a, char* ws, bool adam, bool elements,
+                        bool finalize, hipStream_t s, const GClipHost* clip = nullptr) {
     GApplyArgs g;
     memset(&g, 0, sizeof(g));
     g.a = a;
     if (!elements) g.a.n_params = 0;
     make_tensors(L, g.t);
     g.ws = (float*)ws; g.adam = adam ? 1 : 0; g.finalize = finalize ? 1 : 0;
+    if (finalize) weighted_kl(plan, L, (char*)ws, g);
     return clip ? launch_apply_clipped_table(g, *clip, s) : launch_apply_table(g, s);
 }
 
 static int launch_rows(const dvae_train_generic_plan_t* plan, const GLayout& L, char* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
                        const float* eps, float elbo_eps, bool fwd_only, hipStream_t s, int mode = ROWS_STEP, const GModuleArgs* module = nullptr) {
-    static bool attr_done[6][64] = {};
+    static bool attr_done[8][64] = {};
     const bool dec = L.dec != 0;
     DVAE_CHECK_ARG(!dec || mode != ROWS_STEP, "train_generic_rows_kernel: no train step on a plan of model M2_DEC");
+    const bool klw = mode == ROWS_STEP && kl_weighted(plan);
     const void* kernel = mode == ROWS_MODULE_FWD ? (dec ? (const void*)train_generic_rows_kernel<false, ROWS_MODULE_FWD, true>
                                                        : (const void*)train_generic_rows_kernel<false, ROWS_MODULE_FWD>)
                        : mode == ROWS_MODULE_BWD ? (dec ? (const void*)train_generic_rows_kernel<false, ROWS_MODULE_BWD, true>
                                                        : (const void*)train_generic_rows_kernel<false, ROWS_MODULE_BWD>)
+                       : klw ? (L.norm ? (const void*)train_generic_rows_kernel<true, ROWS_STEP, false, true>
+                                       : (const void*)train_generic_rows_kernel<false, ROWS_STEP, false, true>)
                        : L.norm ? (const void*)train_generic_rows_kernel<true> : (const void*)train_generic_rows_kernel<false>;
     if (int rc = raise_lds_limit(kernel, "train_generic_rows_kernel", L.lds_bytes,
-                                 attr_done[mode == ROWS_STEP ? L.norm : (dec ? 3 : 1) + mode])) return rc;
+                                 attr_done[mode == ROWS_STEP ? (klw ? 6 : 0) + L.norm : (dec ? 3 : 1) + mode])) return rc;
     GModuleArgs mo;
     memset(&mo, 0, sizeof(mo));
     if (module) mo = *module;
@@ -978,6 +1035,7 @@ static int launch_rows(const dvae_train_generic_plan_t* plan, const GLayout& L, 
     g.row_index = (const int64_t*)(uintptr_t)plan->row_index; g.row_count = plan->row_count; g.bad = (int*)(uintptr_t)plan->bad_row_counter;
     g.ws = (float*)ws; g.stash = (float*)(ws + L.o_stash); g.partials = (double*)(ws + L.o_partials);
     g.elbo_eps = elbo_eps; g.invB = (float)(1.0 / (double)L.B); g.fwd_only = fwd_only ? 1 : 0;
+    g.kl_scale = (float)plan->kl_weight * g.invB; g.kl_floor = (float)plan->kl_floor;        // (read by the KLW instantiations)
     const dim3 grid((unsigned)L.rows_grid), block(256);
     if (mode == ROWS_MODULE_FWD && dec) {
         hipLaunchKernelGGL((train_generic_rows_kernel<false, ROWS_MODULE_FWD, true>), grid, block, (size_t)L.lds_bytes, s, L, g, mo);
@@ -989,7 +1047,10 @@ static int launch_rows(const dvae_train_generic_plan_t* plan, const GLayout& L, 
         hipLaunchKernelGGL((train_generic_rows_kernel<false, ROWS_MODULE_BWD>), grid, block, (size_t)L.lds_bytes, s, L, g, mo);
     } else if (L.norm) {
         g.nmean = (const float*)(uintptr_t)plan->norm_mean; g.ndiv = (const float*)(uintptr_t)plan->norm_div;
-        hipLaunchKernelGGL(train_generic_rows_kernel<true>, grid, block, (size_t)L.lds_bytes, s, L, g, mo);
+        if (klw) hipLaunchKernelGGL((train_generic_rows_kernel<true, ROWS_STEP, false, true>), grid, block, (size_t)L.lds_bytes, s, L, g, mo);
+        else hipLaunchKernelGGL(train_generic_rows_kernel<true>, grid, block, (size_t)L.lds_bytes, s, L, g, mo);
+    } else if (klw) {
+        hipLaunchKernelGGL((train_generic_rows_kernel<false, ROWS_STEP, false, true>), grid, block, (size_t)L.lds_bytes, s, L, g, mo);
     } else {
         hipLaunchKernelGGL(train_generic_rows_kernel<false>, grid, block, (size_t)L.lds_bytes, s, L, g, mo);
     }
@@ -1019,6 +1080,7 @@ using namespace dvae::tg;
 static void fill_plan(dvae_train_generic_plan_t* plan, const GLayout& L, int model, int precision, int std_norm) {
     memset(plan, 0, sizeof(*plan));
     plan->std_norm = std_norm;
+    plan->kl_weight = 1.0; plan->kl_floor = 0.0;
     plan->model = model; plan->y_dim = L.y; plan->z_dim = L.z; plan->h1 = L.h1; plan->h2 = L.h2; plan->precision = precision;
     plan->ksplit = L.nslices; plan->n_tensors = M_NT; plan->B = L.B; plan->n_params = L.n_params;
     for (int t = 0; t < M_NT; ++t) { plan->tensor_offset[t] = L.toff[t]; plan->tensor_rows[t] = L.trows[t]; plan->tensor_cols[t] = L.tcols[t]; }
@@ -1060,7 +1122,7 @@ extern "C" int dvae_train_generic_repack(const dvae_train_generic_plan_t* plan, 
     hipStream_t s = (hipStream_t)stream;
     DVAE_HIP(hipMemsetAsync(ws, 0, (size_t)L.wpack_elems * 4, s));          // the padding of the packed copies
     const ApplyArgs a = apply_args(plan, L, (float*)params, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, nullptr);
-    return launch_apply(L, a, (char*)ws, false, true, false, s);
+    return launch_apply(plan, L, a, (char*)ws, false, true, false, s);
 }
 
 extern "C" int dvae_train_generic_init(const dvae_train_generic_plan_t* plan, const float* params, void* ws, void* stream) {
@@ -1096,7 +1158,7 @@ extern "C" int dvae_train_generic_apply(const dvae_train_generic_plan_t* plan, f
     DVAE_CHECK_ARG(params && m && v && ws && losses3, "train_generic_apply: null pointer");
     DVAE_CHECK_ARG(step >= 1, "train_generic_apply: step %d (1-based)", step);
     const ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, losses3);
-    return launch_apply(L, a, (char*)ws, true, true, true, (hipStream_t)stream);
+    return launch_apply(plan, L, a, (char*)ws, true, true, true, (hipStream_t)stream);
 }
 
 extern "C" int dvae_train_generic_reduce(const dvae_train_generic_plan_t* plan, void* ws, float* flat, int accumulate, float weight, float* losses3,
@@ -1110,6 +1172,7 @@ extern "C" int dvae_train_generic_reduce(const dvae_train_generic_plan_t* plan, 
     g.f.a = apply_args(plan, L, nullptr, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, losses3);
     make_tensors(L, g.f.t);
     g.f.ws = (float*)ws; g.f.finalize = 1;
+    weighted_kl(plan, L, (char*)ws, g.f);
     g.flat = flat; g.accumulate = accumulate; g.weight = weight;
     return launch_reduce_table(g, (hipStream_t)stream);
 }
@@ -1121,7 +1184,7 @@ extern "C" int dvae_train_generic_apply_flat(const dvae_train_generic_plan_t* pl
     if (int rc = check_apply_flat_args("train_generic_apply_flat", params, m, v, ws, flat, step, lr, grad_scale)) return rc;
     ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, nullptr);
     a.slabs = flat; a.nslabs = 1;                       // the flat gradient is the one slab
-    return launch_apply(L, a, (char*)ws, true, true, false, (hipStream_t)stream);
+    return launch_apply(plan, L, a, (char*)ws, true, true, false, (hipStream_t)stream);
 }
 
 extern "C" int64_t dvae_train_gradnorm_scratch_bytes(int64_t n_params) {
@@ -1143,7 +1206,7 @@ extern "C" int dvae_train_generic_apply_flat_clipped(const dvae_train_generic_pl
     if (int rc = check_clip_args("train_generic_apply_flat_clipped", flat, clip)) return rc;
     ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, nullptr);
     a.slabs = flat; a.nslabs = 1;                       // the flat gradient is the one slab
-    return launch_apply(L, a, (char*)ws, true, true, false, (hipStream_t)stream, &clip);
+    return launch_apply(plan, L, a, (char*)ws, true, true, false, (hipStream_t)stream, &clip);
 }
 
 extern "C" int dvae_train_generic_step(const dvae_train_generic_plan_t* plan, float* params, float* m, float* v, void* ws, const float* x, int64_t ldx,
@@ -1164,7 +1227,7 @@ extern "C" int dvae_train_generic_eval(const dvae_train_generic_plan_t* plan, vo
     hipStream_t s = (hipStream_t)stream;
     if (int rc = launch_rows(plan, L, (char*)ws, x, ldx, y, ldy, eps_noise, elbo_eps, true, s)) return rc;
     const ApplyArgs a = apply_args(plan, L, nullptr, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, losses3);
-    return launch_apply(L, a, (char*)ws, false, false, true, s);
+    return launch_apply(plan, L, a, (char*)ws, false, false, true, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -1188,7 +1251,7 @@ extern "C" int dvae_module_generic_forward(const dvae_train_generic_plan_t* plan
     hipStream_t s = (hipStream_t)stream;
     if (repack) {                                       // every element of both packed copies from `params`; the padding is dvae_train_generic_init's
         const ApplyArgs a = apply_args(plan, L, (float*)params, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, nullptr);
-        if (int rc = launch_apply(L, a, (char*)ws, false, true, false, s)) return rc;
+        if (int rc = launch_apply(plan, L, a, (char*)ws, false, true, false, s)) return rc;
     }
     GModuleArgs mo;
     memset(&mo, 0, sizeof(mo));

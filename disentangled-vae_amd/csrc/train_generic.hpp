@@ -126,7 +126,11 @@ struct GWgradArgs {
 // also the confusion counts of the classifier step: [cnt_wgs][4] integers summed in workgroup order into counts4 (and added to cnt_accum);
 // with `v_partials` (the M2_info step whose adversarial term is not a cross entropy, train_info.hip) a fifth loss sum per rows workgroup
 // (a.npartials <= G_ROWS_GRID of them): aux_enc_loss = beta V replaces beta BCE in the loss scalars, and the running sums go to v_accum
-// (a.accum is then null)
+// (a.accum is then null); with `kl_partials` (the M1 / M2 and M2_info steps under a weighted KL term: dvae_train_generic_plan_t.kl_weight /
+// kl_floor other than 1 / 0) one more loss sum per rows workgroup, at kl_partials[i * kl_stride]: the KL elements clamped from below at
+// kl_floor.  The ELBO slot becomes fl32(recon + fl32(kl_w * mean)) -- and enc_loss is rebuilt on it --, the recon and KL slots stay the
+// raw means, and the running sums go to kl_accum (a.accum is then null; where v_partials is set too, v_accum takes them behind both).
+// Null -- every other caller -- leaves the finalising workgroup's arithmetic as it is.
 struct GApplyArgs {
     fused::ApplyArgs a;
     GTensor t[G_NT];
@@ -135,6 +139,8 @@ struct GApplyArgs {
     const long long* cnt_partials; int cnt_wgs;
     long long* counts4; long long* cnt_accum;
     const double* v_partials; double* v_accum;
+    const double* kl_partials; double* kl_accum;
+    int kl_stride; float kl_w;
 };
 
 // reduce kernel (train_generic.hip: train_generic_reduce_kernel), between _grads and _apply_flat: flat = [flat +] weight * (the slabs of

@@ -164,7 +164,8 @@ static ILayout make_layout(int y, int z, int h1, int h2, int64_t B, int ksplit_h
     // workspace
     int64_t w = al256(L.wpack_elems * 4);
     L.o_items = w; w = al256(w + (int64_t)L.n_items * sizeof(GItem));
-    L.o_partials = w; w = al256(w + L.rows_grid * (aux_v ? 5 : 4) * sizeof(double));      // the fifth sum (V) behind the [rows_grid][4]
+    // the fifth sum (V) behind the [rows_grid][4]; the clamped KL sums behind whichever comes last (partials_k_off)
+    L.o_partials = w; w = al256(w + L.rows_grid * (aux_v ? 6 : 5) * sizeof(double));
     L.o_stash = w; w = al256(w + L.Bp * (int64_t)L.S * 4);
     L.o_grads = w; w = al256(w + (int64_t)L.nslices * L.n_params * 4);
     L.ws_bytes = w;
@@ -172,6 +173,9 @@ static ILayout make_layout(int y, int z, int h1, int h2, int64_t B, int ksplit_h
     L.lds_bytes = (int64_t)GT * (GXP + L.yp + 2 * L.hm + 3 * L.zp) * 4 + GT * sizeof(int64_t);
     return L;
 }
+
+// the clamped KL sums of the weighted KL term, in doubles from o_partials
+static int64_t partials_k_off(const ILayout& L) { return ((L.mode & (DVAE_INFO_AUX_UNIFORM | DVAE_INFO_AUX_ENTROPY)) ? 5 : 4) * L.rows_grid; }
 
 static void make_tensors(const ILayout& L, GTensor* T) {
     for (int t = 0; t < G_NT; ++t) memset(&T[t], 0, sizeof(GTensor));
@@ -226,6 +230,9 @@ struct IRowsArgs {
     float aux_gamma;                  // gamma: the weight of d BCE in the auxiliary tensors when the adversarial term is not a cross entropy
     double* partials_v;               // [rows_grid] the sums of V (then only)
     int fwd_only;
+    // the weighted KL term (plan->kl_weight w, plan->kl_floor; train_generic.hip: GRowsArgs): kl_scale = fl32(fl32(w) * invB), invB itself at w = 1
+    float kl_scale, kl_floor;
+    double* partials_k;               // [rows_grid] the sums of the KL elements clamped from below at kl_floor
 };
 static_assert(sizeof(ILayout) + sizeof(IRowsArgs) <= G_KERNARG_MAX, "layout and arguments travel as kernel arguments");
 
@@ -239,7 +246,11 @@ static_assert(sizeof(ILayout) + sizeof(IRowsArgs) <= G_KERNARG_MAX, "layout and 
 //   AV  the output layer of the auxiliary net forms two gradients: gamma dBCE - beta dV at weight 1 / B -> X (towards the weights: the
 //       chain that is stashed) and dV at weight 1 / B -> Y (towards z; the labels are done with for this tile).  The weight chain runs
 //       first, then the z chain through the same relu masks, read from the stash; dpre_a1 of the z chain -> X for phase 5.
-template <bool DC, int AV>
+// KLW (plan->kl_weight / kl_floor other than 1 / 0): the weighted KL term as in train_generic_rows_kernel -- kl_scale = w / B on the KL parts
+//   of d mu and d log_var where the element is not below kl_floor, exact zeros below it, and the sums of max(k, kl_floor) in partials_k.
+//   A template flag: the six instantiations without it are the code they were (the compiler spills in three of them when the two
+//   scalars are read at run time: DESIGN 4a''').
+template <bool DC, int AV, bool KLW = false>
 __global__ __launch_bounds__(256) void train_info_rows_kernel(const ILayout L, const IRowsArgs g) {
     extern __shared__ __attribute__((aligned(16))) float ism[];
     float* X = ism;                                     // [528][16] x; dpre_o of the classifier; x again; d loss / d a; a1, dpre_ao, dpre_a1
@@ -256,6 +267,7 @@ __global__ __launch_bounds__(256) void train_info_rows_kernel(const ILayout L, c
     const bool bwd = !g.fwd_only;
     double sum_is = 0.0, sum_kl = 0.0, sum_bc = 0.0, sum_ba = 0.0;
     [[maybe_unused]] double sum_bv = 0.0;                // V, where it is not the cross entropy
+    [[maybe_unused]] double sum_kc = 0.0;               // KLW: the KL elements clamped from below at kl_floor
 
     for (int64_t tile = blockIdx.x; tile < L.tiles; tile += gridDim.x) {
         const int64_t r0 = tile * GT;
@@ -452,10 +464,20 @@ __global__ __launch_bounds__(256) void train_info_rows_kernel(const ILayout L, c
             const float sd = expf(0.5f * lv), ev = expf(lv);
             const float zv = mu + sd * e;
             Bf[j * GT + c] = zv;
-            C[j * GT + c] = ok ? mu * g.invB : 0.f;
-            C[(L.zp + j) * GT + c] = ok ? -0.5f * (1.f - ev) * g.invB : 0.f;
-            C[(2 * L.zp + j) * GT + c] = 0.5f * sd * e;
-            if (ok) sum_kl += (double)(-0.5f * (lv - mu * mu - ev));
+            if constexpr (KLW) {
+                // the KL element and its weight: w / B where it is not below the floor (torch.clamp's gradient), zero below it
+                const float k = -0.5f * (lv - mu * mu - ev);
+                const float ks = (ok && !(k < g.kl_floor)) ? g.kl_scale : 0.f;
+                C[j * GT + c] = ok ? mu * ks : 0.f;
+                C[(L.zp + j) * GT + c] = ok ? -0.5f * (1.f - ev) * ks : 0.f;
+                C[(2 * L.zp + j) * GT + c] = 0.5f * sd * e;
+                if (ok) { sum_kl += (double)k; sum_kc += (double)(k < g.kl_floor ? g.kl_floor : k); }
+            } else {
+                C[j * GT + c] = ok ? mu * g.invB : 0.f;
+                C[(L.zp + j) * GT + c] = ok ? -0.5f * (1.f - ev) * g.invB : 0.f;
+                C[(2 * L.zp + j) * GT + c] = 0.5f * sd * e;
+                if (ok) sum_kl += (double)(-0.5f * (lv - mu * mu - ev));
+            }
             g.stash[(r0 + c) * (int64_t)L.S + L.s_z + j] = zv;
             if constexpr (DC) {
                 if (bwd && j < L.z) g.stash[(r0 + c) * (int64_t)L.S + L.s_zc + j] = zv;     // [z | p_c] for the weight gradient of decoder layer 1
@@ -820,6 +842,13 @@ __global__ __launch_bounds__(256) void train_info_rows_kernel(const ILayout L, c
         __syncthreads();
         if (tid == 0) g.partials_v[blockIdx.x] = ((redv[0] + redv[1]) + redv[2]) + redv[3];
     }
+    if constexpr (KLW) {
+        sum_kc = wave_sum(sum_kc);
+        double* redk = reinterpret_cast<double*>(ism) + 20;
+        if (lane == 0) redk[wave] = sum_kc;
+        __syncthreads();
+        if (tid == 0) g.partials_k[blockIdx.x] = ((redk[0] + redk[1]) + redk[2]) + redk[3];
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -830,6 +859,8 @@ static int plan_layout(const char* who, const dvae_train_info_plan_t* plan, ILay
     DVAE_CHECK_ARG(plan, "%s: null plan", who);
     DVAE_CHECK_ARG(dims_ok(plan->y_dim, plan->z_dim, plan->h1, plan->h2) && plan->B >= 1 && plan->n_tensors == I_NT && mode_ok(plan->info_mode),
                    "%s: not a plan of dvae_train_info_plan", who);
+    DVAE_CHECK_ARG(plan->kl_weight >= 0.0 && isfinite(plan->kl_weight) && plan->kl_floor >= 0.0 && isfinite(plan->kl_floor),
+                   "%s: kl_weight %g / kl_floor %g in the plan (finite numbers >= 0; the planner sets 1 and 0)", who, plan->kl_weight, plan->kl_floor);
     L = make_layout(plan->y_dim, plan->z_dim, plan->h1, plan->h2, plan->B, plan->ksplit, plan->info_mode);
     DVAE_CHECK_ARG(L.ws_bytes == plan->workspace_bytes && L.nslices == plan->ksplit && L.n_params == plan->n_params &&
                    L.slice_frames == plan->slice_frames, "%s: the plan was changed after dvae_train_info_plan", who);
@@ -863,6 +894,16 @@ static ApplyArgs apply_args(const dvae_train_info_plan_t* plan, const ILayout& L
     return a;
 }
 
+// The weighted KL term of a finalising launch (train_generic.hip: weighted_kl).  The plan's defaults (1, 0) leave every argument as it
+// was.  Where the fifth sum is finalised too (MODE_AUX), its block runs last on the rebuilt ELBO and v_accum takes the running sums.
+static bool kl_weighted(const dvae_train_info_plan_t* plan) { return !((float)plan->kl_weight == 1.f && (float)plan->kl_floor == 0.f); }
+static void weighted_kl(const dvae_train_info_plan_t* plan, const ILayout& L, char* ws, GApplyArgs& g) {
+    if (!kl_weighted(plan)) return;
+    const float w = (float)plan->kl_weight;
+    g.kl_partials = (const double*)(ws + L.o_partials) + partials_k_off(L); g.kl_stride = 1; g.kl_w = w;
+    if (!(L.mode & MODE_AUX)) { g.kl_accum = g.a.accum; g.a.accum = nullptr; }
+}
+
 // adam: the optimizer step on every parameter; otherwise only the packed copies are rewritten (elements) and / or the losses finalised
 static int launch_apply(const dvae_train_info_plan_t* plan, const ILayout& L, const ApplyArgs& a, char* ws, bool adam, bool elements, bool finalize,
                         hipStream_t s, const GClipHost* clip = nullptr) {
@@ -876,16 +917,21 @@ static int launch_apply(const dvae_train_info_plan_t* plan, const ILayout& L, co
         g.v_accum = (double*)(uintptr_t)plan->loss_accum;
     }
     g.ws = (float*)ws; g.adam = adam ? 1 : 0; g.finalize = finalize ? 1 : 0;
+    if (finalize) weighted_kl(plan, L, ws, g);
     return clip ? launch_apply_clipped_table(g, *clip, s) : launch_apply_table(g, s);
 }
 
-template <bool DC, int AV>
-static int launch_rows_mode(const ILayout& L, const IRowsArgs& g, hipStream_t s) {
+template <bool DC, int AV, bool KLW>
+static int launch_rows_klw(const ILayout& L, const IRowsArgs& g, hipStream_t s) {
     static bool attr_done[64] = {};                     // (one per instantiation: the limit is a property of the kernel)
-    if (int rc = raise_lds_limit((const void*)train_info_rows_kernel<DC, AV>, "train_info_rows_kernel", L.lds_bytes, attr_done)) return rc;
-    hipLaunchKernelGGL((train_info_rows_kernel<DC, AV>), dim3((unsigned)L.rows_grid), dim3(256), (size_t)L.lds_bytes, s, L, g);
+    if (int rc = raise_lds_limit((const void*)train_info_rows_kernel<DC, AV, KLW>, "train_info_rows_kernel", L.lds_bytes, attr_done)) return rc;
+    hipLaunchKernelGGL((train_info_rows_kernel<DC, AV, KLW>), dim3((unsigned)L.rows_grid), dim3(256), (size_t)L.lds_bytes, s, L, g);
     DVAE_LAUNCH_OK("train_info_rows_kernel");
     return 0;
+}
+template <bool DC, int AV>
+static int launch_rows_mode(const ILayout& L, const IRowsArgs& g, bool klw, hipStream_t s) {
+    return klw ? launch_rows_klw<DC, AV, true>(L, g, s) : launch_rows_klw<DC, AV, false>(L, g, s);
 }
 
 static int launch_rows(const dvae_train_info_plan_t* plan, const ILayout& L, char* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
@@ -901,10 +947,13 @@ static int launch_rows(const dvae_train_info_plan_t* plan, const ILayout& L, cha
     g.aux_w_scale = (float)(plan->info_gamma - plan->info_beta);
     g.aux_gamma = (float)plan->info_gamma;
     g.partials_v = g.partials + 4 * L.rows_grid;
+    g.partials_k = g.partials + partials_k_off(L);
+    g.kl_scale = (float)plan->kl_weight * g.invB; g.kl_floor = (float)plan->kl_floor;        // (read by the KLW instantiations)
     const bool dc = (L.mode & DVAE_INFO_DEC_CLASSIFIER) != 0;
     const int av = (L.mode & DVAE_INFO_AUX_UNIFORM) ? 1 : ((L.mode & DVAE_INFO_AUX_ENTROPY) ? 2 : 0);
-    if (!dc) return av == 0 ? launch_rows_mode<false, 0>(L, g, s) : (av == 1 ? launch_rows_mode<false, 1>(L, g, s) : launch_rows_mode<false, 2>(L, g, s));
-    return av == 0 ? launch_rows_mode<true, 0>(L, g, s) : (av == 1 ? launch_rows_mode<true, 1>(L, g, s) : launch_rows_mode<true, 2>(L, g, s));
+    const bool klw = kl_weighted(plan);
+    if (!dc) return av == 0 ? launch_rows_mode<false, 0>(L, g, klw, s) : (av == 1 ? launch_rows_mode<false, 1>(L, g, klw, s) : launch_rows_mode<false, 2>(L, g, klw, s));
+    return av == 0 ? launch_rows_mode<true, 0>(L, g, klw, s) : (av == 1 ? launch_rows_mode<true, 1>(L, g, klw, s) : launch_rows_mode<true, 2>(L, g, klw, s));
 }
 
 static int launch_wgrad(const dvae_train_info_plan_t* plan, const ILayout& L, char* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
@@ -947,6 +996,7 @@ extern "C" int dvae_train_info_plan_mode(int y_dim, int z_dim, int h1, int h2, i
     plan->workspace_bytes = L.ws_bytes; plan->grad_offset_bytes = L.o_grads; plan->Bp = L.Bp; plan->rows_grid = L.rows_grid;
     plan->slice_frames = L.slice_frames; plan->wgrad_items = L.n_items; plan->lds_bytes = L.lds_bytes;
     plan->info_alpha = 0.0; plan->info_beta = 10.0; plan->info_gamma = 1.0;        // scripts/training_M2_info_vad.py:53-55
+    plan->kl_weight = 1.0; plan->kl_floor = 0.0;
     return 0;
 }
 
@@ -971,7 +1021,7 @@ extern "C" int dvae_train_info_init(const dvae_train_info_plan_t* plan, const fl
     const std::vector<GItem> items = make_items(gm, order, I_NG, L.nslices);
     DVAE_CHECK_ARG((int)items.size() == L.n_items, "train_info_init: %d items for a table of %d", (int)items.size(), L.n_items);
     DVAE_HIP(hipMemcpyAsync((char*)ws + L.o_items, items.data(), items.size() * sizeof(GItem), hipMemcpyHostToDevice, s));
-    DVAE_HIP(hipMemsetAsync((char*)ws + L.o_partials, 0, (size_t)L.rows_grid * ((L.mode & MODE_AUX) ? 5 : 4) * sizeof(double), s));
+    DVAE_HIP(hipMemsetAsync((char*)ws + L.o_partials, 0, (size_t)L.rows_grid * ((L.mode & MODE_AUX) ? 6 : 5) * sizeof(double), s));
     DVAE_HIP(hipStreamSynchronize(s));                                      // the table leaves host memory that ends with this call
     return dvae_train_info_repack(plan, params, ws, stream);
 }
@@ -1011,6 +1061,7 @@ extern "C" int dvae_train_info_reduce(const dvae_train_info_plan_t* plan, void* 
         g.f.v_accum = (double*)(uintptr_t)plan->loss_accum;
     }
     g.f.ws = (float*)ws; g.f.finalize = 1;
+    weighted_kl(plan, L, (char*)ws, g.f);
     g.flat = flat; g.accumulate = accumulate; g.weight = weight;
     return launch_reduce_table(g, (hipStream_t)stream);
 }

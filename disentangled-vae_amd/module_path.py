@@ -35,7 +35,8 @@ takes one Function per nn.Linear by default, as it always did.  With the switch 
               + weight-gradient kernel + reduce into one flat gradient                                               (3 launches)
 
 within `trainer_generic.covered`: M1 / M2, x 513, y 0..513, two hidden widths 1..512, z 1..128, no flow.  Any loss written in torch on
-(r, z, mu, log_var) -- a weighted or warmed-up KL term, free bits, a regulariser on z -- becomes the upstream gradients of that one
+(r, z, mu, log_var) -- a weighted or warmed-up KL term, free bits (the fused steps take those too, per element: kl_weight.py; the
+batch-mean form lives here), a regulariser on z -- becomes the upstream gradients of that one
 backward.  The switch:
     DVAE_MODULE_GENERIC unset / 0   off: every call keeps the path and the bits it had
     DVAE_MODULE_GENERIC=1           on for the sizes the resident engine does not serve

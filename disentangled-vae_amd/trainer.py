@@ -67,7 +67,11 @@ class Trainer:
 
     def __init__(self, model, dims, params=None, batch=128, device="cuda:0", precision="fp32", lr=1e-4, betas=(0.9, 0.999),
                  adam_eps=1e-8, elbo_eps=1e-8, process_group=None, world=1, ksplit=0, seed=None, alpha=0.0, beta=10.0, gamma=1.0,
-                 share=None, direct_exchange=None):
+                 share=None, direct_exchange=None, kl_weight=None, kl_warmup=None, kl_floor=None):
+        if kl_weight is not None or kl_warmup is not None or kl_floor is not None:
+            raise NotImplementedError("kl_weight / kl_warmup / kl_floor exist on the generic step only (trainer_generic.GenericTrainer, "
+                                      "trainer_info.InfoTrainer; make_trainer / make_info_trainer choose it when one of them is given): the "
+                                      "resident step's kernels carry the unweighted KL term")
         if not torch.cuda.is_available():
             raise RuntimeError("Trainer needs the MI355X HIP path (no CPU fallback)")
         if not supported(model, dims):
@@ -498,31 +502,42 @@ class Trainer:
         return {n: (ms[i], calls[i]) for i, n in enumerate(names)}
 
 
-def trainer_kind(model, dims, std_norm=False):
+def trainer_kind(model, dims, std_norm=False, kl_weight=None, kl_warmup=None, kl_floor=None):
     """Which fused train step serves (model, dims): "resident" (the hand-tuned kernels of the reference's geometry, supported()),
     "generic" (csrc/train_generic.hip: M1 / M2, x 513, y_dim 0 / 1..513, two hidden widths 1..512, z_dim 1..128, fp32) or None.
-    The resident step has no standardised encoder input, so std_norm goes to the generic step at the reference geometry too (None
-    for M2_info: no fused step offers it there).  Host logic only."""
+    The resident step has no standardised encoder input and no weighted KL term, so std_norm, and any of kl_weight / kl_warmup /
+    kl_floor other than 1 / 0 / 0 (kl_weight.py), go to the generic step at the reference geometry too (None for M2_info: no fused
+    step offers std_norm there).  Host logic only."""
+    from . import kl_weight as KL
     from . import trainer_generic as G
     try:
-        if not std_norm and supported(model, dims):
+        if not std_norm and KL.is_default(kl_weight, kl_warmup, kl_floor) and supported(model, dims):
             return "resident"
     except KeyError:                    # a dims dict without one of the keys names no geometry of the resident step
         pass
     return "generic" if G.covered(model, dims) else None
 
 
-def make_trainer(model, dims, generic=False, std_norm=None, norm_eps=1e-8, **kw):
+def make_trainer(model, dims, generic=False, std_norm=None, norm_eps=1e-8, kl_weight=None, kl_warmup=None, kl_floor=None, **kw):
     """A Trainer where supported() holds (the default there: it is the faster step), otherwise a GenericTrainer; raises with the limits
-    named when neither covers (model, dims).  generic=True puts the reference geometry on the generic step too, and so does
-    std_norm=(mean, std) (GenericTrainer), which only the generic M1 / M2 step offers."""
+    named when neither covers (model, dims).  generic=True puts the reference geometry on the generic step too, and so do
+    std_norm=(mean, std) and a weighted KL term (kl_weight / kl_warmup / kl_floor other than 1 / 0 / 0: kl_weight.py), which only the
+    generic M1 / M2 step offers."""
+    from . import kl_weight as KL
     from . import trainer_generic as G
+    klw = not KL.is_default(kl_weight, kl_warmup, kl_floor)
+    if klw:
+        kw.update(zip(("kl_weight", "kl_warmup", "kl_floor"), KL.check_options(1.0 if kl_weight is None else kl_weight, kl_warmup or 0,
+                                                                                kl_floor or 0.0, "make_trainer")))
+        if not G.covered(model, dims):
+            raise NotImplementedError(f"kl_weight / kl_warmup / kl_floor exist on the generic M1 / M2 step only; {G.LIMITS}; got {model} {dims}")
+        generic = True
     if std_norm is not None:
         if not G.covered(model, dims):
             raise NotImplementedError(f"std_norm exists on the generic M1 / M2 step only; {G.LIMITS}; got {model} {dims}")
         generic = True
         kw.update(std_norm=std_norm, norm_eps=norm_eps)
-    kind = trainer_kind(model, dims, std_norm is not None)
+    kind = trainer_kind(model, dims, std_norm is not None or klw)
     if kind is None:
         raise NotImplementedError(f"no fused train step for {model} {dims}: the resident step covers M1 / M2 (y 1 or 513) / M2_info (y 1) at "
                                   f"x 513, z 16, h [128, 128]; {G.LIMITS}")

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import clip
+from . import kl_weight as KL
 from . import native as N
 from .trainer import MAXT, MODEL_CODE, PREC_CODE, TENSOR_NAMES
 
@@ -27,7 +28,7 @@ class GenericPlan(ctypes.Structure):
                 ("Bp", ctypes.c_int64), ("rows_grid", ctypes.c_int64), ("slice_frames", ctypes.c_int64), ("wgrad_items", ctypes.c_int64),
                 ("lds_bytes", ctypes.c_int64), ("loss_accum", ctypes.c_uint64), ("row_index", ctypes.c_uint64), ("row_count", ctypes.c_int64),
                 ("bad_row_counter", ctypes.c_uint64), ("std_norm", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("norm_mean", ctypes.c_uint64),
-                ("norm_div", ctypes.c_uint64)]
+                ("norm_div", ctypes.c_uint64), ("kl_weight", ctypes.c_double), ("kl_floor", ctypes.c_double)]
 
 
 def covered(model, dims):
@@ -93,9 +94,15 @@ def make_plan(model, dims, batch, precision="fp32", ksplit=0, std_norm=False):
     return plan
 
 
-class GenericTrainer:
+class GenericTrainer(KL.KLOptions):
     """One object = one model replica on one GPU.  step(x, y, eps_noise) enqueues one full train step and returns a device tensor
     [ELBO, recon, KL] (no host sync).
+
+    kl_weight, kl_warmup, kl_floor (kl_weight.py): the objective is recon + w_s * mean_b sum_j max(k_bj, kl_floor) with
+    w_s = kl_weight * min(1, s / kl_warmup) at optimizer step s; the ELBO slot is that objective, the recon and KL slots stay the raw
+    means; evaluate() uses the target kl_weight.  The defaults (1, 0, 0) are the unweighted step, bit for bit.  kl_weight may be
+    reassigned between steps, kl_weight_next is the weight the next optimizer step will use; forks share the options and the schedule;
+    none of the three is part of state_dict().
 
     std_norm=(mean, std) (513 floats each; check_std_norm) is the scripts' switch of that name: the encoder reads
     [(x - mean) / (std + norm_eps) | y], the float32 bits of torch's expression, while the loss is scored against the raw x
@@ -103,7 +110,9 @@ class GenericTrainer:
     are data of the train set, read back with .std_norm."""
 
     def __init__(self, model, dims, params=None, batch=128, device="cuda:0", lr=1e-4, betas=(0.9, 0.999), adam_eps=1e-8, elbo_eps=1e-8,
-                 seed=None, ksplit=0, share=None, precision="fp32", world=1, std_norm=None, norm_eps=1e-8):
+                 seed=None, ksplit=0, share=None, precision="fp32", world=1, std_norm=None, norm_eps=1e-8, kl_weight=1.0, kl_warmup=0,
+                 kl_floor=0.0):
+        KL.check_options(kl_weight, kl_warmup, kl_floor, "GenericTrainer")      # ValueError before anything touches the device
         if int(world) != 1:
             raise NotImplementedError(f"data-parallel training is not built on the generic step ({LIMITS}); got world={world}: wrap a "
                                       "one-GPU trainer per rank in accumulate.AccumulatedStep(trainer, process_group)")
@@ -130,6 +139,7 @@ class GenericTrainer:
                 self._shared = {"step_count": 0, "version": 0}
             else:                       # same parameters / Adam state, another batch size (see fork())
                 self._params, self._m, self._v, self._shared = share._params, share._m, share._v, share._shared
+            self._kl_init(kl_weight, kl_warmup, kl_floor, share)
             self.ws = torch.empty(self.plan.workspace_bytes, dtype=torch.uint8, device=self.device)
             self.losses = torch.zeros(3, dtype=torch.float32, device=self.device)
             self.bad_rows = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -311,6 +321,7 @@ class GenericTrainer:
         x, y, yp, ldy, eps_noise = self._inputs(x, y, eps_noise)
         self._shared["version"] += 1
         self._copy_version = self._shared["version"]
+        self._kl_plan(self.step_count)
         with torch.cuda.device(self.device):
             N.check(self.lib.dvae_train_generic_step(ctypes.byref(self.plan), N.ptr(self._params), N.ptr(self._m), N.ptr(self._v), N.ptr(self.ws),
                                                      N.ptr(x), N.ld(x), yp, ldy, N.ptr(eps_noise), self.elbo_eps, self.step_count, self.lr,
@@ -328,6 +339,7 @@ class GenericTrainer:
             eps_noise = self.noise((1 << 40) + self._shared["eval_count"])
         x, y, yp, ldy, eps_noise = self._inputs(x, y, eps_noise)
         out = torch.zeros_like(self.losses)
+        self._kl_plan(None)                             # the target weight: validation curves are comparable across epochs
         with torch.cuda.device(self.device):
             N.check(self.lib.dvae_train_generic_eval(ctypes.byref(self.plan), N.ptr(self.ws), N.ptr(x), N.ld(x), yp, ldy, N.ptr(eps_noise),
                                                      self.elbo_eps, N.ptr(out), N.stream()), "dvae_train_generic_eval")
@@ -339,6 +351,7 @@ class GenericTrainer:
         self._check_inputs(x, y, None, eps_noise)
         self._sync_copies()
         x, y, yp, ldy, eps_noise = self._inputs(x, y, eps_noise)
+        self._kl_plan(self.step_count + 1)
         with torch.cuda.device(self.device):
             N.check(self.lib.dvae_train_generic_grads(ctypes.byref(self.plan), N.ptr(self.ws), N.ptr(x), N.ld(x), yp, ldy, N.ptr(eps_noise),
                                                       self.elbo_eps, N.stream()), "dvae_train_generic_grads")
@@ -350,6 +363,7 @@ class GenericTrainer:
         self._check_inputs(x, y, rows, eps_noise)
         self._sync_copies()
         x, y, yp, ldy, eps_noise = self._inputs(x, y, eps_noise)
+        self._kl_plan(self.step_count + 1)              # the weight of the optimizer step this micro-batch ends in
         with torch.cuda.device(self.device):
             N.check(self.lib.dvae_train_generic_grads(ctypes.byref(self.plan), N.ptr(self.ws), N.ptr(x), N.ld(x), yp, ldy, N.ptr(eps_noise),
                                                       self.elbo_eps, N.stream()), "dvae_train_generic_grads")

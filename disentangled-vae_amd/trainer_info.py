@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import clip
+from . import kl_weight as KL
 from . import native as N
 from .trainer import INFO_NAMES, MAXT, Trainer, supported
 
@@ -35,7 +36,8 @@ class InfoPlan(ctypes.Structure):
                 ("tensor_cols", ctypes.c_int32 * MAXT), ("workspace_bytes", ctypes.c_int64), ("grad_offset_bytes", ctypes.c_int64),
                 ("Bp", ctypes.c_int64), ("rows_grid", ctypes.c_int64), ("slice_frames", ctypes.c_int64), ("wgrad_items", ctypes.c_int64),
                 ("lds_bytes", ctypes.c_int64), ("info_alpha", ctypes.c_double), ("info_beta", ctypes.c_double), ("info_gamma", ctypes.c_double),
-                ("loss_accum", ctypes.c_uint64), ("row_index", ctypes.c_uint64), ("row_count", ctypes.c_int64), ("bad_row_counter", ctypes.c_uint64)]
+                ("loss_accum", ctypes.c_uint64), ("row_index", ctypes.c_uint64), ("row_count", ctypes.c_int64), ("bad_row_counter", ctypes.c_uint64),
+                ("kl_weight", ctypes.c_double), ("kl_floor", ctypes.c_double)]
 
 
 def covered(dims):
@@ -78,16 +80,23 @@ def make_plan(dims, batch, ksplit=0, dec_label="truth", aux_enc="bce"):
     return plan
 
 
-class InfoTrainer:
+class InfoTrainer(KL.KLOptions):
     """One object = one M2_info replica on one GPU.  step(x, y, eps_noise) enqueues one full train step and returns the device tensor
-    [ELBO, recon, KL, enc_loss, classif_loss, aux_loss, aux_enc_loss, 0] (no host sync)."""
+    [ELBO, recon, KL, enc_loss, classif_loss, aux_loss, aux_enc_loss, 0] (no host sync).
+
+    kl_weight, kl_warmup, kl_floor (kl_weight.py; `beta` is the adversarial weight here): the ELBO of the VAE body is
+    recon + w_s * mean_b sum_j max(k_bj, kl_floor), in the ELBO slot and inside enc_loss; the recon and KL slots stay the raw means;
+    evaluate() uses the target kl_weight.  The defaults (1, 0, 0) are the unweighted step, bit for bit; forks share the options and
+    the schedule; they are not part of state_dict()."""
 
     model = "M2_info"
 
     def __init__(self, dims, params=None, batch=128, device="cuda:0", lr=1e-4, betas=(0.9, 0.999), adam_eps=1e-8, elbo_eps=1e-8,
-                 alpha=0.0, beta=10.0, gamma=1.0, seed=None, ksplit=0, share=None, dec_label="truth", aux_enc="bce", std_norm=None):
+                 alpha=0.0, beta=10.0, gamma=1.0, seed=None, ksplit=0, share=None, dec_label="truth", aux_enc="bce", std_norm=None,
+                 kl_weight=1.0, kl_warmup=0, kl_floor=0.0):
         if std_norm is not None:
             raise NotImplementedError(STD_NORM_REFUSAL)
+        KL.check_options(kl_weight, kl_warmup, kl_floor, "InfoTrainer")         # ValueError before anything touches the device
         self.plan = make_plan(dims, batch, ksplit, dec_label, aux_enc)      # refuses before anything touches the device
         self.dec_label, self.aux_enc = dec_label, aux_enc
         self.plan.info_alpha, self.plan.info_beta, self.plan.info_gamma = float(alpha), float(beta), float(gamma)
@@ -112,6 +121,7 @@ class InfoTrainer:
                 self._shared = {"step_count": 0, "version": 0}
             else:                       # same parameters / Adam state, another batch size (see fork())
                 self._params, self._m, self._v, self._shared = share._params, share._m, share._v, share._shared
+            self._kl_init(kl_weight, kl_warmup, kl_floor, share)
             self.ws = torch.empty(self.plan.workspace_bytes, dtype=torch.uint8, device=self.device)
             self.losses = torch.zeros(8, dtype=torch.float32, device=self.device)
             self.bad_rows = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -276,6 +286,7 @@ class InfoTrainer:
         x, y, eps_noise = self._inputs(x, y, eps_noise)
         self._shared["version"] += 1
         self._copy_version = self._shared["version"]
+        self._kl_plan(self.step_count)
         with torch.cuda.device(self.device):
             N.check(self.lib.dvae_train_info_step(ctypes.byref(self.plan), N.ptr(self._params), N.ptr(self._m), N.ptr(self._v), N.ptr(self.ws),
                                                   N.ptr(x), N.ld(x), N.ptr(y), N.ld(y), N.ptr(eps_noise), self.elbo_eps, self.step_count, self.lr,
@@ -293,6 +304,7 @@ class InfoTrainer:
             eps_noise = self.noise((1 << 40) + self._shared["eval_count"])
         x, y, eps_noise = self._inputs(x, y, eps_noise)
         out = torch.zeros_like(self.losses)
+        self._kl_plan(None)                             # the target weight: validation curves are comparable across epochs
         with torch.cuda.device(self.device):
             N.check(self.lib.dvae_train_info_eval(ctypes.byref(self.plan), N.ptr(self.ws), N.ptr(x), N.ld(x), N.ptr(y), N.ld(y), N.ptr(eps_noise),
                                                   self.elbo_eps, N.ptr(out), N.stream()), "dvae_train_info_eval")
@@ -304,6 +316,7 @@ class InfoTrainer:
         self._check_inputs(x, y, None, eps_noise)
         self._sync_copies()
         x, y, eps_noise = self._inputs(x, y, eps_noise)
+        self._kl_plan(self.step_count + 1)
         with torch.cuda.device(self.device):
             N.check(self.lib.dvae_train_info_grads(ctypes.byref(self.plan), N.ptr(self.ws), N.ptr(x), N.ld(x), N.ptr(y), N.ld(y), N.ptr(eps_noise),
                                                    self.elbo_eps, N.stream()), "dvae_train_info_grads")
@@ -315,6 +328,7 @@ class InfoTrainer:
         self._check_inputs(x, y, rows, eps_noise)
         self._sync_copies()
         x, y, eps_noise = self._inputs(x, y, eps_noise)
+        self._kl_plan(self.step_count + 1)              # the weight of the optimizer step this micro-batch ends in
         with torch.cuda.device(self.device):
             N.check(self.lib.dvae_train_info_grads(ctypes.byref(self.plan), N.ptr(self.ws), N.ptr(x), N.ld(x), N.ptr(y), N.ld(y), N.ptr(eps_noise),
                                                    self.elbo_eps, N.stream()), "dvae_train_info_grads")
@@ -357,11 +371,12 @@ STD_NORM_REFUSAL = ("std_norm exists on the generic M1 / M2 step only (trainer_g
                     "read one x tile, and the reference's M2_info script loads the statistics without using them; " + LIMITS)
 
 
-def info_trainer_kind(dims, dec_label="truth", aux_enc="bce"):
+def info_trainer_kind(dims, dec_label="truth", aux_enc="bce", kl_weight=None, kl_warmup=None, kl_floor=None):
     """Which fused train step serves M2_info at `dims`: "resident" (the hand-tuned kernels of the reference's geometry,
     trainer.supported), "generic" (csrc/train_info.hip) or None.  The resident step has the default options only, so any other
-    goes to the generic step at the reference geometry too.  Host logic only."""
-    default = mode_bits(dec_label, aux_enc) == 0
+    -- a weighted KL term included (kl_weight / kl_warmup / kl_floor other than 1 / 0 / 0) -- goes to the generic step at the
+    reference geometry too.  Host logic only."""
+    default = mode_bits(dec_label, aux_enc) == 0 and KL.is_default(kl_weight, kl_warmup, kl_floor)
     try:
         if default and supported("M2_info", dims):
             return "resident"
@@ -370,14 +385,19 @@ def info_trainer_kind(dims, dec_label="truth", aux_enc="bce"):
     return "generic" if covered(dims) else None
 
 
-def make_info_trainer(dims, generic=False, dec_label="truth", aux_enc="bce", std_norm=None, **kw):
+def make_info_trainer(dims, generic=False, dec_label="truth", aux_enc="bce", std_norm=None, kl_weight=None, kl_warmup=None, kl_floor=None,
+                      **kw):
     """The resident Trainer("M2_info", ...) where trainer.supported holds (the default there: the faster step, the 16-bit operand policies,
-    data-parallel training), otherwise an InfoTrainer; generic=True, or an option other than dec_label="truth" / aux_enc="bce", puts the
-    reference geometry on the generic step too.  Raises with the limits named when neither covers `dims`, and for a 16-bit policy or
+    data-parallel training), otherwise an InfoTrainer; generic=True, an option other than dec_label="truth" / aux_enc="bce", or a
+    weighted KL term (kl_weight / kl_warmup / kl_floor other than 1 / 0 / 0: kl_weight.py) puts the reference geometry on the generic
+    step too.  Raises with the limits named when neither covers `dims`, and for a 16-bit policy or
     world != 1 on the generic step; ValueError naming the choices for an unknown option, before anything touches the device."""
     if std_norm is not None:
         raise NotImplementedError(STD_NORM_REFUSAL)
-    kind = info_trainer_kind(dims, dec_label, aux_enc)
+    if not KL.is_default(kl_weight, kl_warmup, kl_floor):
+        kw.update(zip(("kl_weight", "kl_warmup", "kl_floor"), KL.check_options(1.0 if kl_weight is None else kl_weight, kl_warmup or 0,
+                                                                                kl_floor or 0.0, "make_info_trainer")))
+    kind = info_trainer_kind(dims, dec_label, aux_enc, kl_weight, kl_warmup, kl_floor)
     if kind is None or (generic and not covered(dims)):
         raise NotImplementedError(f"no fused M2_info train step for {dims}: the resident step covers x 513, z 16, h [128, 128], y 1; {LIMITS}")
     if kind == "resident" and not generic:

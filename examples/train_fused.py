@@ -217,6 +217,12 @@ def main():
     ap.add_argument("--std-norm", action="store_true",
                     help="M1 / M2 (generic step): standardise the encoder input with the train split's per-bin mean and standard deviation, "
                          "from --h5 where the file has them, else computed on the device; writes norm.pt beside the checkpoints")
+    ap.add_argument("--kl-weight", type=float, default=1.0, metavar="W",
+                    help="generic steps: the objective is recon + W * KL (a beta-VAE weight; W >= 0); the log's Recon. and KL stay raw")
+    ap.add_argument("--kl-warmup", type=int, default=0, metavar="N",
+                    help="generic steps: the KL weight rises linearly to --kl-weight over the first N optimizer steps")
+    ap.add_argument("--kl-floor", type=float, default=0.0, metavar="L",
+                    help="generic steps: free bits per element, max(k, L) for every element k of the KL term (its minimum is 0.5)")
     a = ap.parse_args()
     if a.std_norm and a.model == "M2_info":
         ap.error("--std-norm applies to --model M1 / M2 (the reference's M2_info script loads the statistics without using them)")
@@ -256,6 +262,9 @@ def main():
     kw = dict(batch=min(a.batch, len(train)), precision=a.precision, lr=a.lr, seed=a.seed, device=device)
     if accumulated or a.clip_norm is not None:
         kw["generic"] = True                        # accumulation, data parallelism of this kind and clipping are built on the generic steps
+    kl_options = (a.kl_weight, a.kl_warmup, a.kl_floor) != (1.0, 0, 0.0)
+    if kl_options:                                  # a weighted KL term goes to the generic steps too (ValueError for a negative value)
+        kw.update(kl_weight=a.kl_weight, kl_warmup=a.kl_warmup, kl_floor=a.kl_floor)
     if a.model == "M2_info":                        # the resident step at the reference geometry, csrc/train_info.hip at any other covered size
         tr = make_info_trainer(dims, alpha=a.alpha, beta=a.beta, gamma=a.gamma, dec_label=a.decoder_label, aux_enc=a.aux_enc, **kw)
         if a.init_classifier:
@@ -291,7 +300,8 @@ def main():
         os.makedirs(a.out, exist_ok=True)
         open(os.path.join(a.out, "output_epoch.log"), "w").close()
     log(f"{a.model} {dims}: {len(train)} training frames, {len(valid)} validation frames, batch {tr.B}, {a.precision}, {type(tr).__name__}"
-        + (f", {a.accumulate} micro-batches a step on each of {world} rank(s)" if accumulated else ""))
+        + (f", {a.accumulate} micro-batches a step on each of {world} rank(s)" if accumulated else "")
+        + (f", KL weight {a.kl_weight:g} after {a.kl_warmup} warm-up steps, floor {a.kl_floor:g}" if kl_options else ""))
     for epoch in range(a.epochs):
         torch.cuda.synchronize(); t0 = time.perf_counter()
         if accumulated:
@@ -307,6 +317,8 @@ def main():
         if clip is not None:                        # (read once per epoch, on every rank: the counter is each replica's own)
             norm, skipped = clip.read()
             clipped = ", grad norm: {:.3f} (clipped to {:g}), skipped steps: {}".format(norm, a.clip_norm, skipped)
+        if kl_options:                              # the train ELBO is the weighted objective, the validation ELBO the target weight's
+            clipped += ", KL weight: {:.4f} (step {})".format(tr.kl_weight_next, tr.step_count)
         if rank != 0:                               # rank 0 writes logs and checkpoints
             continue
         lines = [f"Epoch: {epoch}",

@@ -213,6 +213,16 @@ typedef struct {
     int32_t  reserved0;
     uint64_t norm_mean;
     uint64_t norm_div;
+    /* The weighted KL term; the planners set 1 and 0, the caller may overwrite both before any call (finite, >= 0; not part of the layout).
+       With k_bj = -0.5 (lv_bj - mu_bj^2 - exp(lv_bj)) the element of the reference's KL (its minimum is 0.5), the objective is
+           loss = recon + kl_weight * mean_b sum_j max(k_bj, kl_floor)
+       with torch.clamp(k, min=kl_floor)'s gradient: the KL parts of d mu and d log_var are fl32(fl32(kl_weight) / B) times mu and
+       -0.5 (1 - e^lv) where k_bj >= kl_floor and exact zeros below (the per-element form of free bits; kl_floor <= 0.5 clamps nothing).
+       losses3 = {the objective, recon, KL}: recon and KL stay the raw, unweighted, unclamped means.  _grads, _reduce, _apply, _step and
+       _eval read the fields at each call; a warm-up is the caller writing kl_weight before a step.  (1, 0) is the unweighted step, bit
+       for bit.  The module entry points do not read them: their upstream gradients carry the loss. */
+    double   kl_weight;
+    double   kl_floor;
 } dvae_train_generic_plan_t;
 
 /* Host only.  ksplit_hint 0 = choose.  DVAE_E_UNSUPPORTED for M2_info / M2_DEC and the bf16 policies (they exist at the reference geometry
@@ -236,7 +246,8 @@ int dvae_train_generic_repack(const dvae_train_generic_plan_t* plan, const float
  * eps_noise [B, z_dim] (required).  The gradient of the mean loss over the B frames is left as plan->ksplit slabs. */
 int dvae_train_generic_grads(const dvae_train_generic_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
                              const float* eps_noise, float elbo_eps, void* stream);
-/* apply kernel: g = grad_scale * (slabs summed in slab order); Adam at `step` (1-based); packed copies; losses3 = {recon + KL, recon, KL}.
+/* apply kernel: g = grad_scale * (slabs summed in slab order); Adam at `step` (1-based); packed copies; losses3 = {recon + KL, recon, KL}
+ * (under plan->kl_weight / kl_floor other than 1 / 0: {recon + kl_weight * the clamped KL, recon, KL}, see the plan).
  * Separate from _grads so that a gradient exchange can sit between them. */
 int dvae_train_generic_apply(const dvae_train_generic_plan_t* plan, float* params, float* m, float* v, void* ws, int step, double lr,
                              double beta1, double beta2, double adam_eps, double grad_scale, float* losses3, void* stream);
@@ -453,6 +464,10 @@ typedef struct {
     uint64_t row_index;
     int64_t  row_count;
     uint64_t bad_row_counter;
+    /* The weighted KL term of the VAE body, as in dvae_train_generic_plan_t (the planners set 1 and 0; read at each call): the ELBO of
+       losses8[0], and of enc_loss in losses8[3], is recon + kl_weight * mean_b sum_j max(k_bj, kl_floor); losses8[1], [2] stay raw. */
+    double   kl_weight;
+    double   kl_floor;
 } dvae_train_info_plan_t;
 
 /* Host only (callable without a GPU).  ksplit_hint 0 = choose.  DVAE_E_BADARG naming the limits for a size outside them. */
