@@ -1,5 +1,5 @@
 """Gradient accumulation and data parallelism for the fused train steps of any covered size (GenericTrainer, ClassifierTrainer,
-InfoTrainer of any mode; include/dvae_train.h: dvae_train_*_reduce / _apply_flat; csrc/train_generic.hip: train_generic_reduce_kernel).
+InfoTrainer of any mode; include/dvae_train.h: dvae_train_*_reduce / _apply_flat; csrc/train_tables.hip: train_generic_reduce_kernel).
 
 One optimizer step = K micro-batches and one apply:
 

@@ -1,5 +1,5 @@
 """Global-norm gradient clipping on the device for the fused train steps of any covered size (include/dvae_train.h:
-dvae_train_*_apply_flat_clipped; csrc/train_generic.hip: train_generic_gradnorm_kernel, train_generic_apply_clipped_kernel): what
+dvae_train_*_apply_flat_clipped; csrc/train_tables.hip: train_generic_gradnorm_kernel, train_generic_apply_clipped_kernel): what
 GenericTrainer, ClassifierTrainer and InfoTrainer share.  The semantics are torch.nn.utils.clip_grad_norm_(parameters, max_norm) over all
 tensors of the plan at once; a gradient whose sum of squares is not finite skips the update and is counted (DESIGN 4a'''').  The state
 -- scratch of the norm launch, [total_norm, coef], the skip counter, the flat gradient of step(max_norm=...) -- lives in the trainer's

@@ -4,7 +4,8 @@
 // binary_cross_entropy (packages/models/utils.py:55-56, eps inside the logs), backward, Adam, the confusion counts of y_hat > 0.5.
 // Limits: x 513, h1 / h2 1..512, y_dim 1..513 -- those of mlp_generic.hip, which runs the trained classifier.
 //
-// The design is train_generic.hip's; its weight-gradient and apply kernels serve this step through the tables of train_generic.hpp:
+// The design is train_generic.hip's; the weight-gradient and apply kernels of train_tables.hip serve this step through its tables, and the
+// host path around the launches is train_step_host.hpp's (CStep below describes this step to it):
 //   * rows kernel (here): 256 threads own a tile of 16 frames; products on v_mfma_f32_16x16x4_f32 from packed copies in fragment order
 //     (tg_gemm).  c1 = relu(x W1^T + b1), c2 = relu(c1 W2^T + b2), a = c2 Wo^T + bo, p = 1 / (1 + exp(-a)); the row loss
 //     -sum_j [y log(p + eps) + (1 - y) log(1 - p + eps)]; d loss / d p = -(1 / B) (y / (p + eps) - (1 - y) / (1 - p + eps)) with the eps
@@ -21,7 +22,7 @@
 #include <vector>
 #include "common.hpp"
 #include "../../include/dvae_train.h"
-#include "train_generic.hpp"
+#include "train_step_host.hpp"
 
 namespace dvae {
 namespace tc {
@@ -293,82 +294,57 @@ __global__ __launch_bounds__(256) void train_clf_rows_kernel(const CLayout L, co
 // host
 static const char* LIMITS = "the classifier train step covers Classifier([513, [h1, h2], y_dim]) at x 513, hidden widths 1..512, y_dim 1..513, exact fp32, one GPU";
 
-static int plan_layout(const char* who, const dvae_train_clf_plan_t* plan, CLayout& L) {
-    DVAE_CHECK_ARG(plan, "%s: null plan", who);
-    DVAE_CHECK_ARG(plan->precision == DVAE_PREC_F32 && dims_ok(plan->h1, plan->h2, plan->y_dim) && plan->B >= 1, "%s: not a plan of dvae_train_clf_plan", who);
-    L = make_layout(plan->h1, plan->h2, plan->y_dim, plan->B, plan->ksplit);
-    DVAE_CHECK_ARG(L.ws_bytes == plan->workspace_bytes && L.nslices == plan->ksplit && L.n_params == plan->n_params &&
-                   L.slice_frames == plan->slice_frames, "%s: the plan was changed after dvae_train_clf_plan", who);
-    return 0;
-}
+// the classifier step as train_step_host.hpp reads it
+struct CStep {
+    using Plan = dvae_train_clf_plan_t;
+    using Layout = CLayout;
+    static constexpr int NT = C_NT, NG = C_NG;
+    static constexpr int ORDER[C_NG] = {0, 1, 2};                           // layer 1 first: 513 input columns
+    static constexpr bool COUNTS = true, WGRAD_Y = false;
 
-static int check_inputs(const char* who, const dvae_train_clf_plan_t* plan, const void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy) {
-    DVAE_CHECK_ARG(ws && x && y, "%s: null pointer", who);
-    DVAE_CHECK_ARG(ldx >= GX && ldx < ((int64_t)1 << 20), "%s: leading dimension of x %lld (at least 513)", who, (long long)ldx);
-    DVAE_CHECK_ARG(ldy >= plan->y_dim && ldy < ((int64_t)1 << 20), "%s: leading dimension of y %lld for y_dim %d", who, (long long)ldy, plan->y_dim);
-    DVAE_CHECK_ARG(!plan->row_index || plan->row_count >= 1, "%s: a gather table needs row_count >= 1 (got %lld)", who, (long long)plan->row_count);
-    return 0;
-}
-
-static ApplyArgs apply_args(const dvae_train_clf_plan_t* plan, const CLayout& L, float* params, float* m, float* v, char* ws, bool adam, int step,
-                            double lr, double beta1, double beta2, double adam_eps, double grad_scale, float* losses3) {
-    ApplyArgs a;
-    memset(&a, 0, sizeof(a));
-    a.p = params; a.m = m; a.v = v;
-    a.slabs = (const float*)(ws + L.o_grads); a.slab_stride = L.n_params; a.nslabs = L.nslices;
-    a.n_params = L.n_params;
-    if (adam) {
-        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-        a.one_minus_b1 = (float)(1.0 - beta1); a.b2 = (float)beta2; a.one_minus_b2 = (float)(1.0 - beta2);
-        a.step_size = (float)(lr / bc1); a.bc2_sqrt = (float)sqrt(bc2); a.eps = (float)adam_eps; a.gscale = (float)grad_scale;
+    static int plan_layout(const char* who, const Plan* plan, CLayout& L, bool) {
+        DVAE_CHECK_ARG(plan, "%s: null plan", who);
+        DVAE_CHECK_ARG(plan->precision == DVAE_PREC_F32 && dims_ok(plan->h1, plan->h2, plan->y_dim) && plan->B >= 1, "%s: not a plan of dvae_train_clf_plan", who);
+        L = make_layout(plan->h1, plan->h2, plan->y_dim, plan->B, plan->ksplit);
+        DVAE_CHECK_ARG(L.ws_bytes == plan->workspace_bytes && L.nslices == plan->ksplit && L.n_params == plan->n_params &&
+                       L.slice_frames == plan->slice_frames, "%s: the plan was changed after dvae_train_clf_plan", who);
+        return 0;
     }
-    a.partials = (const double*)(ws + L.o_partials); a.npartials = (int)L.rows_grid; a.B = L.B; a.losses3 = losses3;
-    a.accum = (double*)(uintptr_t)plan->loss_accum;
-    return a;
-}
 
-// adam: the optimizer step on every parameter; otherwise only the packed copies are rewritten (elements) and / or the loss and counts finalised
-static int launch_apply(const dvae_train_clf_plan_t* plan, const CLayout& L, const ApplyArgs& a, char* ws, bool adam, bool elements, bool finalize,
-                        long long* counts4, hipStream_t s, const GClipHost* clip = nullptr) {
-    GApplyArgs g;
-    memset(&g, 0, sizeof(g));
-    g.a = a;
-    if (!elements) g.a.n_params = 0;
-    make_tensors(L, g.t);
-    g.ws = (float*)ws; g.adam = adam ? 1 : 0; g.finalize = finalize ? 1 : 0;
-    if (finalize) {
+    static int check_inputs(const char* who, const Plan* plan, const void* ws, const StepInputs& in) {
+        DVAE_CHECK_ARG(ws && in.x && in.y, "%s: null pointer", who);
+        DVAE_CHECK_ARG(in.ldx >= GX && in.ldx < ((int64_t)1 << 20), "%s: leading dimension of x %lld (at least 513)", who, (long long)in.ldx);
+        DVAE_CHECK_ARG(in.ldy >= plan->y_dim && in.ldy < ((int64_t)1 << 20), "%s: leading dimension of y %lld for y_dim %d", who, (long long)in.ldy,
+                       plan->y_dim);
+        DVAE_CHECK_ARG(!plan->row_index || plan->row_count >= 1, "%s: a gather table needs row_count >= 1 (got %lld)", who, (long long)plan->row_count);
+        return 0;
+    }
+
+    static int launch_rows(const Plan* plan, const CLayout& L, char* ws, const StepInputs& in, bool fwd_only, hipStream_t s) {
+        static bool attr_done[64] = {};
+        if (int rc = raise_lds_limit((const void*)train_clf_rows_kernel, "train_clf_rows_kernel", L.lds_bytes, attr_done)) return rc;
+        CRowsArgs g;
+        memset(&g, 0, sizeof(g));
+        g.x = in.x; g.ldx = in.ldx; g.y = in.y; g.ldy = in.ldy;
+        g.row_index = (const int64_t*)(uintptr_t)plan->row_index; g.row_count = plan->row_count; g.bad = (int*)(uintptr_t)plan->bad_row_counter;
+        g.ws = (float*)ws; g.stash = (float*)(ws + L.o_stash); g.partials = (double*)(ws + L.o_partials); g.counts = (long long*)(ws + L.o_counts);
+        g.bce_eps = in.loss_eps; g.invB = (float)(1.0 / (double)L.B); g.fwd_only = fwd_only ? 1 : 0;
+        hipLaunchKernelGGL(train_clf_rows_kernel, dim3((unsigned)L.rows_grid), dim3(256), (size_t)L.lds_bytes, s, L, g);
+        DVAE_LAUNCH_OK("train_clf_rows_kernel");
+        return 0;
+    }
+
+    static void tensors(const CLayout& L, GTensor* T) { make_tensors(L, T); }
+    static void gemms(const CLayout& L, GGemm* G) { make_gemms(L, G); }
+    static size_t partials_bytes(const CLayout& L) { return (size_t)(L.o_stash - L.o_partials); }      // loss and count partials
+    static void extend_apply_args(const Plan*, const CLayout&, ApplyArgs&) {}
+    // a finalising launch sums the confusion counts too
+    static void extend_table(const Plan* plan, const CLayout& L, char* ws, long long* counts4, GApplyArgs& g) {
+        if (!g.finalize) return;
         g.cnt_partials = (const long long*)(ws + L.o_counts); g.cnt_wgs = (int)L.rows_grid; g.counts4 = counts4;
         g.cnt_accum = (long long*)(uintptr_t)plan->count_accum;
     }
-    return clip ? launch_apply_clipped_table(g, *clip, s) : launch_apply_table(g, s);
-}
-
-static int launch_rows(const dvae_train_clf_plan_t* plan, const CLayout& L, char* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
-                       float bce_eps, bool fwd_only, hipStream_t s) {
-    static bool attr_done[64] = {};
-    if (int rc = raise_lds_limit((const void*)train_clf_rows_kernel, "train_clf_rows_kernel", L.lds_bytes, attr_done)) return rc;
-    CRowsArgs g;
-    memset(&g, 0, sizeof(g));
-    g.x = x; g.ldx = ldx; g.y = y; g.ldy = ldy;
-    g.row_index = (const int64_t*)(uintptr_t)plan->row_index; g.row_count = plan->row_count; g.bad = (int*)(uintptr_t)plan->bad_row_counter;
-    g.ws = (float*)ws; g.stash = (float*)(ws + L.o_stash); g.partials = (double*)(ws + L.o_partials); g.counts = (long long*)(ws + L.o_counts);
-    g.bce_eps = bce_eps; g.invB = (float)(1.0 / (double)L.B); g.fwd_only = fwd_only ? 1 : 0;
-    hipLaunchKernelGGL(train_clf_rows_kernel, dim3((unsigned)L.rows_grid), dim3(256), (size_t)L.lds_bytes, s, L, g);
-    DVAE_LAUNCH_OK("train_clf_rows_kernel");
-    return 0;
-}
-
-static int launch_wgrad(const dvae_train_clf_plan_t* plan, const CLayout& L, char* ws, const float* x, int64_t ldx, hipStream_t s) {
-    GWgradArgs g;
-    memset(&g, 0, sizeof(g));
-    g.x = x; g.ldx = ldx;                               // (no label columns: y_w 0 in every matrix)
-    g.row_index = (const int64_t*)(uintptr_t)plan->row_index; g.row_count = plan->row_count;
-    g.stash = (const float*)(ws + L.o_stash); g.slabs = (float*)(ws + L.o_grads); g.slab_stride = L.n_params;
-    g.B = L.B; g.slice_frames = L.slice_frames; g.items = (const GItem*)(ws + L.o_items); g.S = L.S;
-    make_gemms(L, g.gm);
-    for (int t = 0; t < C_NT; ++t) g.toff[t] = L.toff[t];
-    return launch_wgrad_table(g, L.n_items, s);
-}
+};
 
 }  // namespace tc
 }  // namespace dvae
@@ -398,109 +374,52 @@ extern "C" int dvae_train_clf_plan(int h1, int h2, int y_dim, int precision, int
     return 0;
 }
 
+// the entry points: train_step_host.hpp under this step's description (no noise: eps null; the loss's eps is bce_eps)
 extern "C" int dvae_train_clf_repack(const dvae_train_clf_plan_t* plan, const float* params, void* ws, void* stream) {
-    CLayout L;
-    if (int rc = plan_layout("train_clf_repack", plan, L)) return rc;
-    DVAE_CHECK_ARG(params && ws, "train_clf_repack: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    DVAE_HIP(hipMemsetAsync(ws, 0, (size_t)L.wpack_elems * 4, s));          // the padding of the packed copies
-    const ApplyArgs a = apply_args(plan, L, (float*)params, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, nullptr);
-    return launch_apply(plan, L, a, (char*)ws, false, true, false, nullptr, s);
+    return step_repack<CStep>("train_clf_repack", plan, params, ws, stream);
 }
 
 extern "C" int dvae_train_clf_init(const dvae_train_clf_plan_t* plan, const float* params, void* ws, void* stream) {
-    CLayout L;
-    if (int rc = plan_layout("train_clf_init", plan, L)) return rc;
-    DVAE_CHECK_ARG(params && ws, "train_clf_init: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    GGemm gm[C_NG];
-    make_gemms(L, gm);
-    const int order[C_NG] = {0, 1, 2};                                      // layer 1 first: 513 input columns
-    const std::vector<GItem> items = make_items(gm, order, C_NG, L.nslices);
-    DVAE_CHECK_ARG((int)items.size() == L.n_items, "train_clf_init: %d items for a table of %d", (int)items.size(), L.n_items);
-    DVAE_HIP(hipMemcpyAsync((char*)ws + L.o_items, items.data(), items.size() * sizeof(GItem), hipMemcpyHostToDevice, s));
-    DVAE_HIP(hipMemsetAsync((char*)ws + L.o_partials, 0, (size_t)(L.o_stash - L.o_partials), s));      // loss and count partials
-    DVAE_HIP(hipStreamSynchronize(s));                                      // the table leaves host memory that ends with this call
-    return dvae_train_clf_repack(plan, params, ws, stream);
+    return step_init<CStep>("train_clf_init", plan, params, ws, stream);
 }
 
 extern "C" int dvae_train_clf_grads(const dvae_train_clf_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
                                     float bce_eps, void* stream) {
-    CLayout L;
-    if (int rc = plan_layout("train_clf_grads", plan, L)) return rc;
-    if (int rc = check_inputs("train_clf_grads", plan, ws, x, ldx, y, ldy)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = launch_rows(plan, L, (char*)ws, x, ldx, y, ldy, bce_eps, false, s)) return rc;
-    return launch_wgrad(plan, L, (char*)ws, x, ldx, s);
+    return step_grads<CStep>("train_clf_grads", plan, ws, {x, ldx, y, ldy, nullptr, bce_eps}, stream);
 }
 
 extern "C" int dvae_train_clf_apply(const dvae_train_clf_plan_t* plan, float* params, float* m, float* v, void* ws, int step, double lr,
                                     double beta1, double beta2, double adam_eps, double grad_scale, float* losses3, int64_t* counts4, void* stream) {
-    CLayout L;
-    if (int rc = plan_layout("train_clf_apply", plan, L)) return rc;
-    DVAE_CHECK_ARG(params && m && v && ws && losses3 && counts4, "train_clf_apply: null pointer");
-    DVAE_CHECK_ARG(step >= 1, "train_clf_apply: step %d (1-based)", step);
-    const ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, losses3);
-    return launch_apply(plan, L, a, (char*)ws, true, true, true, (long long*)counts4, (hipStream_t)stream);
+    return step_apply<CStep>("train_clf_apply", plan, {params, m, v, step, lr, beta1, beta2, adam_eps, grad_scale}, ws, {losses3, (long long*)counts4}, stream);
 }
 
 extern "C" int dvae_train_clf_reduce(const dvae_train_clf_plan_t* plan, void* ws, float* flat, int accumulate, float weight, float* losses3,
                                      int64_t* counts4, void* stream) {
-    CLayout L;
-    if (int rc = plan_layout("train_clf_reduce", plan, L)) return rc;
-    if (int rc = check_reduce_args("train_clf_reduce", ws, flat, accumulate, weight)) return rc;
-    DVAE_CHECK_ARG(losses3 && counts4, "train_clf_reduce: null pointer");
-    GReduceArgs g;
-    memset(&g, 0, sizeof(g));
-    g.f.a = apply_args(plan, L, nullptr, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, losses3);
-    make_tensors(L, g.f.t);
-    g.f.ws = (float*)ws; g.f.finalize = 1;
-    g.f.cnt_partials = (const long long*)((char*)ws + L.o_counts); g.f.cnt_wgs = (int)L.rows_grid; g.f.counts4 = (long long*)counts4;
-    g.f.cnt_accum = (long long*)(uintptr_t)plan->count_accum;
-    g.flat = flat; g.accumulate = accumulate; g.weight = weight;
-    return launch_reduce_table(g, (hipStream_t)stream);
+    return step_reduce<CStep>("train_clf_reduce", plan, ws, flat, accumulate, weight, {losses3, (long long*)counts4}, stream);
 }
 
 extern "C" int dvae_train_clf_apply_flat(const dvae_train_clf_plan_t* plan, float* params, float* m, float* v, void* ws, const float* flat, int step,
                                          double lr, double beta1, double beta2, double adam_eps, double grad_scale, void* stream) {
-    CLayout L;
-    if (int rc = plan_layout("train_clf_apply_flat", plan, L)) return rc;
-    if (int rc = check_apply_flat_args("train_clf_apply_flat", params, m, v, ws, flat, step, lr, grad_scale)) return rc;
-    ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, nullptr);
-    a.slabs = flat; a.nslabs = 1;                       // the flat gradient is the one slab
-    return launch_apply(plan, L, a, (char*)ws, true, true, false, nullptr, (hipStream_t)stream);
+    return step_apply_flat<CStep>("train_clf_apply_flat", plan, {params, m, v, step, lr, beta1, beta2, adam_eps, grad_scale}, ws, flat, nullptr, stream);
 }
 
 extern "C" int dvae_train_clf_apply_flat_clipped(const dvae_train_clf_plan_t* plan, float* params, float* m, float* v, void* ws, const float* flat,
                                                  int step, double lr, double beta1, double beta2, double adam_eps, double grad_scale,
                                                  double max_norm, void* scratch, float* norm2_out, int32_t* skipped_counter, void* stream) {
-    CLayout L;
-    if (int rc = plan_layout("train_clf_apply_flat_clipped", plan, L)) return rc;
-    if (int rc = check_apply_flat_args("train_clf_apply_flat_clipped", params, m, v, ws, flat, step, lr, grad_scale)) return rc;
     const GClipHost clip = {grad_scale, max_norm, scratch, norm2_out, skipped_counter};
-    if (int rc = check_clip_args("train_clf_apply_flat_clipped", flat, clip)) return rc;
-    ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, nullptr);
-    a.slabs = flat; a.nslabs = 1;                       // the flat gradient is the one slab
-    return launch_apply(plan, L, a, (char*)ws, true, true, false, nullptr, (hipStream_t)stream, &clip);
+    return step_apply_flat<CStep>("train_clf_apply_flat_clipped", plan, {params, m, v, step, lr, beta1, beta2, adam_eps, grad_scale}, ws, flat, &clip,
+                                  stream);
 }
 
 extern "C" int dvae_train_clf_step(const dvae_train_clf_plan_t* plan, float* params, float* m, float* v, void* ws, const float* x, int64_t ldx,
                                    const float* y, int64_t ldy, float bce_eps, int step, double lr, double beta1, double beta2, double adam_eps,
                                    float* losses3, int64_t* counts4, void* stream) {
-    DVAE_CHECK_ARG(params && m && v && losses3 && counts4, "train_clf_step: null pointer");
-    DVAE_CHECK_ARG(step >= 1, "train_clf_step: step %d (1-based)", step);
-    if (int rc = dvae_train_clf_grads(plan, ws, x, ldx, y, ldy, bce_eps, stream)) return rc;
-    return dvae_train_clf_apply(plan, params, m, v, ws, step, lr, beta1, beta2, adam_eps, 1.0, losses3, counts4, stream);
+    return step_step<CStep>("train_clf_step", "train_clf_grads", "train_clf_apply", plan, {params, m, v, step, lr, beta1, beta2, adam_eps, 1.0}, ws,
+                            {x, ldx, y, ldy, nullptr, bce_eps}, {losses3, (long long*)counts4}, stream);
 }
 
 extern "C" int dvae_train_clf_eval(const dvae_train_clf_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
                                    float bce_eps, float* losses3, int64_t* counts4, void* stream) {
-    CLayout L;
-    if (int rc = plan_layout("train_clf_eval", plan, L)) return rc;
-    if (int rc = check_inputs("train_clf_eval", plan, ws, x, ldx, y, ldy)) return rc;
-    DVAE_CHECK_ARG(losses3 && counts4, "train_clf_eval: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = launch_rows(plan, L, (char*)ws, x, ldx, y, ldy, bce_eps, true, s)) return rc;
-    const ApplyArgs a = apply_args(plan, L, nullptr, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, losses3);
-    return launch_apply(plan, L, a, (char*)ws, false, false, true, (long long*)counts4, s);
+    return step_eval<CStep>("train_clf_eval", plan, ws, {x, ldx, y, ldy, nullptr, bce_eps}, {losses3, (long long*)counts4}, stream);
 }
+

@@ -14,16 +14,9 @@
 //     pre-activation gradient goes to the stash ([frame][S] floats, 16-byte stores straight from the accumulators) for the weight
 //     gradients anyway, and the thread that wrote h reads it back where tanh' needs it.
 //     Frames past B carry zero pre-activation gradients and finite activations; padded units carry zeros throughout.
-//   * weight-gradient kernel: one launch for the seven matrices and their biases, dW = dPre^T in over the frames on the same MFMA
-//     (k = frames), driven by a host-built table of (matrix, 64-row output group, four 64-column blocks, frame slice) items; a wave
-//     keeps a 64 x 64 block of dW in sixteen accumulators.  x and y are read from the caller's memory (through the gather table when
-//     there is one); the bias is the product with a column of ones.  Every item writes its blocks of its slice's slab: no atomics,
-//     and the same inputs give the same bits.
-//   * apply kernel: one thread per parameter: slab sum in slab order, adam_element (apply_common.hpp), both packed copies refreshed,
-//     loss scalars finalised from the rows kernel's per-workgroup sums (and added to the optional float64 accumulator).
-//   * reduce kernel (gradient accumulation, data parallelism): the slabs of a micro-batch summed into one flat gradient; and, for
-//     global-norm clipping on the device, a norm kernel over that flat gradient (per-chunk sums of squares in double, fixed order) in
-//     front of a guarded instantiation of the apply kernel's body (train_generic.hpp: GNormArgs / GClipArgs).
+//   * weight-gradient, apply, reduce and norm kernels: train_tables.hip, which the M2_info and the classifier step launch too; here one
+//     weight-gradient launch covers the seven matrices and their biases.  The host path around the launches is train_step_host.hpp's,
+//     shared with those two steps; this file describes the step to it (MStep).
 //   * module modes of the rows kernel (dvae_module_generic_forward / _backward; module_path.py: GenericModuleEngine): the forward chain
 //     with the model's outputs written, and the backward chain started from upstream gradients of (r, z, mu, log_var) in the place of
 //     the ELBO's -- the drop-in modules' forward as ONE autograd Function under the caller's own loss and optimizer.
@@ -36,15 +29,38 @@
 #include <vector>
 #include "common.hpp"
 #include "../../include/dvae_train.h"
-#include "apply_common.hpp"
-#include "train_generic.hpp"
+#include "train_step_host.hpp"
 
 namespace dvae {
 namespace tg {
 
-using fused::ApplyArgs;
+struct GLayout {
+    int y, z, h1, h2, yp, zp, h1p, h2p, hm;     // sizes and their multiples of 16 (yp 0 without labels); hm = max(h1p, h2p, zp)
+    int dec;                                    // M2_DEC (dvae_module_generic_plan): the encoder reads x alone.  In the four bytes that padded hm: no other field moves
+    // packed copies, float offsets from the start of the workspace: forward [out tile][k block], x / z block and label block apart;
+    // the heads are one matrix (mu rows 0 .. z - 1, log_var rows zp .. zp + z - 1)
+    int64_t W1x, W1y, W2, Wh, D1z, D1y, D2, D3;
+    int64_t D3T, D2T, D1zT, WhT, W2T;           // the transposed copies of the backward-data products
+    int64_t b1, b2, bh, bd1, bd2, bd3;          // zero-padded biases
+    int64_t wpack_elems;
+    // the stash of one frame (floats): layer inputs, then the pre-activation gradients
+    int S, s_h1e, s_h2e, s_z, s_d1, s_d2, s_pe1, s_pe2, s_ph, s_pd1, s_pd2, s_da;
+    // workspace (bytes)
+    int64_t o_items, o_partials, o_stash, o_grads, ws_bytes;
+    int64_t B, Bp, tiles, rows_grid, slice_frames, n_params;
+    int nslices, n_items;
+    int64_t lds_bytes;
+    int64_t toff[G_NT];
+    int trows[G_NT], tcols[G_NT];
+    // std_norm (dvae_train_generic_plan_norm): encoder layer 1 reads the standardised x; its stash block of GXP columns sits behind s_da, so
+    // every other column, S and the workspace of a plan without std_norm are what they are without these two fields
+    int norm, s_xn;
+};
+
+static_assert(offsetof(GLayout, W1x) == 40 && offsetof(GLayout, dec) == 36, "dec sits in the padding behind hm: the kernel arguments of the train step do not move");
+
 static void make_gemms(const GLayout& L, GGemm* G);
-constexpr int M_NT = 14, M_NG = 7;               // this step's share of the tables (G_NT / G_NG entries: train_generic.hpp)
+constexpr int M_NT = 14, M_NG = 7;               // this step's share of the tables (G_NT / G_NG entries: train_tables.hpp)
 
 static bool dims_ok(int y, int z, int h1, int h2) {
     return y >= 0 && y <= GX && h1 >= 1 && h1 <= G_HMAX && h2 >= 1 && h2 <= G_HMAX && z >= 1 && z <= G_ZMAX;
@@ -185,7 +201,6 @@ struct GModuleArgs {
     const float* g_mu; const float* g_lv; const float* g_z;       // [B][z]
 };
 constexpr int ROWS_STEP = 0, ROWS_MODULE_FWD = 1, ROWS_MODULE_BWD = 2;
-struct __attribute__((packed, aligned(4))) G4U { f32x4 v; };      // 16 bytes at dword alignment (rows of 513 floats)
 
 // NORM (std_norm): encoder layer 1 reads xn = fl32(fl32(x - mean) / div) in the place of x -- the tile holds xn, which also goes to the
 // stash block s_xn for the weight gradient of that layer --, and the output layer takes the raw x of its loss terms from the caller's
@@ -563,513 +578,90 @@ __global__ __launch_bounds__(256) void train_generic_rows_kernel(const GLayout L
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// weight-gradient kernel (GWgradArgs: train_generic.hpp; the classifier step launches it too)
-// One item = 64 rows of one matrix (four 16-row tiles of dPre) x four 64-column blocks of its input (the bias is one more block behind
-// them), one block a wave, x one frame slice.  A wave keeps a 64 x 64 block of dW in 16 accumulators: per four frames it loads one dPre value
-// per row tile (a quarter wave reads 16 consecutive floats of a frame) and ONE 16-byte piece of the input row -- columns 4 j .. 4 j + 3 of
-// the block, so column tile c holds the block's columns 4 j + c, j = 0 .. 15 -- for sixteen MFMAs.
-__global__ __launch_bounds__(256) void train_generic_wgrad_kernel(const GWgradArgs g) {
-    const GItem it = g.items[blockIdx.x];
-    const GGemm m = g.gm[it.gemm];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int j = lane & 15, quad = lane >> 4;
-    const int64_t f0 = (int64_t)it.slice * g.slice_frames;
-    const int64_t f1 = f0 + g.slice_frames < g.B ? f0 + g.slice_frames : g.B;
-    const int nb0 = (m.in_w + 63) >> 6, nb1 = (m.y_w + 63) >> 6, nb = nb0 + nb1 + 1;
-    const int nrt = m.nrt - 4 * it.rt < 4 ? m.nrt - 4 * it.rt : 4;           // row tiles of this item (it.rt counts 64-row groups)
-    const float* dp = g.stash + m.dpre + 64 * it.rt + j;
-    float* slab = g.slabs + (int64_t)it.slice * g.slab_stride;
-    const int cb = it.cb0 + wave;                       // the wave's 64-column block
-    if (cb < nb) {
-        // the block's source: rows of `ld` floats at `base` with `w` valid columns, this lane's four from c4; output columns from ocol
-        const bool bias = cb == nb0 + nb1, lab = !bias && cb >= nb0;
-        const bool gather = g.row_index && (lab || m.in_kind == 0);
-        const float* base = lab ? g.y : (m.in_kind == 0 ? g.x : g.stash + m.in_off);
-        const int64_t ld = lab ? g.ldy : (m.in_kind == 0 ? g.ldx : (int64_t)g.S);
-        const int w = bias ? 1 : (lab ? m.y_w : m.in_w), ocol = lab ? m.in_w : 0;
-        const int c4 = 64 * (lab ? cb - nb0 : (bias ? 0 : cb)) + 4 * j;
-        const int ntc = w - (c4 - 4 * j) < 4 ? w - (c4 - 4 * j) : 4;          // column tiles with a valid column
-        const int nv = w - c4 < 0 ? 0 : (w - c4 > 4 ? 4 : w - c4);            // this lane's valid columns
-        f32x4 acc[4][4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc[r][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-        // the operands of the four frames from f: frame f + quad; past the slice: zeros
-        auto load = [&](int64_t f, float (&a)[4], f32x4& b) __attribute__((always_inline)) {
-            const int64_t fr = f + quad;
-            const bool ok = fr < f1;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) a[r] = (ok && r < nrt) ? dp[fr * g.S + 16 * r] : 0.f;
-            b = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (bias) {
-                b[0] = 1.f;
-            } else if (ok && nv > 0) {
-                int64_t s = fr;
-                if (gather) {
-                    s = g.row_index[fr];
-                    if (s < 0 || s >= g.row_count) s = 0;
-                }
-                const float* p = base + s * ld + c4;
-                if (nv == 4) b = reinterpret_cast<const G4U*>(p)->v;
-                else { b[0] = p[0]; if (nv > 1) b[1] = p[1]; if (nv > 2) b[2] = p[2]; }
-            }
-        };
-        float a[4], an[4];
-        f32x4 b, bn;
-        load(f0, a, b);
-        for (int64_t f = f0; f < f1; f += 4) {
-            load(f + 4, an, bn);                        // requested before this round's MFMAs (all zeros past the slice)
-            if (nrt == 4 && ntc == 4) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) acc[r][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], b[c], acc[r][c], 0, 0, 0);
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c)
-                        if (r < nrt && c < ntc) acc[r][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], b[c], acc[r][c], 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) a[r] = an[r];
-            b = bn;
-        }
-#pragma unroll
-        for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = 64 * it.rt + 16 * rt + 4 * quad + r;
-                    if (rt >= nrt || row >= m.rows || c >= nv) continue;
-                    if (bias) {
-                        if (j == 0) slab[g.toff[m.bt] + row] = acc[rt][c][r];
-                    } else {
-                        slab[g.toff[m.wt] + (int64_t)row * m.cols + ocol + c4 + c] = acc[rt][c][r];
-                    }
-                }
-    }
-}
-
-// the finalising workgroup of the apply and reduce launches: loss scalars, the classifier's counts, the M2_info fifth sum (256 threads,
-// every thread calls)
-__device__ __forceinline__ void finalize_step(const GApplyArgs& g, double (*red)[4]) {
-    fused::finalize_losses(g.a, red);
-    if (g.cnt_partials && threadIdx.x < 4) {            // integers, workgroup order
-        long long c = 0;
-        for (int i = 0; i < g.cnt_wgs; ++i) c += g.cnt_partials[4 * (int64_t)i + threadIdx.x];
-        g.counts4[threadIdx.x] = c;
-        if (g.cnt_accum) g.cnt_accum[threadIdx.x] += c;
-    }
-    if (g.kl_partials) {                                // the weighted KL term: one partial a thread, then waves in order, as below
-        __syncthreads();                                // write_losses has read `red`
-        double v = (int)threadIdx.x < g.a.npartials ? g.kl_partials[(int64_t)threadIdx.x * g.kl_stride] : 0.0;
-        v = wave_sum(v);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][0] = v;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-#pragma clang fp contract(off)
-            const float kc = (float)((red[0][0] + red[1][0] + red[2][0] + red[3][0]) / (double)g.a.B);
-            const float wk = g.kl_w * kc;
-            g.a.losses3[0] = g.a.losses3[1] + wk;                            // the objective: recon + w mean sum max(k, floor); [1], [2] stay raw
-            if (g.a.info) g.a.losses3[3] = g.a.losses3[0] + g.a.losses3[4] - g.a.losses3[6];
-            if (g.kl_accum) for (int q = 0; q < (g.a.info ? 8 : 3); ++q) g.kl_accum[q] += (double)g.a.losses3[q];
-        }
-    }
-    if (g.v_partials) {                                 // one partial a thread: workgroup order within a wave's sum, waves in order
-        static_assert(G_ROWS_GRID <= 256, "one thread of the finalising workgroup per rows workgroup");
-        __syncthreads();                                // write_losses has read `red`
-        double v = (int)threadIdx.x < g.a.npartials ? g.v_partials[threadIdx.x] : 0.0;
-        v = wave_sum(v);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][0] = v;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const float bv = (float)((red[0][0] + red[1][0] + red[2][0] + red[3][0]) / (double)g.a.B);
-            const float aux_enc = g.a.beta * bv;
-            g.a.losses3[3] = g.a.losses3[0] + g.a.losses3[4] - aux_enc;      // enc_loss = ELBO + classif_loss - beta V
-            g.a.losses3[6] = aux_enc;
-            if (g.v_accum) for (int q = 0; q < 8; ++q) g.v_accum[q] += (double)g.a.losses3[q];
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// apply kernel: optimizer step, both packed copies, loss scalars (GApplyArgs: train_generic.hpp; the classifier step launches it too,
-// with its confusion counts to finalise)
-// CLIP (the guarded form, train_generic_apply_clipped_kernel): `ga` is g.a with the effective scale in gscale; the element arithmetic
-// is the same code either way
-template <bool CLIP>
-__device__ __forceinline__ void apply_body(const GApplyArgs& g, const ApplyArgs& ga, double (*red)[4]) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx < g.a.n_params) {
-        int t = -1;
-#pragma unroll
-        for (int k = 0; k < G_NT; ++k)
-            if (idx >= g.t[k].off && idx < g.t[k].off + (int64_t)g.t[k].rows * g.t[k].cols) t = k;
-        if (t >= 0) {
-            const GTensor d = g.t[t];
-            float pi = g.a.p[idx];
-            if (g.adam) {
-                const float gi = fused::slab_sum_at(g.a, idx);
-                float mi, vi;
-                fused::adam_element(CLIP ? ga : g.a, pi, g.a.m[idx], g.a.v[idx], gi, mi, vi);
-                g.a.p[idx] = pi; g.a.m[idx] = mi; g.a.v[idx] = vi;
-            }
-            const int i = (int)(idx - d.off);
-            const int r = i / d.cols, c = i - r * d.cols;
-            if (d.bias) {
-                g.ws[d.f0 + d.roff + r] = pi;
-            } else {
-                if (c < d.split) g.ws[d.f0 + frag_pos(r + d.roff, c, d.kb0)] = pi;
-                else g.ws[d.f1 + frag_pos(r + d.roff, c - d.split, d.kb1)] = pi;
-                if (d.t0 >= 0 && c < d.tcmax) g.ws[d.t0 + frag_pos(c, r + d.tkoff, d.tkb)] = pi;
-                if (d.tkb1 > 0 && c >= d.split) g.ws[d.t1 + frag_pos(c - d.split, r, d.tkb1)] = pi;
-            }
-        }
-    }
-    if (g.finalize && blockIdx.x == 0) finalize_step(g, red);
-}
-
-__global__ __launch_bounds__(256) void train_generic_apply_kernel(const GApplyArgs g) {
-    __shared__ double red[4][4];
-    apply_body<false>(g, g.a, red);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// global-norm clipping (GNormArgs / GClipArgs: train_generic.hpp).  The norm kernel: one workgroup a chunk of G_NORM_CHUNK floats.
-__global__ __launch_bounds__(256) void train_generic_gradnorm_kernel(const GNormArgs g) {
-    __shared__ double wsum[4];
-    const int64_t base = (int64_t)blockIdx.x * G_NORM_CHUNK;
-    f32x4 v[4];
-    int i4[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {                       // every load before the first addition; n_params is a multiple of 4 below 2^31
-        const int64_t i = base + ((int64_t)j * 256 + threadIdx.x) * 4;
-        i4[j] = (int)i;
-        v[j] = i < g.n_params ? *reinterpret_cast<const f32x4*>(g.flat + i) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    double s = 0.0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        int nv = 0;                                     // this piece's floats that belong to a tensor (the reduce kernel's rule)
-#pragma unroll
-        for (int k = 0; k < G_NT; ++k)
-            if ((unsigned)(i4[j] - g.off[k]) < (unsigned)g.cnt[k]) nv = g.off[k] + g.cnt[k] - i4[j];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (q < nv) s += (double)v[j][q] * (double)v[j][q];       // address order; the square is exact in double
-    }
-    s = wave_sum(s);                                    // lanes: the same tree on every lane
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) g.partials[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];       // waves in order
-}
-
-// The guarded apply kernel.  Every workgroup forms the same s from the same partials in the same order (a few hundred doubles from L2),
-// so every workgroup takes the same branch: return without a store (s not finite), or the element loop of the apply kernel under
-// gscale_eff = fl32(grad_scale * coef).  coef == 1 leaves fl32(grad_scale): the unguarded kernel's bits.
-__global__ __launch_bounds__(256) void train_generic_apply_clipped_kernel(const GApplyArgs g, const GClipArgs c) {
-    __shared__ double red[4][4];
-    __shared__ double wsum[4];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < c.nchunks; i += 256) s += c.partials[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    s = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-    const bool ok = isfinite(s);                        // (workgroup- and grid-uniform)
-    const double total_norm = fabs(c.grad_scale) * sqrt(s);
-    const double coef = ok ? fmin(1.0, c.max_norm / (total_norm + 1e-6)) : 0.0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        c.norm2_out[0] = (float)total_norm;
-        c.norm2_out[1] = (float)coef;
-        if (!ok) *c.skipped += 1;                       // launches of a stream are ordered: no atomic needed
-    }
-    if (!ok) return;
-    ApplyArgs ga = g.a;
-    ga.gscale = (float)(c.grad_scale * coef);           // formed in double, rounded once
-    apply_body<true>(g, ga, red);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// reduce kernel (GReduceArgs: train_generic.hpp): the frame-slice slabs of one micro-batch summed into the flat gradient accumulator, for
-// gradient accumulation (reduce K times, apply once) and data parallelism (reduce, all-reduce, apply).  A thread owns four consecutive
-// floats: every 16-byte slab load (and the accumulator's, when it is read) is issued before the first addition, the additions run in
-// slab order -- fused::slab_sum_at's order, element for element --, then weight * sum (its own rounding: 1.0 leaves the bits alone),
-// then accumulator + that, one 16-byte store.  No atomics, and no LDS outside the finalising workgroup: the same inputs give the same
-// bits.  With accumulate 0 the accumulator is written and never read; the alignment gaps between tensors receive zeros in every call,
-// whatever the slabs hold there.  The workgroup behind the last block of elements finalises the micro-batch's loss scalars.
-template <int NS>
-__device__ __forceinline__ f32x4 slab_sum4(const float* slabs, int64_t stride, int64_t i4) {
-    f32x4 part[NS];
-#pragma unroll
-    for (int k = 0; k < NS; ++k) part[k] = *reinterpret_cast<const f32x4*>(slabs + k * stride + i4);       // independent loads
-    f32x4 t = part[0];
-#pragma unroll
-    for (int k = 1; k < NS; ++k) t += part[k];                                                              // fixed order
-    return t;
-}
-
-__global__ __launch_bounds__(256) void train_generic_reduce_kernel(const GReduceArgs g) {
-    __shared__ double red[4][4];
-    if (blockIdx.x == gridDim.x - 1) {                  // (workgroup-uniform)
-        if (g.f.finalize) finalize_step(g.f, red);
-        return;
-    }
-    const int64_t i4 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i4 >= g.f.a.n_params) return;                   // (n_params is a multiple of 64)
-    int nv = 0;                                         // this thread's floats that belong to a tensor; the others are the gap behind it
-    const int i = (int)i4;                              // (the 26 tensors hold far fewer than 2^31 floats: 32-bit compares, a third of the ALU work)
-#pragma unroll
-    for (int k = 0; k < G_NT; ++k) {
-        const int off = (int)g.f.t[k].off, n = g.f.t[k].rows * g.f.t[k].cols;     // (unused entries: n = 0)
-        if ((unsigned)(i - off) < (unsigned)n) nv = off + n - i < 4 ? off + n - i : 4;
-    }
-    f32x4 old = {0.f, 0.f, 0.f, 0.f};
-    if (g.accumulate) old = *reinterpret_cast<const f32x4*>(g.flat + i4);
-    const float* sl = g.f.a.slabs;
-    const int64_t st = g.f.a.slab_stride;
-    const int ns = g.f.a.nslabs;
-    f32x4 t;
-    switch (ns) {                                       // the exact slab count (wave-uniform): no load beyond the slabs there are
-#define DVAE_SLABS(n) case n: t = slab_sum4<n>(sl, st, i4); break;
-        DVAE_SLABS(1) DVAE_SLABS(2) DVAE_SLABS(3) DVAE_SLABS(4) DVAE_SLABS(5) DVAE_SLABS(6) DVAE_SLABS(7) DVAE_SLABS(8)
-        DVAE_SLABS(9) DVAE_SLABS(10) DVAE_SLABS(11) DVAE_SLABS(12) DVAE_SLABS(13) DVAE_SLABS(14) DVAE_SLABS(15) DVAE_SLABS(16)
-#undef DVAE_SLABS
-        default:
-            t = *reinterpret_cast<const f32x4*>(sl + i4);
-            for (int k = 1; k < ns; ++k) t += *reinterpret_cast<const f32x4*>(sl + k * st + i4);
-    }
-    f32x4 out;
-    {
-#pragma clang fp contract(off)
-        const f32x4 wt = t * g.weight;
-        out = g.accumulate ? old + wt : wt;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) if (j >= nv) out[j] = 0.f;
-    *reinterpret_cast<f32x4*>(g.flat + i4) = out;
-}
-
-int launch_wgrad_table(const GWgradArgs& g, int n_items, hipStream_t s) {
-    hipLaunchKernelGGL(train_generic_wgrad_kernel, dim3((unsigned)n_items), dim3(256), 0, s, g);
-    DVAE_LAUNCH_OK("train_generic_wgrad_kernel");
-    return 0;
-}
-
-int launch_apply_table(const GApplyArgs& g, hipStream_t s) {
-    const int64_t blocks = g.a.n_params > 0 ? (g.a.n_params + 255) / 256 : 1;
-    hipLaunchKernelGGL(train_generic_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g);
-    DVAE_LAUNCH_OK("train_generic_apply_kernel");
-    return 0;
-}
-
-int launch_reduce_table(const GReduceArgs& g, hipStream_t s) {
-    DVAE_CHECK_ARG(g.f.a.n_params >= 0 && g.f.a.n_params < ((int64_t)1 << 31) && g.f.a.n_params % 64 == 0,
-                   "train_generic_reduce_kernel: %lld parameters (a multiple of 64 below 2^31: the kernel indexes tensors in 32 bits)", (long long)g.f.a.n_params);
-    const int64_t blocks = (g.f.a.n_params / 4 + 255) / 256 + 1;         // + the finalising workgroup
-    hipLaunchKernelGGL(train_generic_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g);
-    DVAE_LAUNCH_OK("train_generic_reduce_kernel");
-    return 0;
-}
-
-int launch_apply_clipped_table(const GApplyArgs& g, const GClipHost& h, hipStream_t s) {
-    const int64_t P = g.a.n_params;
-    DVAE_CHECK_ARG(P >= 1 && P < ((int64_t)1 << 31) - G_NORM_CHUNK && P % 64 == 0 && g.a.nslabs == 1,
-                   "train_generic_gradnorm_kernel: %lld parameters (a multiple of 64 below 2^31: the kernel indexes tensors in 32 bits)", (long long)P);
-    GNormArgs n;
-    memset(&n, 0, sizeof(n));
-    n.flat = g.a.slabs; n.n_params = P; n.partials = (double*)h.scratch;
-    for (int k = 0; k < G_NT; ++k) { n.off[k] = (int32_t)g.t[k].off; n.cnt[k] = g.t[k].rows * g.t[k].cols; }
-    const int64_t chunks = gradnorm_chunks(P);
-    hipLaunchKernelGGL(train_generic_gradnorm_kernel, dim3((unsigned)chunks), dim3(256), 0, s, n);
-    DVAE_LAUNCH_OK("train_generic_gradnorm_kernel");
-    GClipArgs c;
-    memset(&c, 0, sizeof(c));
-    c.partials = (const double*)h.scratch; c.nchunks = (int)chunks; c.grad_scale = h.grad_scale; c.max_norm = h.max_norm;
-    c.norm2_out = h.norm2_out; c.skipped = h.skipped;
-    hipLaunchKernelGGL(train_generic_apply_clipped_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, g, c);
-    DVAE_LAUNCH_OK("train_generic_apply_clipped_kernel");
-    return 0;
-}
-
-int check_clip_args(const char* who, const float* flat, const GClipHost& h) {
-    DVAE_CHECK_ARG(h.scratch && h.norm2_out && h.skipped, "%s: null pointer", who);
-    DVAE_CHECK_ARG(h.max_norm > 0.0, "%s: max_norm %g (a positive number; +inf clips nothing)", who, h.max_norm);      // (a NaN fails the comparison)
-    DVAE_CHECK_ARG(((uintptr_t)flat & 15) == 0 && ((uintptr_t)h.scratch & 7) == 0,
-                   "%s: the flat gradient must be 16-byte aligned and the scratch buffer 8-byte aligned", who);
-    return 0;
-}
-
-int check_reduce_args(const char* who, const void* ws, const float* flat, int accumulate, float weight) {
-    DVAE_CHECK_ARG(ws && flat, "%s: null pointer", who);
-    DVAE_CHECK_ARG(((uintptr_t)flat & 15) == 0, "%s: the flat gradient must be 16-byte aligned", who);
-    DVAE_CHECK_ARG(accumulate == 0 || accumulate == 1, "%s: accumulate %d (0: overwrite the flat gradient, 1: add to it)", who, accumulate);
-    DVAE_CHECK_ARG(isfinite(weight), "%s: the weight of the micro-batch is not finite", who);
-    return 0;
-}
-
-int check_apply_flat_args(const char* who, const float* params, const float* m, const float* v, const void* ws, const float* flat, int step,
-                          double lr, double grad_scale) {
-    DVAE_CHECK_ARG(params && m && v && ws && flat, "%s: null pointer", who);
-    DVAE_CHECK_ARG(step >= 1, "%s: step %d (1-based)", who, step);
-    DVAE_CHECK_ARG(isfinite(grad_scale) && isfinite(lr), "%s: grad_scale / lr is not finite", who);
-    return 0;
-}
-
-int raise_lds_limit(const void* kernel, const char* name, int64_t lds_bytes, bool (&done)[64]) {
-    if (lds_bytes > G_LDS_MAX) { set_error("%s: %lld B of LDS needed, %lld available", name, (long long)lds_bytes, (long long)G_LDS_MAX); return DVAE_E_UNSUPPORTED; }
-    if (lds_bytes <= 64 * 1024) return 0;
-    int dev = 0;
-    DVAE_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !done[dev]) {
-        hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G_LDS_MAX);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();                    // reported here, not left for the caller's next runtime call
-            set_error("hipFuncSetAttribute(%s, %lld B LDS): %s", name, (long long)G_LDS_MAX, hipGetErrorString(e));
-            return (int)e;
-        }
-        if (dev >= 0 && dev < 64) done[dev] = true;
-    }
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
 // host
-// dec_ok: the entry point serves the M2_DEC plans of dvae_module_generic_plan too (init, repack, the module modes); the train-step entry
-// points do not
-static int plan_layout(const char* who, const dvae_train_generic_plan_t* plan, GLayout& L, bool dec_ok = false) {
-    DVAE_CHECK_ARG(plan, "%s: null plan", who);
-    const bool dec = plan->model == DVAE_MODEL_M2_DEC;
-    DVAE_CHECK_ARG(!dec || dec_ok, "%s: a plan of model M2_DEC (dvae_module_generic_plan: the module entry points serve it; there is no train step "
-                   "on the M2_info body alone -- dvae_train_info_* trains the whole model)", who);
-    DVAE_CHECK_ARG((plan->model == DVAE_MODEL_M1 || plan->model == DVAE_MODEL_M2 || dec) && plan->precision == DVAE_PREC_F32 &&
-                   dims_ok(plan->y_dim, plan->z_dim, plan->h1, plan->h2) && (plan->model == DVAE_MODEL_M1) == (plan->y_dim == 0) && plan->B >= 1,
-                   "%s: not a plan of dvae_train_generic_plan / dvae_module_generic_plan", who);
-    DVAE_CHECK_ARG(plan->std_norm == 0 || plan->std_norm == 1, "%s: std_norm %d in the plan (0 or 1)", who, plan->std_norm);
-    DVAE_CHECK_ARG(!dec || !plan->std_norm, "%s: std_norm on a plan of model M2_DEC", who);
-    DVAE_CHECK_ARG(plan->kl_weight >= 0.0 && isfinite(plan->kl_weight) && plan->kl_floor >= 0.0 && isfinite(plan->kl_floor),
-                   "%s: kl_weight %g / kl_floor %g in the plan (finite numbers >= 0; the planner sets 1 and 0)", who, plan->kl_weight, plan->kl_floor);
-    L = make_layout(plan->y_dim, plan->z_dim, plan->h1, plan->h2, plan->B, plan->ksplit, plan->std_norm != 0, dec);
-    DVAE_CHECK_ARG(L.ws_bytes == plan->workspace_bytes && L.nslices == plan->ksplit && L.n_params == plan->n_params &&
-                   L.slice_frames == plan->slice_frames, "%s: the plan was changed after dvae_train_generic_plan", who);
-    return 0;
-}
-
-static int check_inputs(const char* who, const dvae_train_generic_plan_t* plan, const void* ws, const float* x, int64_t ldx, const float* y,
-                        int64_t ldy, const float* eps) {
-    DVAE_CHECK_ARG(ws && x && eps, "%s: null pointer", who);
-    DVAE_CHECK_ARG(ldx >= GX && ldx < ((int64_t)1 << 20), "%s: leading dimension of x %lld (at least 513)", who, (long long)ldx);
-    DVAE_CHECK_ARG((plan->y_dim > 0) == (y != nullptr), "%s: y must be given exactly when y_dim > 0 (y_dim %d)", who, plan->y_dim);
-    DVAE_CHECK_ARG(!y || (ldy >= plan->y_dim && ldy < ((int64_t)1 << 20)), "%s: leading dimension of y %lld for y_dim %d", who, (long long)ldy, plan->y_dim);
-    DVAE_CHECK_ARG(!plan->row_index || plan->row_count >= 1, "%s: a gather table needs row_count >= 1 (got %lld)", who, (long long)plan->row_count);
-    DVAE_CHECK_ARG(!plan->std_norm || (plan->norm_mean && plan->norm_div && (plan->norm_mean & 3) == 0 && (plan->norm_div & 3) == 0),
-                   "%s: a plan with std_norm needs the device tables norm_mean and norm_div (513 floats each)", who);
-    return 0;
-}
-
-static ApplyArgs apply_args(const dvae_train_generic_plan_t* plan, const GLayout& L, float* params, float* m, float* v, char* ws, bool adam, int step,
-                            double lr, double beta1, double beta2, double adam_eps, double grad_scale, float* losses3) {
-    ApplyArgs a;
-    memset(&a, 0, sizeof(a));
-    a.p = params; a.m = m; a.v = v;
-    a.slabs = (const float*)(ws + L.o_grads); a.slab_stride = L.n_params; a.nslabs = L.nslices;
-    a.n_params = L.n_params;
-    if (adam) {
-        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-        a.one_minus_b1 = (float)(1.0 - beta1); a.b2 = (float)beta2; a.one_minus_b2 = (float)(1.0 - beta2);
-        a.step_size = (float)(lr / bc1); a.bc2_sqrt = (float)sqrt(bc2); a.eps = (float)adam_eps; a.gscale = (float)grad_scale;
-    }
-    a.partials = (const double*)(ws + L.o_partials); a.npartials = (int)L.rows_grid; a.B = L.B; a.losses3 = losses3;
-    a.accum = (double*)(uintptr_t)plan->loss_accum;
-    return a;
-}
-
-// adam: the optimizer step on every parameter; otherwise only the packed copies are rewritten (params != null) and / or the losses finalised
-// (clip: the norm launch and the guarded apply kernel in place of the apply kernel)
-// The weighted KL term of a finalising launch.  The plan's defaults (1, 0) leave every argument as it was; any other pair hands the
-// finalising workgroup the clamped KL sums (slot 2 of the rows kernel's partials), and the running sums go through kl_accum.
-static bool kl_weighted(const dvae_train_generic_plan_t* plan) { return !((float)plan->kl_weight == 1.f && (float)plan->kl_floor == 0.f); }
-static void weighted_kl(const dvae_train_generic_plan_t* plan, const GLayout& L, char* ws, GApplyArgs& g) {
-    if (!kl_weighted(plan)) return;
-    const float w = (float)plan->kl_weight;
-    g.kl_partials = (const double*)(ws + L.o_partials) + 2; g.kl_stride = 4; g.kl_w = w;
-    g.kl_accum = g.a.accum; g.a.accum = nullptr;
-}
-
-static int launch_apply(const dvae_train_generic_plan_t* plan, const GLayout& L, const ApplyArgs& a, char* ws, bool adam, bool elements,
-                        bool finalize, hipStream_t s, const GClipHost* clip = nullptr) {
-    GApplyArgs g;
-    memset(&g, 0, sizeof(g));
-    g.a = a;
-    if (!elements) g.a.n_params = 0;
-    make_tensors(L, g.t);
-    g.ws = (float*)ws; g.adam = adam ? 1 : 0; g.finalize = finalize ? 1 : 0;
-    if (finalize) weighted_kl(plan, L, (char*)ws, g);
-    return clip ? launch_apply_clipped_table(g, *clip, s) : launch_apply_table(g, s);
-}
-
-static int launch_rows(const dvae_train_generic_plan_t* plan, const GLayout& L, char* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
-                       const float* eps, float elbo_eps, bool fwd_only, hipStream_t s, int mode = ROWS_STEP, const GModuleArgs* module = nullptr) {
-    static bool attr_done[8][64] = {};
-    const bool dec = L.dec != 0;
-    DVAE_CHECK_ARG(!dec || mode != ROWS_STEP, "train_generic_rows_kernel: no train step on a plan of model M2_DEC");
-    const bool klw = mode == ROWS_STEP && kl_weighted(plan);
-    const void* kernel = mode == ROWS_MODULE_FWD ? (dec ? (const void*)train_generic_rows_kernel<false, ROWS_MODULE_FWD, true>
-                                                       : (const void*)train_generic_rows_kernel<false, ROWS_MODULE_FWD>)
-                       : mode == ROWS_MODULE_BWD ? (dec ? (const void*)train_generic_rows_kernel<false, ROWS_MODULE_BWD, true>
-                                                       : (const void*)train_generic_rows_kernel<false, ROWS_MODULE_BWD>)
-                       : klw ? (L.norm ? (const void*)train_generic_rows_kernel<true, ROWS_STEP, false, true>
-                                       : (const void*)train_generic_rows_kernel<false, ROWS_STEP, false, true>)
-                       : L.norm ? (const void*)train_generic_rows_kernel<true> : (const void*)train_generic_rows_kernel<false>;
-    if (int rc = raise_lds_limit(kernel, "train_generic_rows_kernel", L.lds_bytes,
-                                 attr_done[mode == ROWS_STEP ? (klw ? 6 : 0) + L.norm : (dec ? 3 : 1) + mode])) return rc;
-    GModuleArgs mo;
-    memset(&mo, 0, sizeof(mo));
-    if (module) mo = *module;
-    GRowsArgs g;
-    memset(&g, 0, sizeof(g));
-    g.x = x; g.ldx = ldx; g.y = y; g.ldy = ldy; g.eps = eps;
-    g.row_index = (const int64_t*)(uintptr_t)plan->row_index; g.row_count = plan->row_count; g.bad = (int*)(uintptr_t)plan->bad_row_counter;
-    g.ws = (float*)ws; g.stash = (float*)(ws + L.o_stash); g.partials = (double*)(ws + L.o_partials);
-    g.elbo_eps = elbo_eps; g.invB = (float)(1.0 / (double)L.B); g.fwd_only = fwd_only ? 1 : 0;
-    g.kl_scale = (float)plan->kl_weight * g.invB; g.kl_floor = (float)plan->kl_floor;        // (read by the KLW instantiations)
-    const dim3 grid((unsigned)L.rows_grid), block(256);
-    if (mode == ROWS_MODULE_FWD && dec) {
-        hipLaunchKernelGGL((train_generic_rows_kernel<false, ROWS_MODULE_FWD, true>), grid, block, (size_t)L.lds_bytes, s, L, g, mo);
-    } else if (mode == ROWS_MODULE_BWD && dec) {
-        hipLaunchKernelGGL((train_generic_rows_kernel<false, ROWS_MODULE_BWD, true>), grid, block, (size_t)L.lds_bytes, s, L, g, mo);
-    } else if (mode == ROWS_MODULE_FWD) {
-        hipLaunchKernelGGL((train_generic_rows_kernel<false, ROWS_MODULE_FWD>), grid, block, (size_t)L.lds_bytes, s, L, g, mo);
-    } else if (mode == ROWS_MODULE_BWD) {
-        hipLaunchKernelGGL((train_generic_rows_kernel<false, ROWS_MODULE_BWD>), grid, block, (size_t)L.lds_bytes, s, L, g, mo);
-    } else if (L.norm) {
-        g.nmean = (const float*)(uintptr_t)plan->norm_mean; g.ndiv = (const float*)(uintptr_t)plan->norm_div;
-        if (klw) hipLaunchKernelGGL((train_generic_rows_kernel<true, ROWS_STEP, false, true>), grid, block, (size_t)L.lds_bytes, s, L, g, mo);
-        else hipLaunchKernelGGL(train_generic_rows_kernel<true>, grid, block, (size_t)L.lds_bytes, s, L, g, mo);
-    } else if (klw) {
-        hipLaunchKernelGGL((train_generic_rows_kernel<false, ROWS_STEP, false, true>), grid, block, (size_t)L.lds_bytes, s, L, g, mo);
-    } else {
-        hipLaunchKernelGGL(train_generic_rows_kernel<false>, grid, block, (size_t)L.lds_bytes, s, L, g, mo);
-    }
+template <bool NORM, int MODE, bool DEC, bool KLW>
+static int launch_rows_as(const GLayout& L, const GRowsArgs& g, const GModuleArgs& mo, hipStream_t s) {
+    static bool attr_done[64] = {};                     // (one per instantiation: the limit is a property of the kernel)
+    if (int rc = raise_lds_limit((const void*)train_generic_rows_kernel<NORM, MODE, DEC, KLW>, "train_generic_rows_kernel", L.lds_bytes, attr_done)) return rc;
+    hipLaunchKernelGGL((train_generic_rows_kernel<NORM, MODE, DEC, KLW>), dim3((unsigned)L.rows_grid), dim3(256), (size_t)L.lds_bytes, s, L, g, mo);
     DVAE_LAUNCH_OK("train_generic_rows_kernel");
     return 0;
 }
 
-static int launch_wgrad(const dvae_train_generic_plan_t* plan, const GLayout& L, char* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
-                        hipStream_t s) {
-    GWgradArgs g;
-    memset(&g, 0, sizeof(g));
-    g.x = x; g.ldx = ldx; g.y = y; g.ldy = ldy;
-    g.row_index = (const int64_t*)(uintptr_t)plan->row_index; g.row_count = plan->row_count;
-    g.stash = (const float*)(ws + L.o_stash); g.slabs = (float*)(ws + L.o_grads); g.slab_stride = L.n_params;
-    g.B = L.B; g.slice_frames = L.slice_frames; g.items = (const GItem*)(ws + L.o_items); g.S = L.S;
-    make_gemms(L, g.gm);
-    for (int t = 0; t < G_NT; ++t) g.toff[t] = L.toff[t];
-    return launch_wgrad_table(g, L.n_items, s);
-}
+// the M1 / M2 step as train_step_host.hpp reads it
+struct MStep {
+    using Plan = dvae_train_generic_plan_t;
+    using Layout = GLayout;
+    static constexpr int NT = M_NT, NG = M_NG;
+    static constexpr int ORDER[M_NG] = {0, 6, 4, 1, 5, 2, 3};               // the widest inputs first: their items run longest
+    static constexpr bool COUNTS = false, WGRAD_Y = true;
+
+    // dec_ok: the entry point serves the M2_DEC plans of dvae_module_generic_plan too (init, repack, the module modes); the train-step
+    // entry points do not
+    static int plan_layout(const char* who, const Plan* plan, GLayout& L, bool dec_ok) {
+        DVAE_CHECK_ARG(plan, "%s: null plan", who);
+        const bool dec = plan->model == DVAE_MODEL_M2_DEC;
+        DVAE_CHECK_ARG(!dec || dec_ok, "%s: a plan of model M2_DEC (dvae_module_generic_plan: the module entry points serve it; there is no train step "
+                       "on the M2_info body alone -- dvae_train_info_* trains the whole model)", who);
+        DVAE_CHECK_ARG((plan->model == DVAE_MODEL_M1 || plan->model == DVAE_MODEL_M2 || dec) && plan->precision == DVAE_PREC_F32 &&
+                       dims_ok(plan->y_dim, plan->z_dim, plan->h1, plan->h2) && (plan->model == DVAE_MODEL_M1) == (plan->y_dim == 0) && plan->B >= 1,
+                       "%s: not a plan of dvae_train_generic_plan / dvae_module_generic_plan", who);
+        DVAE_CHECK_ARG(plan->std_norm == 0 || plan->std_norm == 1, "%s: std_norm %d in the plan (0 or 1)", who, plan->std_norm);
+        DVAE_CHECK_ARG(!dec || !plan->std_norm, "%s: std_norm on a plan of model M2_DEC", who);
+        DVAE_CHECK_ARG(plan->kl_weight >= 0.0 && isfinite(plan->kl_weight) && plan->kl_floor >= 0.0 && isfinite(plan->kl_floor),
+                       "%s: kl_weight %g / kl_floor %g in the plan (finite numbers >= 0; the planner sets 1 and 0)", who, plan->kl_weight, plan->kl_floor);
+        L = make_layout(plan->y_dim, plan->z_dim, plan->h1, plan->h2, plan->B, plan->ksplit, plan->std_norm != 0, dec);
+        DVAE_CHECK_ARG(L.ws_bytes == plan->workspace_bytes && L.nslices == plan->ksplit && L.n_params == plan->n_params &&
+                       L.slice_frames == plan->slice_frames, "%s: the plan was changed after dvae_train_generic_plan", who);
+        return 0;
+    }
+
+    static int check_inputs(const char* who, const Plan* plan, const void* ws, const StepInputs& in) {
+        DVAE_CHECK_ARG(ws && in.x && in.eps, "%s: null pointer", who);
+        DVAE_CHECK_ARG(in.ldx >= GX && in.ldx < ((int64_t)1 << 20), "%s: leading dimension of x %lld (at least 513)", who, (long long)in.ldx);
+        DVAE_CHECK_ARG((plan->y_dim > 0) == (in.y != nullptr), "%s: y must be given exactly when y_dim > 0 (y_dim %d)", who, plan->y_dim);
+        DVAE_CHECK_ARG(!in.y || (in.ldy >= plan->y_dim && in.ldy < ((int64_t)1 << 20)), "%s: leading dimension of y %lld for y_dim %d", who,
+                       (long long)in.ldy, plan->y_dim);
+        DVAE_CHECK_ARG(!plan->row_index || plan->row_count >= 1, "%s: a gather table needs row_count >= 1 (got %lld)", who, (long long)plan->row_count);
+        DVAE_CHECK_ARG(!plan->std_norm || (plan->norm_mean && plan->norm_div && (plan->norm_mean & 3) == 0 && (plan->norm_div & 3) == 0),
+                       "%s: a plan with std_norm needs the device tables norm_mean and norm_div (513 floats each)", who);
+        return 0;
+    }
+
+    static int launch_rows(const Plan* plan, const GLayout& L, char* ws, const StepInputs& in, bool fwd_only, hipStream_t s, int mode = ROWS_STEP,
+                           const GModuleArgs* module = nullptr) {
+        const bool dec = L.dec != 0;
+        DVAE_CHECK_ARG(!dec || mode != ROWS_STEP, "train_generic_rows_kernel: no train step on a plan of model M2_DEC");
+        GModuleArgs mo;
+        memset(&mo, 0, sizeof(mo));
+        if (module) mo = *module;
+        GRowsArgs g;
+        memset(&g, 0, sizeof(g));
+        g.x = in.x; g.ldx = in.ldx; g.y = in.y; g.ldy = in.ldy; g.eps = in.eps;
+        g.row_index = (const int64_t*)(uintptr_t)plan->row_index; g.row_count = plan->row_count; g.bad = (int*)(uintptr_t)plan->bad_row_counter;
+        g.ws = (float*)ws; g.stash = (float*)(ws + L.o_stash); g.partials = (double*)(ws + L.o_partials);
+        g.elbo_eps = in.loss_eps; g.invB = (float)(1.0 / (double)L.B); g.fwd_only = fwd_only ? 1 : 0;
+        g.kl_scale = (float)plan->kl_weight * g.invB; g.kl_floor = (float)plan->kl_floor;        // (read by the KLW instantiations)
+        if (mode == ROWS_MODULE_FWD) return dec ? launch_rows_as<false, ROWS_MODULE_FWD, true, false>(L, g, mo, s) : launch_rows_as<false, ROWS_MODULE_FWD, false, false>(L, g, mo, s);
+        if (mode == ROWS_MODULE_BWD) return dec ? launch_rows_as<false, ROWS_MODULE_BWD, true, false>(L, g, mo, s) : launch_rows_as<false, ROWS_MODULE_BWD, false, false>(L, g, mo, s);
+        const bool klw = kl_weighted(plan);
+        if (!L.norm) return klw ? launch_rows_as<false, ROWS_STEP, false, true>(L, g, mo, s) : launch_rows_as<false, ROWS_STEP, false, false>(L, g, mo, s);
+        g.nmean = (const float*)(uintptr_t)plan->norm_mean; g.ndiv = (const float*)(uintptr_t)plan->norm_div;
+        return klw ? launch_rows_as<true, ROWS_STEP, false, true>(L, g, mo, s) : launch_rows_as<true, ROWS_STEP, false, false>(L, g, mo, s);
+    }
+
+    static void tensors(const GLayout& L, GTensor* T) { make_tensors(L, T); }
+    static void gemms(const GLayout& L, GGemm* G) { make_gemms(L, G); }
+    static size_t partials_bytes(const GLayout& L) { return (size_t)L.rows_grid * 4 * sizeof(double); }
+    static void extend_apply_args(const Plan*, const GLayout&, ApplyArgs&) {}
+    // The weighted KL term of a finalising launch: the finalising workgroup takes the clamped KL sums (slot 2 of the rows kernel's partials),
+    // and the running sums go through kl_accum.
+    static void extend_table(const Plan* plan, const GLayout& L, char* ws, long long*, GApplyArgs& g) {
+        if (!g.finalize || !kl_weighted(plan)) return;
+        g.kl_partials = (const double*)(ws + L.o_partials) + 2; g.kl_stride = 4; g.kl_w = (float)plan->kl_weight;
+        g.kl_accum = g.a.accum; g.a.accum = nullptr;
+    }
+};
 
 }  // namespace tg
 }  // namespace dvae
@@ -1115,156 +707,93 @@ extern "C" int dvae_train_generic_plan_norm(int model, int y_dim, int z_dim, int
     return 0;
 }
 
+// the train step's entry points: train_step_host.hpp under this step's description
 extern "C" int dvae_train_generic_repack(const dvae_train_generic_plan_t* plan, const float* params, void* ws, void* stream) {
-    GLayout L;
-    if (int rc = plan_layout("train_generic_repack", plan, L, true)) return rc;
-    DVAE_CHECK_ARG(params && ws, "train_generic_repack: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    DVAE_HIP(hipMemsetAsync(ws, 0, (size_t)L.wpack_elems * 4, s));          // the padding of the packed copies
-    const ApplyArgs a = apply_args(plan, L, (float*)params, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, nullptr);
-    return launch_apply(plan, L, a, (char*)ws, false, true, false, s);
+    return step_repack<MStep>("train_generic_repack", plan, params, ws, stream);
 }
 
 extern "C" int dvae_train_generic_init(const dvae_train_generic_plan_t* plan, const float* params, void* ws, void* stream) {
-    GLayout L;
-    if (int rc = plan_layout("train_generic_init", plan, L, true)) return rc;
-    DVAE_CHECK_ARG(params && ws, "train_generic_init: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    GGemm gm[M_NG];
-    make_gemms(L, gm);
-    const int order[M_NG] = {0, 6, 4, 1, 5, 2, 3};                         // the widest inputs first: their items run longest
-    const std::vector<GItem> items = make_items(gm, order, M_NG, L.nslices);
-    DVAE_CHECK_ARG((int)items.size() == L.n_items, "train_generic_init: %d items for a table of %d", (int)items.size(), L.n_items);
-    DVAE_HIP(hipMemcpyAsync((char*)ws + L.o_items, items.data(), items.size() * sizeof(GItem), hipMemcpyHostToDevice, s));
-    DVAE_HIP(hipMemsetAsync((char*)ws + L.o_partials, 0, (size_t)L.rows_grid * 4 * sizeof(double), s));
-    DVAE_HIP(hipStreamSynchronize(s));                                      // the table leaves host memory that ends with this call
-    return dvae_train_generic_repack(plan, params, ws, stream);
+    return step_init<MStep>("train_generic_init", plan, params, ws, stream);
 }
 
 extern "C" int dvae_train_generic_grads(const dvae_train_generic_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
                                         const float* eps_noise, float elbo_eps, void* stream) {
-    GLayout L;
-    if (int rc = plan_layout("train_generic_grads", plan, L)) return rc;
-    if (int rc = check_inputs("train_generic_grads", plan, ws, x, ldx, y, ldy, eps_noise)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = launch_rows(plan, L, (char*)ws, x, ldx, y, ldy, eps_noise, elbo_eps, false, s)) return rc;
-    return launch_wgrad(plan, L, (char*)ws, x, ldx, y, ldy, s);
+    return step_grads<MStep>("train_generic_grads", plan, ws, {x, ldx, y, ldy, eps_noise, elbo_eps}, stream);
 }
 
 extern "C" int dvae_train_generic_apply(const dvae_train_generic_plan_t* plan, float* params, float* m, float* v, void* ws, int step, double lr,
                                         double beta1, double beta2, double adam_eps, double grad_scale, float* losses3, void* stream) {
-    GLayout L;
-    if (int rc = plan_layout("train_generic_apply", plan, L)) return rc;
-    DVAE_CHECK_ARG(params && m && v && ws && losses3, "train_generic_apply: null pointer");
-    DVAE_CHECK_ARG(step >= 1, "train_generic_apply: step %d (1-based)", step);
-    const ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, losses3);
-    return launch_apply(plan, L, a, (char*)ws, true, true, true, (hipStream_t)stream);
+    return step_apply<MStep>("train_generic_apply", plan, {params, m, v, step, lr, beta1, beta2, adam_eps, grad_scale}, ws, {losses3, nullptr}, stream);
 }
 
 extern "C" int dvae_train_generic_reduce(const dvae_train_generic_plan_t* plan, void* ws, float* flat, int accumulate, float weight, float* losses3,
                                          void* stream) {
-    GLayout L;
-    if (int rc = plan_layout("train_generic_reduce", plan, L)) return rc;
-    if (int rc = check_reduce_args("train_generic_reduce", ws, flat, accumulate, weight)) return rc;
-    DVAE_CHECK_ARG(losses3, "train_generic_reduce: null pointer");
-    GReduceArgs g;
-    memset(&g, 0, sizeof(g));
-    g.f.a = apply_args(plan, L, nullptr, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, losses3);
-    make_tensors(L, g.f.t);
-    g.f.ws = (float*)ws; g.f.finalize = 1;
-    weighted_kl(plan, L, (char*)ws, g.f);
-    g.flat = flat; g.accumulate = accumulate; g.weight = weight;
-    return launch_reduce_table(g, (hipStream_t)stream);
+    return step_reduce<MStep>("train_generic_reduce", plan, ws, flat, accumulate, weight, {losses3, nullptr}, stream);
 }
 
 extern "C" int dvae_train_generic_apply_flat(const dvae_train_generic_plan_t* plan, float* params, float* m, float* v, void* ws, const float* flat,
                                              int step, double lr, double beta1, double beta2, double adam_eps, double grad_scale, void* stream) {
-    GLayout L;
-    if (int rc = plan_layout("train_generic_apply_flat", plan, L)) return rc;
-    if (int rc = check_apply_flat_args("train_generic_apply_flat", params, m, v, ws, flat, step, lr, grad_scale)) return rc;
-    ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, nullptr);
-    a.slabs = flat; a.nslabs = 1;                       // the flat gradient is the one slab
-    return launch_apply(plan, L, a, (char*)ws, true, true, false, (hipStream_t)stream);
-}
-
-extern "C" int64_t dvae_train_gradnorm_scratch_bytes(int64_t n_params) {
-    if (n_params < 1 || n_params >= ((int64_t)1 << 31) - G_NORM_CHUNK) {
-        set_error("train_gradnorm_scratch_bytes: n_params %lld (the plan's n_params: at least 1, below 2^31)", (long long)n_params);
-        return 0;
-    }
-    return gradnorm_chunks(n_params) * (int64_t)sizeof(double);
+    return step_apply_flat<MStep>("train_generic_apply_flat", plan, {params, m, v, step, lr, beta1, beta2, adam_eps, grad_scale}, ws, flat, nullptr, stream);
 }
 
 extern "C" int dvae_train_generic_apply_flat_clipped(const dvae_train_generic_plan_t* plan, float* params, float* m, float* v, void* ws,
                                                      const float* flat, int step, double lr, double beta1, double beta2, double adam_eps,
                                                      double grad_scale, double max_norm, void* scratch, float* norm2_out,
                                                      int32_t* skipped_counter, void* stream) {
-    GLayout L;
-    if (int rc = plan_layout("train_generic_apply_flat_clipped", plan, L)) return rc;
-    if (int rc = check_apply_flat_args("train_generic_apply_flat_clipped", params, m, v, ws, flat, step, lr, grad_scale)) return rc;
     const GClipHost clip = {grad_scale, max_norm, scratch, norm2_out, skipped_counter};
-    if (int rc = check_clip_args("train_generic_apply_flat_clipped", flat, clip)) return rc;
-    ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, nullptr);
-    a.slabs = flat; a.nslabs = 1;                       // the flat gradient is the one slab
-    return launch_apply(plan, L, a, (char*)ws, true, true, false, (hipStream_t)stream, &clip);
+    return step_apply_flat<MStep>("train_generic_apply_flat_clipped", plan, {params, m, v, step, lr, beta1, beta2, adam_eps, grad_scale}, ws, flat, &clip,
+                                  stream);
 }
 
 extern "C" int dvae_train_generic_step(const dvae_train_generic_plan_t* plan, float* params, float* m, float* v, void* ws, const float* x, int64_t ldx,
                                        const float* y, int64_t ldy, const float* eps_noise, float elbo_eps, int step, double lr, double beta1,
                                        double beta2, double adam_eps, float* losses3, void* stream) {
-    DVAE_CHECK_ARG(params && m && v && losses3, "train_generic_step: null pointer");
-    DVAE_CHECK_ARG(step >= 1, "train_generic_step: step %d (1-based)", step);
-    if (int rc = dvae_train_generic_grads(plan, ws, x, ldx, y, ldy, eps_noise, elbo_eps, stream)) return rc;
-    return dvae_train_generic_apply(plan, params, m, v, ws, step, lr, beta1, beta2, adam_eps, 1.0, losses3, stream);
+    return step_step<MStep>("train_generic_step", "train_generic_grads", "train_generic_apply", plan, {params, m, v, step, lr, beta1, beta2, adam_eps, 1.0},
+                            ws, {x, ldx, y, ldy, eps_noise, elbo_eps}, {losses3, nullptr}, stream);
 }
 
 extern "C" int dvae_train_generic_eval(const dvae_train_generic_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
                                        const float* eps_noise, float elbo_eps, float* losses3, void* stream) {
-    GLayout L;
-    if (int rc = plan_layout("train_generic_eval", plan, L)) return rc;
-    if (int rc = check_inputs("train_generic_eval", plan, ws, x, ldx, y, ldy, eps_noise)) return rc;
-    DVAE_CHECK_ARG(losses3, "train_generic_eval: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = launch_rows(plan, L, (char*)ws, x, ldx, y, ldy, eps_noise, elbo_eps, true, s)) return rc;
-    const ApplyArgs a = apply_args(plan, L, nullptr, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, losses3);
-    return launch_apply(plan, L, a, (char*)ws, false, false, true, s);
+    return step_eval<MStep>("train_generic_eval", plan, ws, {x, ldx, y, ldy, eps_noise, elbo_eps}, {losses3, nullptr}, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // the whole-model autograd path of the drop-in modules at any covered size (disentangled-vae_amd/module_path.py: GenericModuleEngine)
-static int check_module(const char* who, const dvae_train_generic_plan_t* plan, const float* params, const void* ws, const float* x, int64_t ldx,
-                        const float* y, int64_t ldy, const float* eps) {
+static int check_module(const char* who, const dvae_train_generic_plan_t* plan, const float* params, const void* ws, const StepInputs& in) {
     DVAE_CHECK_ARG(!plan->std_norm, "%s: a std_norm plan (the module path takes the encoder input as given: normalise x in torch and pass it)", who);
     DVAE_CHECK_ARG(!plan->row_index, "%s: a gather table in the plan (row_index: the module path reads the batch itself)", who);
     DVAE_CHECK_ARG(params, "%s: null pointer", who);
-    return check_inputs(who, plan, ws, x, ldx, y, ldy, eps);
+    return MStep::check_inputs(who, plan, ws, in);
 }
 
 extern "C" int dvae_module_generic_forward(const dvae_train_generic_plan_t* plan, const float* params, void* ws, const float* x, int64_t ldx,
                                            const float* y, int64_t ldy, const float* eps_noise, float* out_r, int64_t ld_r, float* out_mu,
                                            float* out_lv, float* out_z, int repack, void* stream) {
     GLayout L;
-    if (int rc = plan_layout("module_generic_forward", plan, L, true)) return rc;
-    if (int rc = check_module("module_generic_forward", plan, params, ws, x, ldx, y, ldy, eps_noise)) return rc;
+    const StepInputs in = {x, ldx, y, ldy, eps_noise, 0.f};
+    if (int rc = MStep::plan_layout("module_generic_forward", plan, L, true)) return rc;
+    if (int rc = check_module("module_generic_forward", plan, params, ws, in)) return rc;
     DVAE_CHECK_ARG(out_r && out_mu && out_lv, "module_generic_forward: null pointer (out_z alone may be null)");
     DVAE_CHECK_ARG(ld_r >= GX && ld_r < ((int64_t)1 << 20), "module_generic_forward: ld_r %lld (the leading dimension of out_r: at least 513)", (long long)ld_r);
     hipStream_t s = (hipStream_t)stream;
     if (repack) {                                       // every element of both packed copies from `params`; the padding is dvae_train_generic_init's
-        const ApplyArgs a = apply_args(plan, L, (float*)params, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, nullptr);
-        if (int rc = launch_apply(plan, L, a, (char*)ws, false, true, false, s)) return rc;
+        StepUpdate u = {};
+        u.params = (float*)params;
+        const ApplyArgs a = apply_args<MStep>(plan, L, (char*)ws, u, false, nullptr);
+        if (int rc = launch_apply<MStep>(plan, L, a, (char*)ws, false, true, false, nullptr, s)) return rc;
     }
     GModuleArgs mo;
     memset(&mo, 0, sizeof(mo));
     mo.out_r = out_r; mo.ld_r = ld_r; mo.out_mu = out_mu; mo.out_lv = out_lv; mo.out_z = out_z;
-    return launch_rows(plan, L, (char*)ws, x, ldx, y, ldy, eps_noise, 0.f, true, s, ROWS_MODULE_FWD, &mo);
+    return MStep::launch_rows(plan, L, (char*)ws, in, true, s, ROWS_MODULE_FWD, &mo);
 }
 
-static int module_backward(const char* who, const dvae_train_generic_plan_t* plan, const float* params, void* ws, const float* x, int64_t ldx,
-                           const float* y, int64_t ldy, const float* eps_noise, const float* g_r, int64_t ld_gr, const float* g_mu,
-                           const float* g_lv, const float* g_z, float* grad_flat, int accumulate, float* g_y, int64_t ld_gy, void* stream) {
+static int module_backward(const char* who, const dvae_train_generic_plan_t* plan, const float* params, void* ws, const StepInputs& in,
+                           const float* g_r, int64_t ld_gr, const float* g_mu, const float* g_lv, const float* g_z, float* grad_flat, int accumulate,
+                           float* g_y, int64_t ld_gy, void* stream) {
     GLayout L;
-    if (int rc = plan_layout(who, plan, L, true)) return rc;
-    if (int rc = check_module(who, plan, params, ws, x, ldx, y, ldy, eps_noise)) return rc;
+    if (int rc = MStep::plan_layout(who, plan, L, true)) return rc;
+    if (int rc = check_module(who, plan, params, ws, in)) return rc;
     if (int rc = check_reduce_args(who, ws, grad_flat, accumulate, 1.f)) return rc;
     DVAE_CHECK_ARG(!g_r || (ld_gr >= GX && ld_gr < ((int64_t)1 << 20)), "%s: ld_gr %lld (the leading dimension of g_r: at least 513)", who,
                    (long long)ld_gr);
@@ -1277,31 +806,27 @@ static int module_backward(const char* who, const dvae_train_generic_plan_t* pla
     memset(&mo, 0, sizeof(mo));
     mo.g_r = g_r; mo.ld_gr = ld_gr; mo.g_mu = g_mu; mo.g_lv = g_lv; mo.g_z = g_z;
     mo.out_gy = g_y; mo.ld_gy = ld_gy;
-    if (int rc = launch_rows(plan, L, (char*)ws, x, ldx, y, ldy, eps_noise, 0.f, false, s, ROWS_MODULE_BWD, &mo)) return rc;
-    if (int rc = launch_wgrad(plan, L, (char*)ws, x, ldx, y, ldy, s)) return rc;
-    GReduceArgs g;                                      // the slabs in slab order into grad_flat; weight 1: the sum's bits; nothing to finalise
-    memset(&g, 0, sizeof(g));
-    g.f.a = apply_args(plan, L, nullptr, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, nullptr);
-    g.f.a.accum = nullptr;
-    make_tensors(L, g.f.t);
-    g.f.ws = (float*)ws; g.f.finalize = 0;
-    g.flat = grad_flat; g.accumulate = accumulate; g.weight = 1.f;
-    return launch_reduce_table(g, s);
+    if (int rc = MStep::launch_rows(plan, L, (char*)ws, in, false, s, ROWS_MODULE_BWD, &mo)) return rc;
+    if (int rc = launch_wgrad<MStep>(plan, L, (char*)ws, in, s)) return rc;
+    // the slabs in slab order into grad_flat; weight 1: the sum's bits; nothing to finalise, no running sums
+    ApplyArgs a = apply_args<MStep>(plan, L, (char*)ws, StepUpdate{}, false, nullptr);
+    a.accum = nullptr;
+    return launch_reduce<MStep>(plan, L, a, (char*)ws, false, nullptr, grad_flat, accumulate, 1.f, s);
 }
 
 extern "C" int dvae_module_generic_backward(const dvae_train_generic_plan_t* plan, const float* params, void* ws, const float* x, int64_t ldx,
                                             const float* y, int64_t ldy, const float* eps_noise, const float* g_r, int64_t ld_gr,
                                             const float* g_mu, const float* g_lv, const float* g_z, float* grad_flat, int accumulate,
                                             void* stream) {
-    return module_backward("module_generic_backward", plan, params, ws, x, ldx, y, ldy, eps_noise, g_r, ld_gr, g_mu, g_lv, g_z, grad_flat, accumulate,
-                           nullptr, 0, stream);
+    return module_backward("module_generic_backward", plan, params, ws, {x, ldx, y, ldy, eps_noise, 0.f}, g_r, ld_gr, g_mu, g_lv, g_z, grad_flat,
+                           accumulate, nullptr, 0, stream);
 }
 
 extern "C" int dvae_module_generic_backward_y(const dvae_train_generic_plan_t* plan, const float* params, void* ws, const float* x, int64_t ldx,
                                               const float* y, int64_t ldy, const float* eps_noise, const float* g_r, int64_t ld_gr,
                                               const float* g_mu, const float* g_lv, const float* g_z, float* grad_flat, int accumulate,
                                               float* g_y, int64_t ld_gy, void* stream) {
-    return module_backward("module_generic_backward_y", plan, params, ws, x, ldx, y, ldy, eps_noise, g_r, ld_gr, g_mu, g_lv, g_z, grad_flat,
+    return module_backward("module_generic_backward_y", plan, params, ws, {x, ldx, y, ldy, eps_noise, 0.f}, g_r, ld_gr, g_mu, g_lv, g_z, grad_flat,
                            accumulate, g_y, ld_gy, stream);
 }
 
@@ -1324,3 +849,4 @@ extern "C" int dvae_module_generic_plan(int model, int y_dim, int z_dim, int h1,
     fill_plan(plan, L, model, DVAE_PREC_F32, 0);
     return 0;
 }
+

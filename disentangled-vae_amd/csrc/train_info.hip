@@ -9,8 +9,8 @@
 // The resident step (train_rows*.hip) is written for 513-128-128-16 / y 1 and stays the default there; this file serves every other size
 // within x 513, y_dim 1..513, h1 / h2 1..512, z 1..128 -- and the reference geometry too when asked.
 //
-// The design is train_generic.hip's and train_classifier.hip's, composed; their weight-gradient and apply kernels serve this step
-// through the tables of train_generic.hpp (one launch each):
+// The design is train_generic.hip's and train_classifier.hip's, composed; the weight-gradient and apply kernels of train_tables.hip serve
+// this step (one launch each), and the host path around the launches is train_step_host.hpp's (IStep below describes this step to it):
 //   * rows kernel (here): 256 threads own a tile of 16 frames; products on v_mfma_f32_16x16x4_f32 from packed copies in fragment order,
 //     zero-padded to multiples of 16 (tg_gemm).  LDS holds the tiles of the M1 / M2 kernel and no more -- X [528][16], Y [yp][16], A and
 //     Bf [hm][16] with hm = max(h1p, h2p, zp), C [3 zp][16]: 154 KB at 512 / 512 / z 128 / y 513, sized from the dims at launch -- so the
@@ -43,7 +43,7 @@
 #include <vector>
 #include "common.hpp"
 #include "../../include/dvae_train.h"
-#include "train_generic.hpp"
+#include "train_step_host.hpp"
 
 namespace dvae {
 namespace ti {
@@ -53,11 +53,11 @@ using fused::ApplyArgs;
 
 constexpr int I_NT = 26, I_NG = 13;
 constexpr int I_LAUNCHES = 3;
-static_assert(I_NT <= G_NT && I_NG <= G_NG, "the tables of train_generic.hpp hold this step");
+static_assert(I_NT <= G_NT && I_NG <= G_NG, "the tables of train_tables.hpp hold this step");
 
 struct ILayout {
     int y, z, h1, h2, yp, zp, h1p, h2p, hm;     // sizes and their multiples of 16; hm = max(h1p, h2p, zp)
-    // packed copies, float offsets from the start of the workspace (fragment order, train_generic.hpp); the heads are one matrix
+    // packed copies, float offsets from the start of the workspace (fragment order, train_tables.hpp); the heads are one matrix
     int64_t W1, W2, Wh, D1z, D1y, D2, D3, D3T, D2T, D1zT, WhT, W2T;       // the VAE: forward copies, then the transposed ones
     int64_t C1, C2, Co, CoT, C2T;                                        // classifier on x
     int64_t A1, A2, Ao, AoT, A2T, A1T;                                   // auxiliary net on z
@@ -855,72 +855,6 @@ __global__ __launch_bounds__(256) void train_info_rows_kernel(const ILayout L, c
 // host
 static const char* LIMITS = "the M2_info train step covers DeepGenerativeModel_v5 at x 513, y_dim 1..513, hidden widths 1..512, z_dim 1..128, exact fp32, one GPU";
 
-static int plan_layout(const char* who, const dvae_train_info_plan_t* plan, ILayout& L) {
-    DVAE_CHECK_ARG(plan, "%s: null plan", who);
-    DVAE_CHECK_ARG(dims_ok(plan->y_dim, plan->z_dim, plan->h1, plan->h2) && plan->B >= 1 && plan->n_tensors == I_NT && mode_ok(plan->info_mode),
-                   "%s: not a plan of dvae_train_info_plan", who);
-    DVAE_CHECK_ARG(plan->kl_weight >= 0.0 && isfinite(plan->kl_weight) && plan->kl_floor >= 0.0 && isfinite(plan->kl_floor),
-                   "%s: kl_weight %g / kl_floor %g in the plan (finite numbers >= 0; the planner sets 1 and 0)", who, plan->kl_weight, plan->kl_floor);
-    L = make_layout(plan->y_dim, plan->z_dim, plan->h1, plan->h2, plan->B, plan->ksplit, plan->info_mode);
-    DVAE_CHECK_ARG(L.ws_bytes == plan->workspace_bytes && L.nslices == plan->ksplit && L.n_params == plan->n_params &&
-                   L.slice_frames == plan->slice_frames, "%s: the plan was changed after dvae_train_info_plan", who);
-    return 0;
-}
-
-static int check_inputs(const char* who, const dvae_train_info_plan_t* plan, const void* ws, const float* x, int64_t ldx, const float* y,
-                        int64_t ldy, const float* eps) {
-    DVAE_CHECK_ARG(ws && x && y && eps, "%s: null pointer", who);
-    DVAE_CHECK_ARG(ldx >= GX && ldx < ((int64_t)1 << 20), "%s: leading dimension of x %lld (at least 513)", who, (long long)ldx);
-    DVAE_CHECK_ARG(ldy >= plan->y_dim && ldy < ((int64_t)1 << 20), "%s: leading dimension of y %lld for y_dim %d", who, (long long)ldy, plan->y_dim);
-    DVAE_CHECK_ARG(!plan->row_index || plan->row_count >= 1, "%s: a gather table needs row_count >= 1 (got %lld)", who, (long long)plan->row_count);
-    return 0;
-}
-
-static ApplyArgs apply_args(const dvae_train_info_plan_t* plan, const ILayout& L, float* params, float* m, float* v, char* ws, bool adam, int step,
-                            double lr, double beta1, double beta2, double adam_eps, double grad_scale, float* losses8) {
-    ApplyArgs a;
-    memset(&a, 0, sizeof(a));
-    a.p = params; a.m = m; a.v = v;
-    a.slabs = (const float*)(ws + L.o_grads); a.slab_stride = L.n_params; a.nslabs = L.nslices;
-    a.n_params = L.n_params;
-    if (adam) {
-        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-        a.one_minus_b1 = (float)(1.0 - beta1); a.b2 = (float)beta2; a.one_minus_b2 = (float)(1.0 - beta2);
-        a.step_size = (float)(lr / bc1); a.bc2_sqrt = (float)sqrt(bc2); a.eps = (float)adam_eps; a.gscale = (float)grad_scale;
-    }
-    a.partials = (const double*)(ws + L.o_partials); a.npartials = (int)L.rows_grid; a.B = L.B; a.losses3 = losses8;
-    a.accum = (L.mode & MODE_AUX) ? nullptr : (double*)(uintptr_t)plan->loss_accum;      // (launch_apply: the apply kernel corrects the scalars first)
-    a.info = 1; a.alpha = (float)plan->info_alpha; a.beta = (float)plan->info_beta; a.gamma = (float)plan->info_gamma;
-    return a;
-}
-
-// The weighted KL term of a finalising launch (train_generic.hip: weighted_kl).  The plan's defaults (1, 0) leave every argument as it
-// was.  Where the fifth sum is finalised too (MODE_AUX), its block runs last on the rebuilt ELBO and v_accum takes the running sums.
-static bool kl_weighted(const dvae_train_info_plan_t* plan) { return !((float)plan->kl_weight == 1.f && (float)plan->kl_floor == 0.f); }
-static void weighted_kl(const dvae_train_info_plan_t* plan, const ILayout& L, char* ws, GApplyArgs& g) {
-    if (!kl_weighted(plan)) return;
-    const float w = (float)plan->kl_weight;
-    g.kl_partials = (const double*)(ws + L.o_partials) + partials_k_off(L); g.kl_stride = 1; g.kl_w = w;
-    if (!(L.mode & MODE_AUX)) { g.kl_accum = g.a.accum; g.a.accum = nullptr; }
-}
-
-// adam: the optimizer step on every parameter; otherwise only the packed copies are rewritten (elements) and / or the losses finalised
-static int launch_apply(const dvae_train_info_plan_t* plan, const ILayout& L, const ApplyArgs& a, char* ws, bool adam, bool elements, bool finalize,
-                        hipStream_t s, const GClipHost* clip = nullptr) {
-    GApplyArgs g;
-    memset(&g, 0, sizeof(g));
-    g.a = a;
-    if (!elements) g.a.n_params = 0;
-    make_tensors(L, g.t);
-    if (L.mode & MODE_AUX) {
-        g.v_partials = (const double*)(ws + L.o_partials) + 4 * L.rows_grid;
-        g.v_accum = (double*)(uintptr_t)plan->loss_accum;
-    }
-    g.ws = (float*)ws; g.adam = adam ? 1 : 0; g.finalize = finalize ? 1 : 0;
-    if (finalize) weighted_kl(plan, L, ws, g);
-    return clip ? launch_apply_clipped_table(g, *clip, s) : launch_apply_table(g, s);
-}
-
 template <bool DC, int AV, bool KLW>
 static int launch_rows_klw(const ILayout& L, const IRowsArgs& g, hipStream_t s) {
     static bool attr_done[64] = {};                     // (one per instantiation: the limit is a property of the kernel)
@@ -934,40 +868,76 @@ static int launch_rows_mode(const ILayout& L, const IRowsArgs& g, bool klw, hipS
     return klw ? launch_rows_klw<DC, AV, true>(L, g, s) : launch_rows_klw<DC, AV, false>(L, g, s);
 }
 
-static int launch_rows(const dvae_train_info_plan_t* plan, const ILayout& L, char* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
-                       const float* eps, float elbo_eps, bool fwd_only, hipStream_t s) {
-    IRowsArgs g;
-    memset(&g, 0, sizeof(g));
-    g.x = x; g.ldx = ldx; g.y = y; g.ldy = ldy; g.eps = eps;
-    g.row_index = (const int64_t*)(uintptr_t)plan->row_index; g.row_count = plan->row_count; g.bad = (int*)(uintptr_t)plan->bad_row_counter;
-    g.ws = (float*)ws; g.stash = (float*)(ws + L.o_stash); g.partials = (double*)(ws + L.o_partials);
-    g.elbo_eps = elbo_eps; g.invB = (float)(1.0 / (double)L.B); g.fwd_only = fwd_only ? 1 : 0;
-    g.clf_scale = (float)(plan->info_alpha / (double)L.B);
-    g.aux_z_scale = (float)(-plan->info_beta);
-    g.aux_w_scale = (float)(plan->info_gamma - plan->info_beta);
-    g.aux_gamma = (float)plan->info_gamma;
-    g.partials_v = g.partials + 4 * L.rows_grid;
-    g.partials_k = g.partials + partials_k_off(L);
-    g.kl_scale = (float)plan->kl_weight * g.invB; g.kl_floor = (float)plan->kl_floor;        // (read by the KLW instantiations)
-    const bool dc = (L.mode & DVAE_INFO_DEC_CLASSIFIER) != 0;
-    const int av = (L.mode & DVAE_INFO_AUX_UNIFORM) ? 1 : ((L.mode & DVAE_INFO_AUX_ENTROPY) ? 2 : 0);
-    const bool klw = kl_weighted(plan);
-    if (!dc) return av == 0 ? launch_rows_mode<false, 0>(L, g, klw, s) : (av == 1 ? launch_rows_mode<false, 1>(L, g, klw, s) : launch_rows_mode<false, 2>(L, g, klw, s));
-    return av == 0 ? launch_rows_mode<true, 0>(L, g, klw, s) : (av == 1 ? launch_rows_mode<true, 1>(L, g, klw, s) : launch_rows_mode<true, 2>(L, g, klw, s));
-}
+// the M2_info step as train_step_host.hpp reads it
+struct IStep {
+    using Plan = dvae_train_info_plan_t;
+    using Layout = ILayout;
+    static constexpr int NT = I_NT, NG = I_NG;
+    static constexpr int ORDER[I_NG] = {0, 7, 6, 4, 1, 5, 8, 11, 2, 3, 9, 12, 10};     // the widest inputs first: their items run longest
+    static constexpr bool COUNTS = false, WGRAD_Y = true;
 
-static int launch_wgrad(const dvae_train_info_plan_t* plan, const ILayout& L, char* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
-                        hipStream_t s) {
-    GWgradArgs g;
-    memset(&g, 0, sizeof(g));
-    g.x = x; g.ldx = ldx; g.y = y; g.ldy = ldy;
-    g.row_index = (const int64_t*)(uintptr_t)plan->row_index; g.row_count = plan->row_count;
-    g.stash = (const float*)(ws + L.o_stash); g.slabs = (float*)(ws + L.o_grads); g.slab_stride = L.n_params;
-    g.B = L.B; g.slice_frames = L.slice_frames; g.items = (const GItem*)(ws + L.o_items); g.S = L.S;
-    make_gemms(L, g.gm);
-    for (int t = 0; t < I_NT; ++t) g.toff[t] = L.toff[t];
-    return launch_wgrad_table(g, L.n_items, s);
-}
+    static int plan_layout(const char* who, const Plan* plan, ILayout& L, bool) {
+        DVAE_CHECK_ARG(plan, "%s: null plan", who);
+        DVAE_CHECK_ARG(dims_ok(plan->y_dim, plan->z_dim, plan->h1, plan->h2) && plan->B >= 1 && plan->n_tensors == I_NT && mode_ok(plan->info_mode),
+                       "%s: not a plan of dvae_train_info_plan", who);
+        DVAE_CHECK_ARG(plan->kl_weight >= 0.0 && isfinite(plan->kl_weight) && plan->kl_floor >= 0.0 && isfinite(plan->kl_floor),
+                       "%s: kl_weight %g / kl_floor %g in the plan (finite numbers >= 0; the planner sets 1 and 0)", who, plan->kl_weight, plan->kl_floor);
+        L = make_layout(plan->y_dim, plan->z_dim, plan->h1, plan->h2, plan->B, plan->ksplit, plan->info_mode);
+        DVAE_CHECK_ARG(L.ws_bytes == plan->workspace_bytes && L.nslices == plan->ksplit && L.n_params == plan->n_params &&
+                       L.slice_frames == plan->slice_frames, "%s: the plan was changed after dvae_train_info_plan", who);
+        return 0;
+    }
+
+    static int check_inputs(const char* who, const Plan* plan, const void* ws, const StepInputs& in) {
+        DVAE_CHECK_ARG(ws && in.x && in.y && in.eps, "%s: null pointer", who);
+        DVAE_CHECK_ARG(in.ldx >= GX && in.ldx < ((int64_t)1 << 20), "%s: leading dimension of x %lld (at least 513)", who, (long long)in.ldx);
+        DVAE_CHECK_ARG(in.ldy >= plan->y_dim && in.ldy < ((int64_t)1 << 20), "%s: leading dimension of y %lld for y_dim %d", who, (long long)in.ldy,
+                       plan->y_dim);
+        DVAE_CHECK_ARG(!plan->row_index || plan->row_count >= 1, "%s: a gather table needs row_count >= 1 (got %lld)", who, (long long)plan->row_count);
+        return 0;
+    }
+
+    static int launch_rows(const Plan* plan, const ILayout& L, char* ws, const StepInputs& in, bool fwd_only, hipStream_t s) {
+        IRowsArgs g;
+        memset(&g, 0, sizeof(g));
+        g.x = in.x; g.ldx = in.ldx; g.y = in.y; g.ldy = in.ldy; g.eps = in.eps;
+        g.row_index = (const int64_t*)(uintptr_t)plan->row_index; g.row_count = plan->row_count; g.bad = (int*)(uintptr_t)plan->bad_row_counter;
+        g.ws = (float*)ws; g.stash = (float*)(ws + L.o_stash); g.partials = (double*)(ws + L.o_partials);
+        g.elbo_eps = in.loss_eps; g.invB = (float)(1.0 / (double)L.B); g.fwd_only = fwd_only ? 1 : 0;
+        g.clf_scale = (float)(plan->info_alpha / (double)L.B);
+        g.aux_z_scale = (float)(-plan->info_beta);
+        g.aux_w_scale = (float)(plan->info_gamma - plan->info_beta);
+        g.aux_gamma = (float)plan->info_gamma;
+        g.partials_v = g.partials + 4 * L.rows_grid;
+        g.partials_k = g.partials + partials_k_off(L);
+        g.kl_scale = (float)plan->kl_weight * g.invB; g.kl_floor = (float)plan->kl_floor;        // (read by the KLW instantiations)
+        const bool dc = (L.mode & DVAE_INFO_DEC_CLASSIFIER) != 0;
+        const int av = (L.mode & DVAE_INFO_AUX_UNIFORM) ? 1 : ((L.mode & DVAE_INFO_AUX_ENTROPY) ? 2 : 0);
+        const bool klw = kl_weighted(plan);
+        if (!dc) return av == 0 ? launch_rows_mode<false, 0>(L, g, klw, s) : (av == 1 ? launch_rows_mode<false, 1>(L, g, klw, s) : launch_rows_mode<false, 2>(L, g, klw, s));
+        return av == 0 ? launch_rows_mode<true, 0>(L, g, klw, s) : (av == 1 ? launch_rows_mode<true, 1>(L, g, klw, s) : launch_rows_mode<true, 2>(L, g, klw, s));
+    }
+
+    static void tensors(const ILayout& L, GTensor* T) { make_tensors(L, T); }
+    static void gemms(const ILayout& L, GGemm* G) { make_gemms(L, G); }
+    static size_t partials_bytes(const ILayout& L) { return (size_t)L.rows_grid * ((L.mode & MODE_AUX) ? 6 : 5) * sizeof(double); }
+    // the eight loss scalars; under MODE_AUX the apply kernel corrects them first, and the running sums go through v_accum (extend_table)
+    static void extend_apply_args(const Plan* plan, const ILayout& L, ApplyArgs& a) {
+        if (L.mode & MODE_AUX) a.accum = nullptr;
+        a.info = 1; a.alpha = (float)plan->info_alpha; a.beta = (float)plan->info_beta; a.gamma = (float)plan->info_gamma;
+    }
+    // MODE_AUX: the fifth loss sum.  Then the weighted KL term of a finalising launch (train_generic.hip: MStep::extend_table); where the
+    // fifth sum is finalised too, its block runs last on the rebuilt ELBO and v_accum takes the running sums.
+    static void extend_table(const Plan* plan, const ILayout& L, char* ws, long long*, GApplyArgs& g) {
+        if (L.mode & MODE_AUX) {
+            g.v_partials = (const double*)(ws + L.o_partials) + 4 * L.rows_grid;
+            g.v_accum = (double*)(uintptr_t)plan->loss_accum;
+        }
+        if (!g.finalize || !kl_weighted(plan)) return;
+        g.kl_partials = (const double*)(ws + L.o_partials) + partials_k_off(L); g.kl_stride = 1; g.kl_w = (float)plan->kl_weight;
+        if (!(L.mode & MODE_AUX)) { g.kl_accum = g.a.accum; g.a.accum = nullptr; }
+    }
+};
 
 }  // namespace ti
 }  // namespace dvae
@@ -1000,112 +970,52 @@ extern "C" int dvae_train_info_plan_mode(int y_dim, int z_dim, int h1, int h2, i
     return 0;
 }
 
+// the entry points: train_step_host.hpp under this step's description
 extern "C" int dvae_train_info_repack(const dvae_train_info_plan_t* plan, const float* params, void* ws, void* stream) {
-    ILayout L;
-    if (int rc = plan_layout("train_info_repack", plan, L)) return rc;
-    DVAE_CHECK_ARG(params && ws, "train_info_repack: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    DVAE_HIP(hipMemsetAsync(ws, 0, (size_t)L.wpack_elems * 4, s));          // the padding of the packed copies
-    const ApplyArgs a = apply_args(plan, L, (float*)params, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, nullptr);
-    return launch_apply(plan, L, a, (char*)ws, false, true, false, s);
+    return step_repack<IStep>("train_info_repack", plan, params, ws, stream);
 }
 
 extern "C" int dvae_train_info_init(const dvae_train_info_plan_t* plan, const float* params, void* ws, void* stream) {
-    ILayout L;
-    if (int rc = plan_layout("train_info_init", plan, L)) return rc;
-    DVAE_CHECK_ARG(params && ws, "train_info_init: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    GGemm gm[I_NG];
-    make_gemms(L, gm);
-    const int order[I_NG] = {0, 7, 6, 4, 1, 5, 8, 11, 2, 3, 9, 12, 10};     // the widest inputs first: their items run longest
-    const std::vector<GItem> items = make_items(gm, order, I_NG, L.nslices);
-    DVAE_CHECK_ARG((int)items.size() == L.n_items, "train_info_init: %d items for a table of %d", (int)items.size(), L.n_items);
-    DVAE_HIP(hipMemcpyAsync((char*)ws + L.o_items, items.data(), items.size() * sizeof(GItem), hipMemcpyHostToDevice, s));
-    DVAE_HIP(hipMemsetAsync((char*)ws + L.o_partials, 0, (size_t)L.rows_grid * ((L.mode & MODE_AUX) ? 6 : 5) * sizeof(double), s));
-    DVAE_HIP(hipStreamSynchronize(s));                                      // the table leaves host memory that ends with this call
-    return dvae_train_info_repack(plan, params, ws, stream);
+    return step_init<IStep>("train_info_init", plan, params, ws, stream);
 }
 
 extern "C" int dvae_train_info_grads(const dvae_train_info_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
                                      const float* eps_noise, float elbo_eps, void* stream) {
-    ILayout L;
-    if (int rc = plan_layout("train_info_grads", plan, L)) return rc;
-    if (int rc = check_inputs("train_info_grads", plan, ws, x, ldx, y, ldy, eps_noise)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = launch_rows(plan, L, (char*)ws, x, ldx, y, ldy, eps_noise, elbo_eps, false, s)) return rc;
-    return launch_wgrad(plan, L, (char*)ws, x, ldx, y, ldy, s);
+    return step_grads<IStep>("train_info_grads", plan, ws, {x, ldx, y, ldy, eps_noise, elbo_eps}, stream);
 }
 
 extern "C" int dvae_train_info_apply(const dvae_train_info_plan_t* plan, float* params, float* m, float* v, void* ws, int step, double lr,
                                      double beta1, double beta2, double adam_eps, double grad_scale, float* losses8, void* stream) {
-    ILayout L;
-    if (int rc = plan_layout("train_info_apply", plan, L)) return rc;
-    DVAE_CHECK_ARG(params && m && v && ws && losses8, "train_info_apply: null pointer");
-    DVAE_CHECK_ARG(step >= 1, "train_info_apply: step %d (1-based)", step);
-    const ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, losses8);
-    return launch_apply(plan, L, a, (char*)ws, true, true, true, (hipStream_t)stream);
+    return step_apply<IStep>("train_info_apply", plan, {params, m, v, step, lr, beta1, beta2, adam_eps, grad_scale}, ws, {losses8, nullptr}, stream);
 }
 
 extern "C" int dvae_train_info_reduce(const dvae_train_info_plan_t* plan, void* ws, float* flat, int accumulate, float weight, float* losses8,
                                       void* stream) {
-    ILayout L;
-    if (int rc = plan_layout("train_info_reduce", plan, L)) return rc;
-    if (int rc = check_reduce_args("train_info_reduce", ws, flat, accumulate, weight)) return rc;
-    DVAE_CHECK_ARG(losses8, "train_info_reduce: null pointer");
-    GReduceArgs g;
-    memset(&g, 0, sizeof(g));
-    g.f.a = apply_args(plan, L, nullptr, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, losses8);
-    make_tensors(L, g.f.t);
-    if (L.mode & MODE_AUX) {                            // (as launch_apply)
-        g.f.v_partials = (const double*)((char*)ws + L.o_partials) + 4 * L.rows_grid;
-        g.f.v_accum = (double*)(uintptr_t)plan->loss_accum;
-    }
-    g.f.ws = (float*)ws; g.f.finalize = 1;
-    weighted_kl(plan, L, (char*)ws, g.f);
-    g.flat = flat; g.accumulate = accumulate; g.weight = weight;
-    return launch_reduce_table(g, (hipStream_t)stream);
+    return step_reduce<IStep>("train_info_reduce", plan, ws, flat, accumulate, weight, {losses8, nullptr}, stream);
 }
 
 extern "C" int dvae_train_info_apply_flat(const dvae_train_info_plan_t* plan, float* params, float* m, float* v, void* ws, const float* flat, int step,
                                           double lr, double beta1, double beta2, double adam_eps, double grad_scale, void* stream) {
-    ILayout L;
-    if (int rc = plan_layout("train_info_apply_flat", plan, L)) return rc;
-    if (int rc = check_apply_flat_args("train_info_apply_flat", params, m, v, ws, flat, step, lr, grad_scale)) return rc;
-    ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, nullptr);
-    a.slabs = flat; a.nslabs = 1;                       // the flat gradient is the one slab
-    return launch_apply(plan, L, a, (char*)ws, true, true, false, (hipStream_t)stream);
+    return step_apply_flat<IStep>("train_info_apply_flat", plan, {params, m, v, step, lr, beta1, beta2, adam_eps, grad_scale}, ws, flat, nullptr, stream);
 }
 
 extern "C" int dvae_train_info_apply_flat_clipped(const dvae_train_info_plan_t* plan, float* params, float* m, float* v, void* ws, const float* flat,
                                                   int step, double lr, double beta1, double beta2, double adam_eps, double grad_scale,
                                                   double max_norm, void* scratch, float* norm2_out, int32_t* skipped_counter, void* stream) {
-    ILayout L;
-    if (int rc = plan_layout("train_info_apply_flat_clipped", plan, L)) return rc;
-    if (int rc = check_apply_flat_args("train_info_apply_flat_clipped", params, m, v, ws, flat, step, lr, grad_scale)) return rc;
     const GClipHost clip = {grad_scale, max_norm, scratch, norm2_out, skipped_counter};
-    if (int rc = check_clip_args("train_info_apply_flat_clipped", flat, clip)) return rc;
-    ApplyArgs a = apply_args(plan, L, params, m, v, (char*)ws, true, step, lr, beta1, beta2, adam_eps, grad_scale, nullptr);
-    a.slabs = flat; a.nslabs = 1;                       // the flat gradient is the one slab
-    return launch_apply(plan, L, a, (char*)ws, true, true, false, (hipStream_t)stream, &clip);
+    return step_apply_flat<IStep>("train_info_apply_flat_clipped", plan, {params, m, v, step, lr, beta1, beta2, adam_eps, grad_scale}, ws, flat, &clip,
+                                  stream);
 }
 
 extern "C" int dvae_train_info_step(const dvae_train_info_plan_t* plan, float* params, float* m, float* v, void* ws, const float* x, int64_t ldx,
                                     const float* y, int64_t ldy, const float* eps_noise, float elbo_eps, int step, double lr, double beta1,
                                     double beta2, double adam_eps, float* losses8, void* stream) {
-    DVAE_CHECK_ARG(params && m && v && losses8, "train_info_step: null pointer");
-    DVAE_CHECK_ARG(step >= 1, "train_info_step: step %d (1-based)", step);
-    if (int rc = dvae_train_info_grads(plan, ws, x, ldx, y, ldy, eps_noise, elbo_eps, stream)) return rc;
-    return dvae_train_info_apply(plan, params, m, v, ws, step, lr, beta1, beta2, adam_eps, 1.0, losses8, stream);
+    return step_step<IStep>("train_info_step", "train_info_grads", "train_info_apply", plan, {params, m, v, step, lr, beta1, beta2, adam_eps, 1.0}, ws,
+                            {x, ldx, y, ldy, eps_noise, elbo_eps}, {losses8, nullptr}, stream);
 }
 
 extern "C" int dvae_train_info_eval(const dvae_train_info_plan_t* plan, void* ws, const float* x, int64_t ldx, const float* y, int64_t ldy,
                                     const float* eps_noise, float elbo_eps, float* losses8, void* stream) {
-    ILayout L;
-    if (int rc = plan_layout("train_info_eval", plan, L)) return rc;
-    if (int rc = check_inputs("train_info_eval", plan, ws, x, ldx, y, ldy, eps_noise)) return rc;
-    DVAE_CHECK_ARG(losses8, "train_info_eval: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = launch_rows(plan, L, (char*)ws, x, ldx, y, ldy, eps_noise, elbo_eps, true, s)) return rc;
-    const ApplyArgs a = apply_args(plan, L, nullptr, nullptr, nullptr, (char*)ws, false, 1, 0, 0, 0, 0, 1, losses8);
-    return launch_apply(plan, L, a, (char*)ws, false, false, true, s);
+    return step_eval<IStep>("train_info_eval", plan, ws, {x, ldx, y, ldy, eps_noise, elbo_eps}, {losses8, nullptr}, stream);
 }
+

@@ -1,8 +1,8 @@
 // What the fused train steps of any covered size share (train_generic.hip: the M1 / M2 step, dvae_train_generic_*; train_classifier.hip:
 // the label classifier's step, dvae_train_clf_*; train_info.hip: the M2_info step, dvae_train_info_*; include/dvae_train.h): the packed
 // weight copies in fragment order and the product that reads them, the tables the weight-gradient and optimizer launches read, and the
-// launches of those two kernels, which live in train_generic.hip and serve all three steps.  Below them: the plain structs of the
-// M1 / M2 step alone.
+// launches of those kernels, which live in train_tables.hip and serve all three steps.  The host code the three steps run around these
+// launches is train_step_host.hpp.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -23,6 +23,7 @@ constexpr int G_ROWS_GRID = 256, G_MAX_SLICES = 16;   // one rows workgroup per 
 inline int up16(int v) { return (v + 15) / 16 * 16; }
 inline int64_t al64(int64_t v) { return (v + 63) / 64 * 64; }        // floats: 256 bytes
 inline int64_t al256(int64_t v) { return (v + 255) / 256 * 256; }
+struct __attribute__((packed, aligned(4))) G4U { f32x4 v; };      // 16 bytes at dword alignment (rows of 513 floats)
 
 // element (row, k) of a matrix packed in fragment order [row tile][k block of 16][lane][4] with kb k blocks (mlp_generic.hip: lane l
 // holds row l & 15, inputs 16 b + 4 i + (l >> 4))
@@ -109,7 +110,7 @@ inline void choose_slices(int64_t B, int row_tiles, int ksplit_hint, int64_t& sl
     nslices = (int)((B + slice_frames - 1) / slice_frames);
 }
 
-// weight-gradient kernel (train_generic.hip: train_generic_wgrad_kernel)
+// weight-gradient kernel (train_tables.hip: train_generic_wgrad_kernel)
 struct GWgradArgs {
     const float* x; int64_t ldx;
     const float* y; int64_t ldy;
@@ -122,7 +123,7 @@ struct GWgradArgs {
     int64_t toff[G_NT];
 };
 
-// apply kernel (train_generic.hip: train_generic_apply_kernel): optimizer step, both packed copies, loss scalars; with `cnt_partials`
+// apply kernel (train_tables.hip: train_generic_apply_kernel): optimizer step, both packed copies, loss scalars; with `cnt_partials`
 // also the confusion counts of the classifier step: [cnt_wgs][4] integers summed in workgroup order into counts4 (and added to cnt_accum);
 // with `v_partials` (the M2_info step whose adversarial term is not a cross entropy, train_info.hip) a fifth loss sum per rows workgroup
 // (a.npartials <= G_ROWS_GRID of them): aux_enc_loss = beta V replaces beta BCE in the loss scalars, and the running sums go to v_accum
@@ -143,7 +144,7 @@ struct GApplyArgs {
     int kl_stride; float kl_w;
 };
 
-// reduce kernel (train_generic.hip: train_generic_reduce_kernel), between _grads and _apply_flat: flat = [flat +] weight * (the slabs of
+// reduce kernel (train_tables.hip: train_generic_reduce_kernel), between _grads and _apply_flat: flat = [flat +] weight * (the slabs of
 // f.a summed in slab order), zeros in the alignment gaps between the tensors of f.t; one more workgroup finalises the micro-batch's loss
 // scalars (and counts) exactly as the apply kernel's finalising workgroup does (f.adam is unused, f.finalize 1)
 struct GReduceArgs {
@@ -154,7 +155,7 @@ struct GReduceArgs {
 };
 
 // Global-norm clipping of the flat gradient (include/dvae_train.h: dvae_train_*_apply_flat_clipped): two launches, no host round trip.
-//   * norm kernel (train_generic.hip: train_generic_gradnorm_kernel): workgroup c owns chunk c = floats [c G_NORM_CHUNK, (c + 1)
+//   * norm kernel (train_tables.hip: train_generic_gradnorm_kernel): workgroup c owns chunk c = floats [c G_NORM_CHUNK, (c + 1)
 //     G_NORM_CHUNK) of the flat gradient, whatever the grid of any other launch or the part: a thread loads four 16-byte pieces,
 //     squares and adds them in double in address order (a float32 square is exact in double), then lanes (xor butterfly: every lane
 //     forms the same tree), waves in order, and partials[c] is written.  Floats that belong to no tensor (the alignment gaps) count
@@ -197,33 +198,6 @@ int check_apply_flat_args(const char* who, const float* params, const float* m, 
 // dynamic LDS past the default 64 KB limit for a rows kernel: raised once per device (done: the caller's flags, one per device)
 int raise_lds_limit(const void* kernel, const char* name, int64_t lds_bytes, bool (&done)[64]);
 constexpr int64_t G_LDS_MAX = 160 * 1024;
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// the M1 / M2 step
-struct GLayout {
-    int y, z, h1, h2, yp, zp, h1p, h2p, hm;     // sizes and their multiples of 16 (yp 0 without labels); hm = max(h1p, h2p, zp)
-    int dec;                                    // M2_DEC (dvae_module_generic_plan): the encoder reads x alone.  In the four bytes that padded hm: no other field moves
-    // packed copies, float offsets from the start of the workspace: forward [out tile][k block], x / z block and label block apart;
-    // the heads are one matrix (mu rows 0 .. z - 1, log_var rows zp .. zp + z - 1)
-    int64_t W1x, W1y, W2, Wh, D1z, D1y, D2, D3;
-    int64_t D3T, D2T, D1zT, WhT, W2T;           // the transposed copies of the backward-data products
-    int64_t b1, b2, bh, bd1, bd2, bd3;          // zero-padded biases
-    int64_t wpack_elems;
-    // the stash of one frame (floats): layer inputs, then the pre-activation gradients
-    int S, s_h1e, s_h2e, s_z, s_d1, s_d2, s_pe1, s_pe2, s_ph, s_pd1, s_pd2, s_da;
-    // workspace (bytes)
-    int64_t o_items, o_partials, o_stash, o_grads, ws_bytes;
-    int64_t B, Bp, tiles, rows_grid, slice_frames, n_params;
-    int nslices, n_items;
-    int64_t lds_bytes;
-    int64_t toff[G_NT];
-    int trows[G_NT], tcols[G_NT];
-    // std_norm (dvae_train_generic_plan_norm): encoder layer 1 reads the standardised x; its stash block of GXP columns sits behind s_da, so
-    // every other column, S and the workspace of a plan without std_norm are what they are without these two fields
-    int norm, s_xn;
-};
-
-static_assert(offsetof(GLayout, W1x) == 40 && offsetof(GLayout, dec) == 36, "dec sits in the padding behind hm: the kernel arguments of the train step do not move");
 
 }  // namespace tg
 }  // namespace dvae

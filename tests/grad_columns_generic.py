@@ -21,8 +21,8 @@ Truth: the cases module's own oracle run in float64 on all B frames (M2_info: g1
 
 The float32 restatement, from the oracle and never from the library, in two summation orders; its figure is the larger of the two:
   numpy      run(case, B, np.float32) of the cases module: blocked GEMMs, pairwise sums.
-  k-steps    the kernels' order through vae_oracle.gemm_hook (StepOrderF32), read from csrc/train_generic.hpp (tg_gemm) and
-             csrc/train_generic.hip (train_generic_wgrad_kernel, slab_sum_at's order, train_generic_reduce_kernel):
+  k-steps    the kernels' order through vae_oracle.gemm_hook (StepOrderF32), read from csrc/train_tables.hpp (tg_gemm) and
+             csrc/train_tables.hip (train_generic_wgrad_kernel, slab_sum_at's order, train_generic_reduce_kernel):
              * a forward or backward-data product is ONE float32 accumulator over k ascending, one mfma_f32_16x16x4f32 per four k
                (frag_pos: MFMA i of k block b holds k = 16 b + 4 i .. + 3).  [x | y] and [z | y] are two packed blocks, each padded with
                zeros to a multiple of 16, summed into the same accumulator x (z) first: the groups of four start again at the first
@@ -107,7 +107,7 @@ def case_label(kind, case, mode, B, ksplit, family="bench", micro=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# the plan's frame slices (csrc/train_generic.hpp: choose_slices)
+# the plan's frame slices (csrc/train_tables.hpp: choose_slices)
 # ---------------------------------------------------------------------------------------------------------------------------------
 
 def slice_plan(B, ksplit):

@@ -9,7 +9,7 @@ the drop-in modules in the CPU test.
 
 Float32 restatement (from the oracle, never from the library): the same composition in float32 in two summation orders, the larger
 figure of the two -- numpy's, and the kernels' k-step order with fused multiply-adds, grad_columns_generic.StepOrderF32 on the plan's
-frame slices (slice_plan below restates choose_slices of csrc/train_generic.hpp; the CPU test holds it against the library's plans).
+frame slices (slice_plan below restates choose_slices of csrc/train_tables.hpp; the CPU test holds it against the library's plans).
 tanh and exp are float32 numpy in both.  The path is exact fp32: there is no policy term.
 
 Statistics.  module_cases.output_figures / grad_figures: log r; mu, log_var, z over the tensor maximum; every gradient per input column,
@@ -64,7 +64,7 @@ def case_id(case, B, key=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# the plan's frame slices (csrc/train_generic.hpp: choose_slices, gemm_items; csrc/train_generic.hip: make_gemms)
+# the plan's frame slices (csrc/train_tables.hpp: choose_slices, gemm_items; csrc/train_generic.hip: make_gemms)
 # ---------------------------------------------------------------------------------------------------------------------------------
 
 def slice_plan(case, B, ksplit=0):

@@ -1,4 +1,4 @@
-"""Gradient accumulation on the any-size fused train steps (disentangled-vae_amd/accumulate.py: AccumulatedStep; csrc/train_generic.hip:
+"""Gradient accumulation on the any-size fused train steps (disentangled-vae_amd/accumulate.py: AccumulatedStep; csrc/train_tables.hip:
 train_generic_reduce_kernel, the apply kernel on the flat gradient), one process.
 
 A. Bit for bit.  K in {2, 4} micro-batches of 48 frames on a trainer built with ksplit=1 equal ONE step() of a trainer with batch 48 K

@@ -1,4 +1,4 @@
-"""Global-norm clipping on the device in the any-size fused train steps (csrc/train_generic.hip: train_generic_gradnorm_kernel,
+"""Global-norm clipping on the device in the any-size fused train steps (csrc/train_tables.hip: train_generic_gradnorm_kernel,
 train_generic_apply_clipped_kernel; include/dvae_train.h: dvae_train_*_apply_flat_clipped; disentangled-vae_amd/clip.py, accumulate.py).
 Truth: tests/clip_ref.py (held against torch in tests/test_train_clip_cpu.py); update bounds: tests/adam_bounds.py.
 

@@ -1,5 +1,5 @@
 """The fused any-size train steps under a weighted KL term (GenericTrainer / InfoTrainer(..., kl_weight=, kl_warmup=, kl_floor=);
-csrc/train_generic.hip and csrc/train_info.hip: the KLW instantiations of the rows kernels, the finalising workgroup of the apply and
+csrc/train_generic.hip and csrc/train_info.hip: the KLW instantiations of the rows kernels; csrc/train_tables.hip: the finalising workgroup of the apply and
 reduce kernels) against the float64 truth of tests/kl_weight_cases.py:
 
     loss = recon + w mean_b sum_j max(k_bj, floor),   k_bj = -0.5 (lv_bj - mu_bj^2 - exp(lv_bj)),   torch.clamp's gradient.

@@ -44,7 +44,7 @@ The smallest stale_ratio seen: 272 (tail.step on 20 frames after main.step), 387
 
 Scratch breakages, one at a time, nothing of them committed; each leaves every address inside its allocation.  This module and tests/test_gpu_train_generic.py,
 tests/test_gpu_train_columns.py, tests/test_gpu_frames.py were RUN once against each:
-  a  apply_body (csrc/train_generic.hip) skips the write of a tensor's transposed copy (d.t0) when g.adam is set
+  a  apply_body (csrc/train_tables.hip) skips the write of a tensor's transposed copy (d.t0) when g.adam is set
        this module: 23 of 41 fail, all at step 2 under A, 4.8e4 ... 1.9e5 column bounds (B and C pass: the forward copies are fresh).
        Of the 18 that pass, three are the fork interleavings (every step there follows another trainer's, so the copies are repacked whole);
        the other 15 -- the reference-size trainer, the module engines -- run none of the broken code.

@@ -45,7 +45,7 @@ tests/test_gpu_fused_columns.py:
   Trainer against its packed twin (printed, not held): in all 33 runs NO gradient element and NO loss scalar differed by a bit.
 No NaN reached a result anywhere: no kernel's result depends on memory outside the view.
 
-Scratch breakages of csrc/train_generic.hip (one at a time in a scratch copy, each only SHRINKS a stride, so every read stays inside
+Scratch breakages of csrc/train_generic.hip and train_tables.hip (one at a time in a scratch copy, each only SHRINKS a stride, so every read stays inside
 the tensor's allocation; nothing of them committed; this module run once against each library):
   a  `513` in place of `g.ldx` in the raw-x re-read of the std_norm output layer (train_generic_rows_kernel)
        4 of 94 fail: the four std_norm tests, and nothing else -- as expected.

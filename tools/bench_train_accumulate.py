@@ -1,4 +1,4 @@
-"""Gradient accumulation on the any-size fused train steps (disentangled-vae_amd/accumulate.py; csrc/train_generic.hip:
+"""Gradient accumulation on the any-size fused train steps (disentangled-vae_amd/accumulate.py; csrc/train_tables.hip:
 train_generic_reduce_kernel) on the MI355X.
 
     python tools/bench_train_accumulate.py [--out profiles/train_accumulate.json] [--reps 10] [--trace-stats kernel_stats.csv]
@@ -22,7 +22,7 @@ inputs are resident on the device, the noise is passed in.
 
     python tools/bench_train_accumulate.py --clip [--out profiles/train_clip.json] [--reps 20]
 
---clip measures what clipping the global gradient norm on the device costs (csrc/train_generic.hip: train_generic_gradnorm_kernel,
+--clip measures what clipping the global gradient norm on the device costs (csrc/train_tables.hip: train_generic_gradnorm_kernel,
 train_generic_apply_clipped_kernel), against the unclipped call in the same run, alternating, at M2 z 32 / h (256, 64) / y 1 and the
 largest M2_info geometry, 128 and 8192 frames: the optimizer launch of apply() on the flat gradient of one micro-batch against the two
 launches of apply(max_norm=inf), and step() (three launches) against step(max_norm=inf) (five: the reduce and the norm launch more).
